@@ -9,7 +9,13 @@ driver launches this file under torch.distributed.run: the 10 kb chunk is broadc
 RCCL/xGMI once, every rank aligns its own shard of reads (weak scaling, no data-path collective), the
 timed region is bracketed by barrier + synchronize and the max over ranks is reported.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` and the
+figures derived from the timed steps themselves (kernel_ms, roofline).  Every other measurement and check -- the device-resident rate,
+the bit-exactness check against the CPU oracle, cold_plan, host_entry, the extra configurations, cpu_baseline, and under --gpus N the
+ordered gather and the one_process leg -- runs only with --full (--no-cpu / --no-host / --no-extras / --verify narrow it down).
+--dump-outputs DIR writes the results of the last timed step as float64 .npy files (see dump_outputs).
+
+Objects of the line:
   roofline      algorithmic bytes (n + m + ceil(b*nm/8) + ceil(b*(n+m)/8) + 8 + 16|cigar| per pair, b = 6 bits affine /
                 2 bits constant gap) / average duration of the dominant kernel's launches (HIP events on the launch stream, inside
                 the library); frac = that kernel alone, frac_step = the whole step, both against the 8.0 TB/s spec peak
@@ -109,6 +115,31 @@ def make_long_workload(seed, n_pairs, n=20000, m=100000):
 def algorithmic_bytes(n, m, bits, pairs, total_ops):
     per_pair = n + m + (n * m * bits + 7) // 8 + ((n + m) * bits + 7) // 8 + 8
     return per_pair * pairs + 16 * total_ops
+
+
+DUMP_BYTES = 60 * 1000 * 1000  # what --dump-outputs may write in all (64 MB cap, .npy headers included)
+
+
+def dump_outputs(dirname, scores, ops, off, seed=0):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- per pair the score and its CIGAR runs -- as float64 .npy
+    files: pairs (indices of the pairs written), scores, cigar_runs (runs per pair), cigar_run_length + cigar_op (the runs of those pairs,
+    concatenated in pair order).  When every pair does not fit into DUMP_BYTES, the pairs of a permutation seeded by `seed` are taken in its
+    order while they fit (pairs.npy is sorted), so two builds that compute the same results write the same sample."""
+    off = np.asarray(off, dtype=np.int64)
+    runs = np.diff(off)
+    cost = 24 + 16 * runs  # pair index, score, run count + (run length, op) per run, 8 bytes each
+    if int(cost.sum()) <= DUMP_BYTES:
+        pick = np.arange(runs.shape[0])
+    else:
+        order = np.random.default_rng(seed).permutation(runs.shape[0])
+        pick = np.sort(order[:int(np.searchsorted(np.cumsum(cost[order]), DUMP_BYTES, side="right"))])
+    cnt = runs[pick]
+    sel = ops[np.repeat(off[pick] - (np.cumsum(cnt) - cnt), cnt) + np.arange(int(cnt.sum()))]
+    os.makedirs(dirname, exist_ok=True)
+    for name, arr in (("pairs", pick), ("scores", np.asarray(scores)[pick]), ("cigar_runs", cnt),
+                      ("cigar_run_length", sel["run_length"]), ("cigar_op", sel["op"])):
+        np.save(os.path.join(dirname, name + ".npy"), np.asarray(arr, dtype=np.float64))
+    return {"dir": dirname, "pairs": int(pick.shape[0]), "of_pairs": int(runs.shape[0]), "runs": int(cnt.sum())}
 
 
 def kernel_source_hash():
@@ -546,10 +577,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--pairs", type=int, default=0, help="pairs per GPU per step (default: 100 k for the C2 series, 2048 for --series long)")
     ap.add_argument("--ws-gb", type=float, default=150.0, help="workspace limit per GPU")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-host", action="store_true", help="skip the host_entry and cold_plan legs")
-    ap.add_argument("--no-extras", action="store_true", help="skip the north_star_1M / c3 / c5 / n1 / gsw_reads / long_pairs sub-objects (and one_process under --gpus N)")
-    ap.add_argument("--verify", type=int, default=-1, help="pairs checked bit-exactly against the oracle after timing (default 32; 2 for --series long)")
+    ap.add_argument("--full", action="store_true", help="after the headline, every other leg and check: device-resident rate, oracle check, cold_plan, "
+                                                         "host_entry, extras, cpu_baseline; under --gpus N the ordered gather and one_process")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the results of the last timed step to DIR/<name>.npy (rank 0's pairs)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-host", action="store_true", help="with --full: skip the host_entry and cold_plan legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the north_star_1M / c3 / c5 / n1 / gsw_reads / long_pairs sub-objects (and one_process under --gpus N)")
+    ap.add_argument("--verify", type=int, default=-1, help="pairs checked bit-exactly against the oracle after timing (default: 32 with --full, 2 for --series long; 0 without)")
     ap.add_argument("--dist-backend", default="nccl", help="debug: 'gloo' lets several ranks share one GPU (with --share-gpu)")
     ap.add_argument("--share-gpu", action="store_true", help="debug: every rank uses cuda:0 (flow check of the N>1 path on a 1-GPU box)")
     ap.add_argument("--one-process", action="store_true", help="run the one_process leg even with --share-gpu / --no-extras (contexts on cuda:0, peer copies)")
@@ -583,7 +617,8 @@ def main():
     _lib.check(L.gnx_init(dev_index, int(ws_gb * (1 << 30))))
 
     n_pairs = args.pairs or S["pairs"]
-    n_verify = args.verify if args.verify >= 0 else (2 if args.series == "long" else 32)
+    n_verify = args.verify if args.verify >= 0 else (0 if not args.full else 2 if args.series == "long" else 32)
+    checked = args.full or n_verify > 0  # bit_exact_sample is null when nothing was checked
     scores = align.HumanChimpTwoScoreMatrix
     if S["shared"]:
         # rank 0 owns the chunk; everyone gets it by broadcast (RCCL over xGMI when world > 1)
@@ -691,19 +726,21 @@ def main():
         got_main = last.copy()
         last.free()
         step_total_ops = int(got_main[2][-1])
-        # the same batch with inputs and outputs resident in HBM (gnx_align_batch_device), timed the same way, per rank
-        size_device_buffers()
-        for _ in range(args.warmup):
-            step()
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        dev_dom_ms, dev_dom_launches = 0.0, 0
-        for _ in range(args.steps):
-            step()
-            tmd = _lib.get_timing()
-            dev_dom_ms += tmd["dominant_ms"]; dev_dom_launches += tmd["dominant_launches"]
-        torch.cuda.synchronize()
-        dt_dev = time.perf_counter() - t1
+        dt_dev = None
+        if args.full:
+            # the same batch with inputs and outputs resident in HBM (gnx_align_batch_device), timed the same way, per rank
+            size_device_buffers()
+            for _ in range(args.warmup):
+                step()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            dev_dom_ms, dev_dom_launches = 0.0, 0
+            for _ in range(args.steps):
+                step()
+                tmd = _lib.get_timing()
+                dev_dom_ms += tmd["dominant_ms"]; dev_dom_launches += tmd["dominant_launches"]
+            torch.cuda.synchronize()
+            dt_dev = time.perf_counter() - t1
     else:
         size_device_buffers()
         for _ in range(args.warmup):
@@ -756,9 +793,12 @@ def main():
         return bool(np.array_equal(got[0], exp[0]) and np.array_equal(got[2], exp[2]) and np.array_equal(got[1]["run_length"], exp[1]["run_length"])
                     and np.array_equal(got[1]["op"], exp[1]["op"]))
 
-    # ---- after the timed region: verification + the other legs (rank 0) ----
+    # ---- after the timed region: the outputs, verification + the other legs (rank 0) ----
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, *fetch(n_pairs))
     ok = True
-    gathered_pairs = n_pairs
+    gathered_pairs = n_pairs if world == 1 else None  # (N > 1: set by the gather, which runs with --full)
     gather_order_ok = None
     if n_verify > 0:
         import oracle
@@ -769,6 +809,7 @@ def main():
         f = torch.tensor([1 if ok else 0], dtype=torch.int32, device=dev)
         dist.all_reduce(f, op=dist.ReduceOp.MIN)
         ok = bool(f.item())
+    if world > 1 and args.full:
         # final gather of scores / CIGAR offsets / CIGAR blob on rank 0, in input order (outside the timed region)
         n_ops_local = int(d_off[n_pairs].item())
         gathered = shard.gather_results(d_score, d_ops[: n_ops_local * 16], d_off, dst=0)
@@ -837,9 +878,7 @@ def main():
             "value_definition": ("SURVEY 8d: sum n*m over pairs / wall time of K calls of the host-buffer entry point (H2D of reads, windows and offset tables + plans + "
                                  "kernels + D2H of scores / offsets / CIGAR runs into pinned host arrays); the chunk upload is part of every call")
                                 if host_timed else "inputs and outputs resident in HBM (gnx_align_batch_device)",
-            "value_device_resident": cells_per_step / world * args.steps / dt_dev, "ms_per_step_device_resident": dt_dev / args.steps * 1e3,
-            "value_device_resident_note": "rank 0's GPU alone, same batch through gnx_align_batch_device, K steps timed the same way",
-            "bit_exact_sample": ok, "bit_exact_pairs_checked": int(min(n_verify, n_pairs)),
+            "bit_exact_sample": ok if checked else None, "bit_exact_pairs_checked": int(min(n_verify, n_pairs)),
             "kernel_ms": {"all_fill_kernels_per_step": float(np.mean(fill_ms)), "traceback_and_rest_per_step": float(np.mean(tb_ms)),
                           "dominant_kernel_per_step": dom_ms / args.steps, "path": path, "launches_per_step": launches / args.steps},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
@@ -851,6 +890,11 @@ def main():
                          "achieved_step": achieved_step, "frac_step": achieved_step / HBM_PEAK_GBS,
                          "frac_step_vs_measured_copy_bw": achieved_step / HBM_COPY_GBS},
         }
+        if dt_dev is not None:
+            out.update({"value_device_resident": cells_per_step / world * args.steps / dt_dev, "ms_per_step_device_resident": dt_dev / args.steps * 1e3,
+                        "value_device_resident_note": "rank 0's GPU alone, same batch through gnx_align_batch_device, K steps timed the same way"})
+        if dumped:
+            out["outputs_dumped"] = dumped
         if pmc and pmc.get("valu_insts_per_pair"):
             # second ceiling: VALU issue, 256 CU x 4 SIMD x 32 lanes x 2.4 GHz = 78.6e12 lane-ops/s
             vi = pmc["valu_insts_per_pair"]
@@ -870,7 +914,7 @@ def main():
             rv = out.setdefault("roofline_valu", {"bound": "valu"})
             rv.update({"floor_ms": floor_ms, "frac_of_floor": floor_ms / fill_avg_ms, "floor_model": "5 instructions per cell x 1.813 ns per wave-instruction slot and SIMD "
                        "(measured issue rate of add_sdwa, max3, add, max, max at >= 2 waves per SIMD, profiles/r3_valu_ubench4.txt) / (4 SIMDs x %d CUs)" % (n_simd // 4)})
-        if not args.no_host and world == 1:
+        if args.full and not args.no_host and world == 1:
             # cold plans: a call of another shape first, so that the next full call builds and uploads its plans afresh
             step(max(n_pairs - 64, 1))
             torch.cuda.synchronize()
@@ -887,7 +931,7 @@ def main():
                                      "equals_device_results": same_h,
                                      "includes": "H2D of reads, windows and offset tables, plans, kernels, D2H of scores / offsets / CIGAR runs into pinned host arrays (gnx_free)"}
                 out["value_survey_8d"] = value  # (kept under its round-3 name: it is `value` now)
-        if not args.no_extras and world == 1 and args.series == "affine":
+        if args.full and not args.no_extras and world == 1 and args.series == "affine":
             d_ops = None  # the extra legs need the memory (C3: 10 M reads of results on the device; C5: 70 GB of snapshots)
             torch.cuda.empty_cache()
             failed = []
@@ -903,7 +947,7 @@ def main():
                 out[name]["leg_wall_s"] = time.perf_counter() - t1
             out["extras_failed"] = failed
             _lib.check(L.gnx_init(dev_index, int(ws_gb * (1 << 30))))
-        if not args.no_cpu and world == 1 and args.series in ("affine", "long"):
+        if args.full and not args.no_cpu and world == 1 and args.series in ("affine", "long"):
             cb = cpu_baseline(S, scores, pair_lists, n_pairs)
             exp, k = cb.pop("_oracle")
             # the oracle results of the baseline sample double as the bit-exactness check of the first k GPU results
@@ -911,9 +955,9 @@ def main():
             ok = ok and ok_k
             out["bit_exact_pairs_checked"] = int(max(k, min(n_verify, n_pairs)))
             out["cpu_baseline"] = cb
-        out["bit_exact_sample"] = ok
+        out["bit_exact_sample"] = ok if checked else None
     # ---- N > 1: the one-process flow of the C ABI (gnx_init_devices) on the same GPUs, after every rank has given its memory back ----
-    if world > 1 and S["shared"] and ((not args.no_extras and not args.share_gpu) or args.one_process):
+    if world > 1 and S["shared"] and ((args.full and not args.no_extras and not args.share_gpu) or args.one_process):
         d_ops = d_score = d_off = d_reads = d_chunk = d_as = d_al = d_bs = d_bl = None  # (referenced by the closures above: release, do not del)
         L.gnx_shutdown()
         torch.cuda.empty_cache()

@@ -13,6 +13,9 @@ The GPU box has no /root/reference, so everything the tests need is committed he
                                           out_{hg38,rheMac10}_gap.{1,2}.expected.bed}
       cmd/cigarToBed/testdata/{firstTest,sethvsraven}/*
       cmd/globalAlignment/testdata/*.fa
+  * shim_ref_digest.json -- what tests/test_shim_static.py checks the cgo shim against: per file of the reference's align / genomeGraph
+      packages its declarations, imports and the names it uses, and sha256 digests of the signatures / types the shim keeps
+      (test_shim_static.reference_digest)
 No reference source text is copied.
 """
 import json
@@ -108,6 +111,11 @@ def main():
         for nm in names:
             shutil.copyfile(os.path.join(REF, d, nm), os.path.join(dst, nm))
             os.chmod(os.path.join(dst, nm), 0o644)
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_shim_static
+    with open(os.path.join(HERE, "shim_ref_digest.json"), "w") as f:
+        json.dump(test_shim_static.reference_digest(REF), f, indent=1, sort_keys=True)
+        f.write("\n")
     print("golden fixtures written under", HERE)
 
 

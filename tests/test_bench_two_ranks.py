@@ -28,7 +28,7 @@ def test_bench_two_ranks_share_one_gpu(gpu_lib):
         env.pop("GNX_FP_SMALL", None)
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
                os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--dist-backend", "gloo", "--pairs", str(pairs), "--steps", "2", "--warmup", "1",
-               "--no-extras", "--no-cpu", "--one-process", "--ws-gb", "16"]
+               "--full", "--no-extras", "--no-cpu", "--one-process", "--ws-gb", "16"]
         r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-3000:]
         line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -56,7 +56,7 @@ def test_bench_two_ranks_long_series(gpu_lib):
         env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
                os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--dist-backend", "gloo", "--series", "long", "--pairs", str(pairs), "--steps", "1", "--warmup", "1",
-               "--no-extras", "--no-cpu", "--verify", "1", "--ws-gb", "16"]
+               "--full", "--no-extras", "--no-cpu", "--verify", "1", "--ws-gb", "16"]
         r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]
         out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

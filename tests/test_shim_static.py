@@ -1,11 +1,14 @@
 """Static checks of the cgo shim (shim/) -- the image has no Go toolchain, so what `go build -tags hip` would reject is checked here.
 
-CPU-only.  The checks that need the reference's sources (`/root/reference`, build container only) replay shim/manifest.json --
-which files get `//go:build !hip`, which declarations move, which shim files are added -- and assert that the resulting package
-is closed: every package-level identifier a kept file uses is declared by a kept file or by the shim, nothing
-is declared twice, imports stay used, replaced functions keep the reference's signatures.  The checks against include/gnx_align.h
+CPU-only.  The checks against the reference's packages replay shim/manifest.json -- which files get `//go:build !hip`, which
+declarations move, which shim files are added -- and assert that the resulting package is closed: every
+package-level identifier a kept file uses is declared by a kept file or by the shim, nothing is declared twice, imports stay used,
+replaced functions keep the reference's signatures.  The reference side of those checks is tests/golden/shim_ref_digest.json: per
+reference file its declarations, imports and the names it uses, and sha256 digests of the replaced signatures / types -- no source
+text -- written from a reference checkout by tests/golden/make_golden.py (reference_digest below).  The checks against include/gnx_align.h
 (every C symbol the shim binds exists, with the same number of arguments; every GNX_* constant and struct field exists) run anywhere.
 """
+import hashlib
 import json
 import os
 import re
@@ -13,9 +16,8 @@ import re
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 MANIFEST = json.load(open(os.path.join(ROOT, "shim", "manifest.json")))
-needs_ref = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "align")), reason="reference sources are only in the build container")
+DIGEST_FILE = os.path.join(ROOT, "tests", "golden", "shim_ref_digest.json")
 
 GO_KEYWORDS = set("break default func interface select case defer go map struct chan else goto package switch const fallthrough if range "
                   "type continue for import return var".split())
@@ -212,17 +214,76 @@ def norm_sig(header):
     return re.sub(r"\s+", "", header)
 
 
+def sha(text):
+    return hashlib.sha256(text.encode()).hexdigest()
+
+
+def type_body(f, nm):
+    _, a, _, _ = f.decls[nm]
+    k = f.code.index("{", a)
+    return norm_sig(f.code[k:match_close(f.code, k, "{", "}") + 1])
+
+
+def _file_entry(f):
+    return {"decls": {nm: d[0] for nm, d in sorted(f.decls.items())}, "imports": {nm: v[0] for nm, v in sorted(f.imports.items())},
+            "identifiers": sorted(f.identifiers()), "local_names": sorted(f.local_names()), "selectors": sorted(f.selectors())}
+
+
+def reference_digest(ref_root):
+    """What the checks below need of the reference's packages, from a reference checkout: per manifest step the package's files (after the
+    step's exclusions and moves) as declaration / import / name sets, and the digests of the signatures and types the shim must keep"""
+    out = {}
+    for pkg, pspec in MANIFEST["packages"].items():
+        ref_dir = os.path.join(ref_root, pkg)
+        files = [GoFile(os.path.join(ref_dir, f)) for f in sorted(os.listdir(ref_dir)) if f.endswith(".go")]
+        files = [f for f in files if f.package == pkg]  # drops external test packages (package x_test), if any
+        steps = {}
+        for step, spec in pspec["steps"].items():
+            kept = {}
+            for f in files:
+                if f.name in spec["exclude_files"]:
+                    continue
+                mv = spec["move_decls"].get(f.name)
+                kept[f.name] = _file_entry(f.without(mv["decls"], mv["imports"]) if mv else f)
+            steps[step] = kept
+        non_test = [f for f in files if not f.name.endswith("_test.go")]
+        decls = {}
+        for f in non_test:
+            decls.update(f.decls)
+        out[pkg] = {"files": {f.name: {k: v for k, v in _file_entry(f).items() if k in ("decls", "imports")} for f in files},
+                    "steps": steps,
+                    "signatures": {nm: [decls[nm][0], sha(norm_sig(decls[nm][3]))] for nm in pspec["same_signature"]},
+                    "types": {nm: sha(type_body(next(f for f in non_test if nm in f.decls), nm)) for nm in pspec["same_type"]}}
+    return out
+
+
+class RefFile:
+    """a reference file as the digest holds it: the parts of GoFile's interface the checks use"""
+
+    def __init__(self, name, entry):
+        self.name = name
+        self.decls = entry["decls"]
+        self.imports = {nm: (path, None, None) for nm, path in entry["imports"].items()}
+        self._entry = entry
+
+    def identifiers(self):
+        return set(self._entry["identifiers"])
+
+    def local_names(self):
+        return set(self._entry["local_names"])
+
+    def selectors(self):
+        return set(self._entry["selectors"])
+
+
+DIGEST = json.load(open(DIGEST_FILE))
+
+
 def load_package(pkg, step):
     spec = MANIFEST["packages"][pkg]["steps"][step]
-    ref_dir = os.path.join(REF, pkg)
-    ref_files = [GoFile(os.path.join(ref_dir, f)) for f in sorted(os.listdir(ref_dir)) if f.endswith(".go")]
-    ref_files = [f for f in ref_files if f.package == pkg]  # drops external test packages (package x_test), if any
-    kept = []
-    for f in ref_files:
-        if f.name in spec["exclude_files"]:
-            continue
-        mv = spec["move_decls"].get(f.name)
-        kept.append(f.without(mv["decls"], mv["imports"]) if mv else f)
+    ref_files = [RefFile(nm, e) for nm, e in sorted(DIGEST[pkg]["files"].items())]
+    kept = [RefFile(nm, e) for nm, e in sorted(DIGEST[pkg]["steps"][step].items())]
+    assert sorted(f.name for f in kept) == sorted(f.name for f in ref_files if f.name not in spec["exclude_files"])
     shim = [GoFile(os.path.join(ROOT, "shim", pkg, s)) for s in spec["shim_files"]]
     return spec, ref_files, kept, shim
 
@@ -230,7 +291,6 @@ def load_package(pkg, step):
 STEPS = [(p, s) for p in MANIFEST["packages"] for s in MANIFEST["packages"][p]["steps"]]
 
 
-@needs_ref
 @pytest.mark.parametrize("pkg,step", STEPS)
 def test_package_is_closed_under_the_hip_tag(pkg, step):
     spec, ref_files, kept, shim = load_package(pkg, step)
@@ -275,32 +335,22 @@ def test_package_is_closed_under_the_hip_tag(pkg, step):
             assert nm in new, "%s uses %s, which the recipe removes and nothing re-declares" % (f.name, nm)
 
 
-@needs_ref
 @pytest.mark.parametrize("pkg", list(MANIFEST["packages"]))
 def test_replaced_functions_keep_their_signatures(pkg):
     spec = MANIFEST["packages"][pkg]
-    ref_dir = os.path.join(REF, pkg)
-    ref = {}
-    for fn in sorted(os.listdir(ref_dir)):
-        if fn.endswith(".go") and not fn.endswith("_test.go"):
-            ref.update(GoFile(os.path.join(ref_dir, fn)).decls)
+    ref = DIGEST[pkg]
+    shim_dir = os.path.join(ROOT, "shim", pkg)
+    shim_files = [GoFile(os.path.join(shim_dir, fn)) for fn in sorted(os.listdir(shim_dir)) if fn.endswith(".go")]
     shim = {}
-    for fn in sorted(os.listdir(os.path.join(ROOT, "shim", pkg))):
-        if fn.endswith(".go"):
-            shim.update(GoFile(os.path.join(ROOT, "shim", pkg, fn)).decls)
+    for f in shim_files:
+        shim.update(f.decls)
     for nm in spec["same_signature"]:
         assert nm in shim, "shim does not declare %s" % nm
-        assert ref[nm][0] == shim[nm][0] == "func"
-        assert norm_sig(ref[nm][3]) == norm_sig(shim[nm][3]), "%s: signature differs\n ref : %s\n shim: %s" % (nm, ref[nm][3], shim[nm][3])
+        assert ref["signatures"][nm][0] == shim[nm][0] == "func"
+        assert ref["signatures"][nm][1] == sha(norm_sig(shim[nm][3])), "%s: signature differs from the reference's\n shim: %s" % (nm, shim[nm][3])
     for nm in spec["same_type"]:
-        rf = next(GoFile(os.path.join(ref_dir, fn)) for fn in sorted(os.listdir(ref_dir)) if fn.endswith(".go") and nm in GoFile(os.path.join(ref_dir, fn)).decls)
-        sf = next(GoFile(os.path.join(ROOT, "shim", pkg, fn)) for fn in sorted(os.listdir(os.path.join(ROOT, "shim", pkg))) if nm in GoFile(os.path.join(ROOT, "shim", pkg, fn)).decls)
-
-        def body(f):
-            _, a, _, _ = f.decls[nm]
-            k = f.code.index("{", a)
-            return norm_sig(f.code[k:match_close(f.code, k, "{", "}") + 1])
-        assert body(rf) == body(sf), "type %s differs" % nm
+        sf = next(f for f in shim_files if nm in f.decls)
+        assert ref["types"][nm] == sha(type_body(sf, nm)), "type %s differs" % nm
 
 
 # ---------------------------------------------------------------------------------------------------------------------

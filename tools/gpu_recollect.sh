@@ -10,10 +10,10 @@ python -c 'import bench; print(bench.kernel_source_hash())' > $out/kernel_source
 echo "${GNX_COMMIT:-unknown}" > $out/commit.txt
 timeout 1500 python -m pytest tests -m gpu -x -q > $out/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $out/pytest_gpu.log
 timeout 300 python -c 'import __graft_entry__ as g; g.smoke(); print("smoke ok")' > $out/smoke.log 2>&1
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.err
-timeout 900 python bench.py --series long --no-extras > $out/bench_long.json 2>> $out/bench.err
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err
+timeout 900 python bench.py --full --series long --no-extras > $out/bench_long.json 2>> $out/bench.err
 cd /tmp
-Q="--no-cpu --no-host --no-extras --verify 0"
+Q="--full --no-cpu --no-host --no-extras --verify 0"
 timeout 900 rocprofv3 --kernel-trace --stats -d $out/stats -o stats --output-format csv -- python $repo/bench.py $Q --steps 3 --warmup 1 > $out/stats_bench.json 2> $out/stats.err
 timeout 900 rocprofv3 --kernel-trace --stats -d $out/stats_long -o stats --output-format csv -- python $repo/bench.py $Q --series long --pairs 1024 --steps 2 --warmup 1 > $out/stats_long_bench.json 2>> $out/stats.err
 for c in FETCH_SIZE WRITE_SIZE; do

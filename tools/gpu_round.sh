@@ -10,12 +10,12 @@ python -c 'import bench; print(bench.kernel_source_hash())' > $out/kernel_source
 echo "${GNX_COMMIT:-unknown}" > $out/commit.txt                                            # (the box has no .git: pass GNX_COMMIT=$(git rev-parse --short HEAD))
 timeout 1500 python -m pytest tests -m gpu -x -q $GNX_PYTEST_EXTRA > $out/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $out/pytest_gpu.log
 timeout 300 python -c 'import __graft_entry__ as g; g.smoke(); print("smoke ok")' > $out/smoke.log 2>&1
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.err
-timeout 900 python bench.py --series long --no-extras > $out/bench_long.json 2>> $out/bench.err
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err
+timeout 900 python bench.py --full --series long --no-extras > $out/bench_long.json 2>> $out/bench.err
 # the N > 1 flow of bench.py on this 1-GPU box: two ranks sharing the device over gloo (plumbing check; no scaling claim)
-timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --share-gpu --dist-backend gloo --pairs 20000 --steps 2 --no-cpu > $out/bench_2ranks_shared_gpu.json 2>> $out/bench.err
+timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --share-gpu --dist-backend gloo --pairs 20000 --steps 2 --no-cpu > $out/bench_2ranks_shared_gpu.json 2>> $out/bench.err
 cd /tmp
-Q="--no-cpu --no-host --no-extras --verify 0"
+Q="--full --no-cpu --no-host --no-extras --verify 0"
 timeout 900 rocprofv3 --kernel-trace --stats -d $out/stats -o stats --output-format csv -- python $repo/bench.py $Q --steps 3 --warmup 1 > $out/stats_bench.json 2> $out/stats.err
 timeout 900 rocprofv3 --kernel-trace --stats -d $out/stats_long -o stats --output-format csv -- python $repo/bench.py $Q --series long --pairs 1024 --steps 2 --warmup 1 > $out/stats_long_bench.json 2>> $out/stats.err
 # reads of 800 bases (5 row blocks in one launch: fp_sweep_levels_kernel) and 20 kb x 100 kb (125 row blocks)
