@@ -18,7 +18,8 @@ EXPORTS = ["gnx_device_count", "gnx_init", "gnx_shutdown", "gnx_last_error", "gn
            "gnx_align_batch_windows", "gnx_align_pair", "gnx_align_batch_device", "gnx_get_timing",
            "gnx_affine_gap_chunk_batch", "gnx_multiple_affine_gap_batch", "gnx_gsw_extend_batch",
            "gnx_init_devices", "gnx_n_devices", "gnx_set_reference", "gnx_set_reference_synthetic", "gnx_align_batch_by_offset",
-           "gnx_seed_index_build", "gnx_seed_index_set", "gnx_seed_find_batch", "gnx_seed_index_set_gen", "gnx_seed_find_batch_gen", "gnx_gsw_graph_create", "gnx_gsw_graph_free", "gnx_gsw_map_reads", "gnx_debug_occupy", "gnx_debug_counter", "gnx_reference_info"]
+           "gnx_seed_index_build", "gnx_seed_index_set", "gnx_seed_find_batch", "gnx_seed_index_set_gen", "gnx_seed_find_batch_gen", "gnx_gsw_graph_create", "gnx_gsw_graph_free", "gnx_gsw_map_reads", "gnx_debug_occupy", "gnx_debug_counter", "gnx_reference_info",
+           "gnx_score_batch", "gnx_score_batch_windows", "gnx_score_batch_by_offset", "gnx_score_batch_device"]
 
 
 class GnxCigar(ctypes.Structure):
@@ -98,6 +99,14 @@ def lib():
         L.gnx_set_reference_synthetic.restype = ctypes.c_int
         L.gnx_align_batch_by_offset.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, c_p, c_p, c_p, c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_p)]
         L.gnx_align_batch_by_offset.restype = ctypes.c_int
+        L.gnx_score_batch.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, c_p, c_p, c_p, c_p]
+        L.gnx_score_batch.restype = ctypes.c_int
+        L.gnx_score_batch_windows.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, i64, c_p, c_p, c_p, i64, c_p, c_p, c_p]
+        L.gnx_score_batch_windows.restype = ctypes.c_int
+        L.gnx_score_batch_by_offset.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, c_p, c_p, c_p, c_p]
+        L.gnx_score_batch_by_offset.restype = ctypes.c_int
+        L.gnx_score_batch_device.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]
+        L.gnx_score_batch_device.restype = ctypes.c_int
         L.gnx_seed_index_build.argtypes = [c_p, c_p, i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(i64)]
         L.gnx_seed_index_build.restype = ctypes.c_int
         L.gnx_seed_index_set.argtypes = [c_p, c_p, i64, c_p, c_p, i64, ctypes.c_int]
@@ -303,6 +312,45 @@ def align_batch(params, alphas, betas):
                             scores.ctypes.data, ctypes.byref(ops_p), ctypes.byref(off_p)))
     ops, off = _take(ops_p, off_p, n)
     return scores[:n], ops, off
+
+
+def score_batch_windows(params, a_buf, a_start, a_len, b_buf, b_start, b_len):
+    """gnx_score_batch_windows: the scores of align_batch_windows without the CIGARs.  Returns scores[int64]."""
+    L = lib()
+    a_buf, b_buf = _u8(a_buf), _u8(b_buf)
+    a_start, a_len, b_start, b_len = _i64(a_start), _i64(a_len), _i64(b_start), _i64(b_len)
+    n = int(a_start.shape[0])
+    scores = np.zeros(max(n, 1), dtype=np.int64)
+    check(L.gnx_score_batch_windows(ctypes.byref(params), n, a_buf.ctypes.data, a_buf.shape[0], a_start.ctypes.data, a_len.ctypes.data,
+                                    b_buf.ctypes.data, b_buf.shape[0], b_start.ctypes.data, b_len.ctypes.data, scores.ctypes.data))
+    return scores[:n]
+
+
+def score_batch_by_offset(params, a_cat, a_off, ref_start, ref_len):
+    """gnx_score_batch_by_offset: reads against windows of the resident reference, scores only."""
+    L = lib()
+    a_cat, a_off, ref_start, ref_len = _u8(a_cat), _i64(a_off), _i64(ref_start), _i64(ref_len)
+    n = int(ref_start.shape[0])
+    scores = np.zeros(max(n, 1), dtype=np.int64)
+    check(L.gnx_score_batch_by_offset(ctypes.byref(params), n, a_cat.ctypes.data, a_off.ctypes.data, ref_start.ctypes.data, ref_len.ctypes.data,
+                                      scores.ctypes.data))
+    return scores[:n]
+
+
+def score_batch(params, alphas, betas):
+    """gnx_score_batch on lists of uint8 arrays.  Returns scores[int64]."""
+    L = lib()
+    n = len(alphas)
+    a_off = np.zeros(n + 1, dtype=np.int64)
+    b_off = np.zeros(n + 1, dtype=np.int64)
+    if n:
+        a_off[1:] = np.cumsum([len(a) for a in alphas])
+        b_off[1:] = np.cumsum([len(b) for b in betas])
+    a_cat = _u8(np.concatenate([_u8(a) for a in alphas])) if n and a_off[-1] else np.zeros(1, dtype=np.uint8)
+    b_cat = _u8(np.concatenate([_u8(b) for b in betas])) if n and b_off[-1] else np.zeros(1, dtype=np.uint8)
+    scores = np.zeros(max(n, 1), dtype=np.int64)
+    check(L.gnx_score_batch(ctypes.byref(params), n, a_cat.ctypes.data, a_off.ctypes.data, b_cat.ctypes.data, b_off.ctypes.data, scores.ctypes.data))
+    return scores[:n]
 
 
 def affine_gap_chunk_batch(params, chunk_size, alphas, betas):

@@ -107,6 +107,85 @@ def AlignBatch(params, alphas, betas):
     return [(int(scores[k]), _to_route(ops[off[k]:off[k + 1]])) for k in range(len(alphas))]
 
 
+# ---- score-only calls (gnx_score_*: an extension, no Go function returns a score alone) ------------------------------------------
+def ScoreBatch(params, alphas, betas):
+    """The scores AlignBatch would return for these pairs, without their routes.  Returns [score, ...] in input order."""
+    try:
+        scores = _lib.score_batch(params, alphas, betas)
+    except _lib.GnxError as e:
+        _raise(e)
+    return [int(x) for x in scores]
+
+
+def _one_score(params, alpha, beta):
+    return ScoreBatch(params, [alpha], [beta])[0]
+
+
+def AffineGapScore(alpha, beta, scores, gapOpen, gapExtend):
+    return _one_score(_lib.make_params(_lib.GNX_AFFINE_GAP, scores, gapOpen, gapExtend), alpha, beta)
+
+
+def ConstGapScore(alpha, beta, scores, gapPen):
+    return _one_score(_lib.make_params(_lib.GNX_CONST_GAP, scores, gapPen), alpha, beta)
+
+
+def AffineGapLocalScore(target, query, scores, gapOpen, gapExtend):
+    return _one_score(_lib.make_params(_lib.GNX_AFFINE_GAP_LOCAL, scores, gapOpen, gapExtend), target, query)
+
+
+def ScoreAllPairs(seqs, params):
+    """Scores of all x < y pairs of `seqs` from one device call: {(x, y): score} (what a distance matrix or the choice of the
+    nearest pair of a progressive-alignment round needs)."""
+    idx = [(x, y) for x in range(len(seqs)) for y in range(x + 1, len(seqs))]
+    sc = ScoreBatch(params, [seqs[x] for x, _ in idx], [seqs[y] for _, y in idx]) if idx else []
+    return {xy: s for xy, s in zip(idx, sc)}
+
+
+def _first_maxima(scores, counts):
+    """Per read the index of the FIRST maximum among its counts[r] consecutive scores (ties go to the lowest index)."""
+    best, at = [], 0
+    for k in counts:
+        if k < 1:
+            raise ValueError("a read without candidates")
+        b = 0
+        for c in range(1, k):
+            if scores[at + c] > scores[at + b]:
+                b = c
+        best.append(b)
+        at += k
+    return best
+
+
+def AlignBestOf(params, reads, candidates):
+    """Best of K: candidates[r] is a list of K_r target sequences, or of (start, len) windows of the resident reference
+    (_lib.set_reference).  One score call over all read x candidate pairs, per read the first maximum in candidate order, then one
+    ordinary align call for the winners only.  Returns [(best_index, score, route), ...]: score and route are what AlignBatch gives
+    for the winning pair."""
+    if not reads:
+        return []
+    counts = [len(c) for c in candidates]
+    flat = [c for cs in candidates for c in cs]
+    windows = bool(flat) and isinstance(flat[0], tuple)
+    rep = [reads[r] for r, k in enumerate(counts) for _ in range(k)]
+    try:
+        if windows:
+            a_cat, a_off = _lib._cat(rep)
+            sc = _lib.score_batch_by_offset(params, a_cat, a_off, [w[0] for w in flat], [w[1] for w in flat])
+        else:
+            sc = _lib.score_batch(params, rep, flat)
+        best = _first_maxima(sc, counts)
+        first = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+        win = [flat[int(first[r]) + b] for r, b in enumerate(best)]
+        if windows:
+            a_cat, a_off = _lib._cat(list(reads))
+            scores, ops, off = _lib.align_batch_by_offset(params, a_cat, a_off, [w[0] for w in win], [w[1] for w in win])
+        else:
+            scores, ops, off = _lib.align_batch(params, list(reads), win)
+    except _lib.GnxError as e:
+        _raise(e)
+    return [(best[r], int(scores[r]), _to_route(ops[off[r]:off[r + 1]])) for r in range(len(reads))]
+
+
 def AffineGapChunk(alpha, beta, scores, gapOpen, gapExtend, chunkSize):
     """align.AffineGapChunk (/root/reference/align/affineGap_highMem.go:227-268)."""
     try:

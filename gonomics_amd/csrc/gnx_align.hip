@@ -50,6 +50,7 @@
 #include "lat_fill.hip.h"
 #include "lat_wide.hip.h"
 #include "seed_kernels.hip.h"
+#include "score_sweep.hip.h"
 
 namespace {
 
@@ -132,6 +133,7 @@ struct Ctx {
     // pipelined host entry (gnx_host.hip.h): double-buffered inputs, results accumulated on the device, the resident reference
     DevBuf pin_a[2], pin_as[2], pin_b[2], pin_bs[2], res_score, res_off, res_ops, ref, gat_score, gat_off, gat_ops;
     // resident seed index of the graph aligner (gnx_seed_index_set)
+    DevBuf ss_plans, ss_rowbuf, ss_prog, ss_err, ss_off; // the score-only sweep (score_sweep.hip.h): plans, hand-over rows, progress / claim words, error flags; offsets of a dropped CIGAR
     DevBuf sd_keys, sd_locs, sd_nodes, sd_node_off, sd_word_off, sd_words, sd_tmp[8];
     int64_t sd_n = -1, sd_nodes_n = 0; int sd_seed_len = 0;
     PinBuf h_plans; // host-side plans of the general path
@@ -2383,6 +2385,132 @@ int run_host_windows(const gnx_params *prm, int64_t n_pairs,
     return GNX_OK;
 }
 
+// ---- score-only calls (gnx_score_*): the score sweep (score_sweep.hip.h) ---------------------------------------------------------
+// Global affine / constant gap with gapOpen <= 0, both sequences non-empty, the shorter one <= SS_MAX_LEVELS * 160 bases, the profile
+// entries s - 2e and gapOpen inside int16 with room to spare, and the rebased keys inside int32: (n + m + 2) * 2 * max|penalty| < 2^30.
+// One pass over the batch: pairs sorted by (row blocks, columns) so that the four pairs of a wave are alike, one launch per number
+// of row blocks.  Returns GNX_OK, an error, or -1 when the batch is not the sweep's (the caller then takes the ordinary route and
+// leaves the CIGAR on the device).  Writes d_score[pair] only.
+int run_score_sweep(const gnx_params *prm, int64_t n_pairs, const uint8_t *d_a, const int64_t *d_as, const uint8_t *d_b, const int64_t *d_bs,
+                    const int64_t *h_alen, const int64_t *h_blen, int64_t *d_score, hipStream_t stream) {
+    Ctx &c = g_ctx;
+    KParams kp; TbParams tp; bool affine, local, lowmem;
+    int rc = check_params(prm, kp, tp, affine, local, lowmem);
+    if (rc) return rc;
+    if (local || prm->gap_open > 0 || prm->gap_open < -16000 || n_pairs <= 0 || n_pairs > 0x7ffffff0) return -1;
+    if (const char *e = getenv("GNX_SCORE_SWEEP")) if (e[0] == '0') return -1; // (A/B: every score call through the ordinary routes)
+    if (lowmem && prm->checkersize_i != prm->checkersize_j) return -1;          // (run_device refuses some of these: let it say so)
+    ScoreParams sp;
+    const int64_t reb = affine ? prm->gap_extend : prm->gap_open;
+    for (int x = 0; x < 25; x++) {
+        const int64_t v = prm->scores[x] - 2 * reb;
+        if (v < -16000 || v > 16000) return -1;
+        sp.sc[x] = (int)v;
+    }
+    sp.o = affine ? (int)prm->gap_open : 0;
+    sp.e = (int)reb;
+    const int64_t maxpen = std::max<int64_t>(max_abs_pen(prm, affine), 1);
+    constexpr int HB = G * SS_RR;
+    std::vector<ScorePlan> plans((size_t)n_pairs);
+    int64_t cells = 0;
+    bool sorted = true;
+    for (int64_t p = 0; p < n_pairs; p++) {
+        const int64_t n = h_alen[p], m = h_blen[p];
+        if (n < 1 || m < 1 || n > 0x3fffffff || m > 0x3fffffff) return -1;
+        const int64_t ns = std::min(n, m), ml = std::max(n, m);
+        if (ns > (int64_t)SS_MAX_LEVELS * HB || (n + m + 2) * 2 * maxpen >= ((int64_t)1 << 30)) return -1;
+        ScorePlan &pl = plans[(size_t)p];
+        pl.n = (int32_t)ns; pl.m = (int32_t)ml; pl.src = (int32_t)p; pl.swap = n > m ? 1 : 0; pl.rowbuf_off = 0; pl.levels = (int32_t)((ns + HB - 1) / HB); pl._pad = 0;
+        cells += n * m;
+        if (p > 0) { const ScorePlan &q = plans[(size_t)p - 1]; if (q.levels > pl.levels || (q.levels == pl.levels && q.m > pl.m)) sorted = false; }
+    }
+    if (!sorted) std::sort(plans.begin(), plans.end(), [](const ScorePlan &x, const ScorePlan &y) { return x.levels != y.levels ? x.levels < y.levels : (x.m != y.m ? x.m < y.m : x.src < y.src); });
+    // quads: four consecutive pairs, all with the row blocks of the tallest (the last) of them; the last quad is filled with empty slots
+    const int64_t n_quads = (n_pairs + 3) / 4;
+    plans.resize((size_t)n_quads * 4, ScorePlan{0, 0, 0, 0, 0, 1, 0});
+    struct Group { int64_t q0, nq; int S; };
+    std::vector<Group> groups;
+    int64_t rb_total = 0, prog_max = 0;
+    for (int64_t q = 0; q < n_quads; q++) {
+        int S = 1;
+        for (int k = 0; k < 4; k++) S = std::max(S, (int)plans[(size_t)(q * 4 + k)].levels);
+        for (int k = 0; k < 4; k++) {
+            ScorePlan &pl = plans[(size_t)(q * 4 + k)];
+            pl.levels = S;
+            if (S > 1 && pl.n > 0) { pl.rowbuf_off = rb_total; rb_total += 2 * ((int64_t)pl.m + 1); }
+        }
+        if (groups.empty() || groups.back().S != S) groups.push_back(Group{q, 0, S});
+        groups.back().nq++;
+    }
+    for (const Group &gq : groups) if (gq.S > 1) prog_max = std::max<int64_t>(prog_max, (int64_t)gq.S * gq.nq * 2 + 2);
+    if ((rc = c.ss_plans.ensure(plans.size() * sizeof(ScorePlan)))) return rc;
+    if ((rc = c.ss_err.ensure(64))) return rc;
+    if (rb_total && (rc = c.ss_rowbuf.ensure((size_t)rb_total * sizeof(int2)))) return rc;
+    if (prog_max && (rc = c.ss_prog.ensure((size_t)prog_max * 4))) return rc;
+    if (c.beta_packed) {
+        kp.b2 = reinterpret_cast<const unsigned *>(c.ref.p); kp.bflag = reinterpret_cast<const unsigned long long *>(c.ref_flag.p);
+        kp.brank = reinterpret_cast<const unsigned *>(c.ref_rank.p); kp.bexc = reinterpret_cast<const unsigned long long *>(c.ref_exc.p);
+    }
+    const ScorePlan *dpl = reinterpret_cast<const ScorePlan *>(c.ss_plans.p);
+    int *d_err = reinterpret_cast<int *>(c.ss_err.p);
+    int2 *rb = reinterpret_cast<int2 *>(c.ss_rowbuf.p);
+    int *prog = reinterpret_cast<int *>(c.ss_prog.p);
+    HIPCHK(hipMemcpyAsync(c.ss_plans.p, plans.data(), plans.size() * sizeof(ScorePlan), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemsetAsync(d_err, 0, 64, stream));
+    int64_t launches = 0;
+    auto sweep = [&](bool piped) -> int {
+        for (const Group &gq : groups) {
+            const ScorePlan *gp = dpl + gq.q0 * 4;
+            const int W = (int)gq.nq, S = gq.S;
+            if (S == 1) {
+                auto k = affine ? score_sweep_kernel<true> : score_sweep_kernel<false>;
+                hipLaunchKernelGGL(k, dim3((unsigned)W), dim3(64), 0, stream, gp, d_a, d_as, d_b, d_bs, kp, sp, d_score, d_err);
+                launches++;
+            } else {
+                auto k = affine ? score_sweep_levels_kernel<true> : score_sweep_levels_kernel<false>;
+                ScoreLevelsArgs la{gp, d_a, d_as, d_b, d_bs, kp, sp, d_score, d_err, rb, S, W, 0, 1, prog};
+                if (piped) {
+                    HIPCHK(hipMemsetAsync(prog, 0, ((size_t)S * W * 2 + 2) * 4, stream)); // progress words, claim words, test switch
+                    if ((rc = claim_test_switch(prog + (size_t)S * W * 2, stream))) return rc;
+                    hipLaunchKernelGGL(k, dim3((unsigned)((int64_t)S * W)), dim3(64), 0, stream, la);
+                    launches++;
+                } else {
+                    la.piped = 0;
+                    for (int level = 0; level < S; level++) {
+                        la.level0 = level;
+                        hipLaunchKernelGGL(k, dim3((unsigned)W), dim3(64), 0, stream, la);
+                        launches++;
+                    }
+                }
+            }
+            HIPCHK(hipGetLastError());
+        }
+        return GNX_OK;
+    };
+    HIPCHK(hipEventRecord(c.ev[0], stream));
+    if ((rc = sweep(!no_pipe()))) return rc;
+    HIPCHK(hipEventRecord(c.ev[1], stream));
+    int ef = 0;
+    HIPCHK(hipMemcpyAsync(&ef, d_err, 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (ef & 16) { // a level that waited 5 s for the one above it (a bug trap, as on the fast path): sweep again, level by level
+        if (getenv("GNX_DEBUG")) fprintf(stderr, "[gnx score] a row block timed out waiting for the one above it -> one launch per level\n");
+        HIPCHK(hipMemsetAsync(d_err, 0, 64, stream));
+        if ((rc = sweep(false))) return rc;
+        HIPCHK(hipEventRecord(c.ev[1], stream));
+        HIPCHK(hipMemcpyAsync(&ef, d_err, 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+    if (getenv("GNX_DEBUG")) fprintf(stderr, "[gnx score] score sweep: %lld pairs, %d group(s), %lld launch(es), %.3f ms\n", (long long)n_pairs, (int)groups.size(), (long long)launches, ms);
+    c.timing = gnx_timing{};
+    c.timing.fill_ms = ms; c.timing.total_ms = ms; c.timing.cells = cells; c.timing.n_launches = 1; c.timing.trace_bytes = 0;
+    c.timing.dominant_ms = ms; c.timing.dominant_launches = launches; c.timing.fast_path = 7;
+    if (ef & 1) { set_err("a base >= 5 was found: the reference would panic (index out of range)%s", ""); return GNX_EBASE; }
+    return GNX_OK;
+}
+
 } // namespace
 
 #include "gnx_host.hip.h"
@@ -2474,7 +2602,7 @@ void gnx_shutdown(void) {
                           &c.fp_wplans[0], &c.fp_wplans[1], &c.fp_active[0], &c.fp_active[1], &c.trace, &c.hcol, &c.rowbuf, &c.dcol, &c.plans, &c.nops, &c.misc, &c.in_a, &c.in_b,
                           &c.in_as, &c.in_al, &c.in_bs, &c.in_bl, &c.out_score, &c.out_off, &c.out_ops, &c.out_end, &c.sc_pairs, &c.sc_mat, &c.sc_err,
                           &c.pin_a[0], &c.pin_a[1], &c.pin_as[0], &c.pin_as[1], &c.pin_b[0], &c.pin_b[1], &c.pin_bs[0], &c.pin_bs[1], &c.res_score, &c.res_off, &c.res_ops,
-                          &c.ref, &c.ref_flag, &c.ref_rank, &c.ref_exc, &c.unpk_b, &c.unpk_off, &c.cl_bases, &c.sc_prof_a, &c.sc_prof_b, &c.mega_rows, &c.mega_state, &c.farm, &c.mega_arena, &c.gat_score, &c.gat_off, &c.gat_ops, &c.sd_keys, &c.sd_locs, &c.sd_nodes, &c.sd_node_off, &c.sd_word_off, &c.sd_words,
+                          &c.ref, &c.ref_flag, &c.ref_rank, &c.ref_exc, &c.unpk_b, &c.unpk_off, &c.cl_bases, &c.sc_prof_a, &c.sc_prof_b, &c.mega_rows, &c.mega_state, &c.farm, &c.mega_arena, &c.gat_score, &c.gat_off, &c.gat_ops, &c.ss_plans, &c.ss_rowbuf, &c.ss_prog, &c.ss_err, &c.ss_off, &c.sd_keys, &c.sd_locs, &c.sd_nodes, &c.sd_node_off, &c.sd_word_off, &c.sd_words,
                           &c.sd_tmp[0], &c.sd_tmp[1], &c.sd_tmp[2], &c.sd_tmp[3], &c.sd_tmp[4], &c.sd_tmp[5], &c.sd_tmp[6], &c.sd_tmp[7]};
         for (DevBuf *b : bufs) b->release();
         PinBuf *pins[] = {&c.h_plans, &c.st_a[0], &c.st_a[1], &c.st_as[0], &c.st_as[1], &c.st_b[0], &c.st_b[1], &c.st_bs[0], &c.st_bs[1]};
@@ -2560,6 +2688,51 @@ int gnx_align_batch(const gnx_params *p, int64_t n_pairs, const uint8_t *alpha_c
     for (int64_t q = 0; q < n_pairs; q++) { al[(size_t)q] = alpha_off[q + 1] - alpha_off[q]; bl[(size_t)q] = beta_off[q + 1] - beta_off[q]; }
     return gnx_align_batch_windows(p, n_pairs, alpha_cat, alpha_off[n_pairs], alpha_off, al.data(), beta_cat, beta_off[n_pairs], beta_off, bl.data(),
                                    out_score, out_ops, out_ops_off);
+}
+
+/* ---- score-only entries: the align entries minus the CIGAR (gnx_align.h) ---- */
+int gnx_score_batch_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *alpha_cat, const int64_t *alpha_off,
+                              const int64_t *ref_start, const int64_t *ref_len, int64_t *out_score) {
+    std::lock_guard<std::mutex> api(g_api_mu);
+    g_err[0] = 0;
+    if (n_pairs < 0 || !alpha_off || (n_pairs > 0 && (!ref_start || !ref_len))) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    std::vector<int64_t> al((size_t)n_pairs);
+    for (int64_t q = 0; q < n_pairs; q++) al[(size_t)q] = alpha_off[q + 1] - alpha_off[q];
+    return run_host_sharded(p, n_pairs, alpha_cat, alpha_off[n_pairs], alpha_off, al.data(), nullptr, 0, ref_start, ref_len, out_score, nullptr, nullptr, true);
+}
+
+int gnx_score_batch_windows(const gnx_params *p, int64_t n_pairs,
+                            const uint8_t *alpha_buf, int64_t alpha_buf_len, const int64_t *alpha_start, const int64_t *alpha_len,
+                            const uint8_t *beta_buf, int64_t beta_buf_len, const int64_t *beta_start, const int64_t *beta_len, int64_t *out_score) {
+    std::lock_guard<std::mutex> api(g_api_mu);
+    g_err[0] = 0;
+    static const uint8_t none = 0;
+    return run_host_sharded(p, n_pairs, alpha_buf ? alpha_buf : &none, alpha_buf_len, alpha_start, alpha_len, beta_buf ? beta_buf : &none, beta_buf_len, beta_start, beta_len,
+                            out_score, nullptr, nullptr, true);
+}
+
+int gnx_score_batch(const gnx_params *p, int64_t n_pairs, const uint8_t *alpha_cat, const int64_t *alpha_off,
+                    const uint8_t *beta_cat, const int64_t *beta_off, int64_t *out_score) {
+    if (n_pairs < 0 || !alpha_off || !beta_off) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    std::vector<int64_t> al((size_t)n_pairs), bl((size_t)n_pairs);
+    for (int64_t q = 0; q < n_pairs; q++) { al[(size_t)q] = alpha_off[q + 1] - alpha_off[q]; bl[(size_t)q] = beta_off[q + 1] - beta_off[q]; }
+    return gnx_score_batch_windows(p, n_pairs, alpha_cat, alpha_off[n_pairs], alpha_off, al.data(), beta_cat, beta_off[n_pairs], beta_off, bl.data(), out_score);
+}
+
+int gnx_score_batch_device(const gnx_params *p, int64_t n_pairs,
+                           const uint8_t *d_alpha_buf, const int64_t *d_alpha_start, const int64_t *d_alpha_len,
+                           const uint8_t *d_beta_buf, const int64_t *d_beta_start, const int64_t *d_beta_len,
+                           const int64_t *h_alpha_len, const int64_t *h_beta_len, int64_t *d_score, void *stream) {
+    (void)d_alpha_len; (void)d_beta_len; // lengths are taken from the host copies (planning needs them anyway)
+    std::lock_guard<std::mutex> api(g_api_mu);
+    CtxScope sc(ctx_at(0));
+    g_err[0] = 0;
+    int rc = ensure_init();
+    if (rc) return rc;
+    if (!p || n_pairs < 0 || !d_score || (n_pairs > 0 && (!h_alpha_len || !h_beta_len || !d_alpha_start || !d_beta_start))) {
+        set_err("bad argument%s", ""); return GNX_EINVAL;
+    }
+    return score_or_fallback(g_ctx, p, n_pairs, d_alpha_buf, d_alpha_start, d_beta_buf, d_beta_start, h_alpha_len, h_beta_len, d_score, (hipStream_t)stream);
 }
 
 int gnx_gsw_extend_batch(int side, const int64_t *scores, int64_t gap_pen, int64_t n_pairs,

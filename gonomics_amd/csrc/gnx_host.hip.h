@@ -282,6 +282,7 @@ struct HostJob {
     const uint8_t *b_buf = nullptr; const int64_t *b_start = nullptr, *b_len = nullptr; // host windows, or windows into b_dev
     const uint8_t *b_dev = nullptr; // != nullptr: the whole beta buffer / the resident reference is on this context's device
     bool packed = false;            // b_dev is the PACKED resident reference (beta windows = base positions in it)
+    bool score_only = false;        // gnx_score_*: scores only (the score sweep, or the ordinary route with its CIGAR left on the device)
     int64_t total_ops = 0;
     int rc = GNX_OK;
     char err[512] = "";
@@ -300,6 +301,23 @@ int grow_ops(Ctx &c, int64_t keep_elems, int64_t want_elems, hipStream_t st) {
     c.res_ops.release();
     c.res_ops = nb;
     return GNX_OK;
+}
+
+// A batch of a score-only call on the current context: the score sweep where it applies (run_score_sweep), else the ordinary
+// route, whose CIGAR goes into the context's result buffer and simply stays there.  Sets c.timing like run_device.
+int score_or_fallback(Ctx &c, const gnx_params *prm, int64_t cnt, const uint8_t *d_a, const int64_t *d_as, const uint8_t *d_b, const int64_t *d_bs,
+                      const int64_t *h_alen, const int64_t *h_blen, int64_t *d_score, hipStream_t stream) {
+    int rc = run_score_sweep(prm, cnt, d_a, d_as, d_b, d_bs, h_alen, h_blen, d_score, stream);
+    if (rc != -1) return rc;
+    if ((rc = c.ss_off.ensure((size_t)(std::max<int64_t>(cnt, 0) + 1) * 8))) return rc;
+    if ((rc = grow_ops(c, 0, std::max<int64_t>((int64_t)1 << 20, 64 * cnt), stream))) return rc;
+    int64_t tot = 0;
+    for (int attempt = 0;; attempt++) {
+        rc = run_device(prm, cnt, d_a, d_as, d_b, d_bs, h_alen, h_blen, d_score, (gnx_cigar *)c.res_ops.p, (int64_t)(c.res_ops.cap / sizeof(gnx_cigar)), (int64_t *)c.ss_off.p, &tot, stream);
+        if (rc != GNX_ECAPACITY || attempt >= 8) break;
+        if ((rc = grow_ops(c, 0, tot + 1024, stream))) break;
+    }
+    return rc;
 }
 
 // runs on the thread that owns the context (t_ctx == job.c, device current)
@@ -368,7 +386,7 @@ int run_host_job(HostJob &j) {
     // CIGAR capacity: a guess that fits every workload of the path's callers, grown (with a retry of the sub-batch) when it does not
     int64_t worst = 0;
     for (int64_t q = 0; q < n; q++) worst += al[q] + bl[q] + 1;
-    if ((rc = grow_ops(c, 0, std::max<int64_t>(std::min<int64_t>(worst, std::max<int64_t>((int64_t)1 << 20, 64 * std::min(n, size))), 1), c.own_stream))) return rc;
+    if (!j.score_only && (rc = grow_ops(c, 0, std::max<int64_t>(std::min<int64_t>(worst, std::max<int64_t>((int64_t)1 << 20, 64 * std::min(n, size))), 1), c.own_stream))) return rc;
     gnx_timing tsum = {};
     for (int64_t k = 0; k < K; k++) {
         const int slot = (int)(k & 1);
@@ -405,7 +423,12 @@ int run_host_job(HostJob &j) {
                 }
             }
         }
-        for (int attempt = 0; rc == GNX_OK; attempt++) {
+        if (j.score_only && rc == GNX_OK) {
+            c.beta_packed = packed;
+            rc = score_or_fallback(c, j.prm, cnt, (const uint8_t *)c.pin_a[slot].p, (const int64_t *)c.pin_as[slot].p, db, dbs, al + b, bl + b, (int64_t *)c.res_score.p + done, c.own_stream);
+            c.beta_packed = false;
+        }
+        for (int attempt = 0; rc == GNX_OK && !j.score_only; attempt++) {
             const int64_t cap = (int64_t)(c.res_ops.cap / sizeof(gnx_cigar)) - total;
             c.beta_packed = packed;
             rc = run_device(j.prm, cnt, (const uint8_t *)c.pin_a[slot].p, (const int64_t *)c.pin_as[slot].p,
@@ -420,8 +443,8 @@ int run_host_job(HostJob &j) {
         if (rc == GNX_OK) {
             tsum.fill_ms += c.timing.fill_ms; tsum.traceback_ms += c.timing.traceback_ms; tsum.total_ms += c.timing.total_ms; tsum.cells += c.timing.cells;
             tsum.n_launches += c.timing.n_launches; tsum.trace_bytes += c.timing.trace_bytes; tsum.dominant_ms += c.timing.dominant_ms;
-            tsum.dominant_launches += c.timing.dominant_launches; tsum.fast_path = c.timing.fast_path;
-            if (total > 0) { // offsets of a sub-batch start at 0
+            tsum.dominant_launches += c.timing.dominant_launches; tsum.fast_path = j.score_only ? std::max(tsum.fast_path, c.timing.fast_path) : c.timing.fast_path;
+            if (total > 0 && !j.score_only) { // offsets of a sub-batch start at 0
                 hipLaunchKernelGGL(add_offset_kernel, dim3((unsigned)((cnt + 1 + 255) / 256)), dim3(256), 0, c.own_stream, (int64_t *)c.res_off.p + done, cnt + 1, total);
                 if (hipGetLastError() != hipSuccess) { set_err("add_offset_kernel failed to launch%s", ""); rc = GNX_EDEVICE; }
             }
@@ -543,9 +566,9 @@ int ensure_reference(int nc) {
 int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
                      const uint8_t *a_buf, int64_t a_len_total, const int64_t *a_start, const int64_t *a_lens,
                      const uint8_t *b_buf, int64_t b_len_total, const int64_t *b_start, const int64_t *b_lens,
-                     int64_t *out_score, gnx_cigar **out_ops, int64_t **out_ops_off) {
+                     int64_t *out_score, gnx_cigar **out_ops, int64_t **out_ops_off, bool score_only = false) {
     const auto t_entry = std::chrono::steady_clock::now();
-    if (!prm || n_pairs < 0 || !out_score || !out_ops || !out_ops_off || a_len_total < 0 || b_len_total < 0) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (!prm || n_pairs < 0 || !out_score || (!score_only && (!out_ops || !out_ops_off)) || a_len_total < 0 || b_len_total < 0) { set_err("bad argument%s", ""); return GNX_EINVAL; }
     if (n_pairs > 0 && (!a_start || !a_lens || !b_start || !b_lens)) { set_err("null window table%s", ""); return GNX_EINVAL; }
     const bool resident = (b_buf == nullptr);
     Ctx &c0 = ctx_at(0);
@@ -593,6 +616,7 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
         j.a_buf = a_buf; j.a_start = a_start; j.a_len = a_lens; j.b_buf = b_buf; j.b_start = b_start; j.b_len = b_lens;
         j.b_dev = (const uint8_t *)bdev[(size_t)d];
         j.packed = resident;
+        j.score_only = score_only;
     }
     auto work = [](HostJob *j) {
         CtxScope sc(*j->c);
@@ -700,7 +724,8 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
         hipStream_t st = c0.own_stream;
         if (n_pairs) HIPCHK(hipMemcpyAsync(out_score, d_score, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
         if (total) HIPCHK(hipMemcpyAsync(ops, d_ops, (size_t)total * sizeof(gnx_cigar), hipMemcpyDeviceToHost, st));
-        if (nc == 1) HIPCHK(hipMemcpyAsync(off, d_off, (size_t)(n_pairs + 1) * 8, hipMemcpyDeviceToHost, st));
+        if (score_only) { /* only the score vector comes back */ }
+        else if (nc == 1) HIPCHK(hipMemcpyAsync(off, d_off, (size_t)(n_pairs + 1) * 8, hipMemcpyDeviceToHost, st));
         else {
             // each context's offsets (n_d + 1 of them, starting at 0) sit at [p0 + d ..]: rebase on the host while copying
             std::vector<int64_t> tmp((size_t)(n_pairs + nc));
@@ -723,6 +748,7 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
     for (int d = 1; d < nc; d++) {
         const gnx_timing &u = jobs[(size_t)d].timing;
         t.fill_ms = std::max(t.fill_ms, u.fill_ms); t.traceback_ms = std::max(t.traceback_ms, u.traceback_ms); t.total_ms = std::max(t.total_ms, u.total_ms);
+        if (score_only) t.fast_path = std::max(t.fast_path, u.fast_path);
         t.dominant_ms = std::max(t.dominant_ms, u.dominant_ms); t.cells += u.cells; t.trace_bytes += u.trace_bytes; t.n_launches += u.n_launches; t.dominant_launches += u.dominant_launches;
     }
     t.fetch_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_fetch).count();
@@ -731,6 +757,7 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
     c0.timing = t;
     if (getenv("GNX_DEBUG")) fprintf(stderr, "[gnx host] %lld pairs on %d context(s): call %.3f ms = first upload %.3f + kernels %.3f (device, slowest context) + gather / D2H %.3f (gather %.3f, transport %d) + broadcast %.3f + rest\n",
                                      (long long)n_pairs, nc, t.host_ms, t.stage0_ms, t.total_ms, t.fetch_ms, t.gather_ms, t.transport, t.bcast_ms);
+    if (score_only) { g_pool.put(ops); g_pool.put(off); return GNX_OK; }
     *out_ops = ops; *out_ops_off = off;
     return GNX_OK;
 }

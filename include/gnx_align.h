@@ -95,7 +95,10 @@ typedef struct gnx_timing {
                             path: the fill kernel) -- what roofline.achieved is computed from */
     int64_t dominant_launches;
     int32_t fast_path;   /* 1: the affine fast path ran (short alpha x long beta; AffineGapLocal: short query x long target);
-                            2: the constant-gap path without a stored direction matrix (const_long.hip.h); 0: full direction matrix */
+                            2: the constant-gap path without a stored direction matrix (const_long.hip.h); 0: full direction matrix;
+                            3 / 4: the latency geometry (few pairs) in its int32 / int64 form; 5: the 64-lane affine snapshot path;
+                            6: the constant-gap snapshot path in its 64-lane form; 7: the score-only sweep ran (gnx_score_* entries,
+                            score_sweep.hip.h).  Multi-context score calls report the maximum over contexts. */
     int32_t _pad;
     /* host-buffer entry points only (wall clock inside the library): */
     double host_ms;      /* entry to return of the whole call */
@@ -188,6 +191,35 @@ int gnx_align_batch_device(const gnx_params *p, int64_t n_pairs,
                            const int64_t *h_alpha_len, const int64_t *h_beta_len,
                            int64_t *d_score, gnx_cigar *d_ops, int64_t ops_capacity, int64_t *d_ops_off,
                            int64_t *out_total_ops, void *stream);
+
+/* ---- score-only entries (an extension: no Go signature of the reference returns a score alone) --------------------------------- */
+/* Mirrors of gnx_align_batch / _windows / _by_offset / _device minus the CIGAR outputs: same argument conventions, same validation and
+ * the same return codes for the same inputs (GNX_EBASE, GNX_EEMPTY in the low-memory modes, GNX_EINVAL, GNX_EDEVICE without a device:
+ * no CPU fallback).  Contract: out_score[p] equals, for every gnx_mode, the score gnx_align_batch returns for that pair with the same
+ * gnx_params (checkersize_* have no influence on it: the reference computes the score as a step of its own, highestScore_affineGap,
+ * align/affineGap.go:151-207, highestScore, align/constGap.go:129-176).  All five modes are accepted; a score call never
+ * returns GNX_ERANGE.  What a caller saves: checkpoints, direction matrices, snapshots, the walk and 16 bytes per CIGAR run of D2H --
+ * a score needs O(n + m) state per pair and 8 bytes back.
+ * Routes (gnx_timing.fast_path tells which ran): the score-only sweep (7) serves global affine and global constant gap
+ * (GNX_AFFINE_GAP, GNX_CONST_GAP and their _HIGHMEM twins) with gapOpen <= 0 when every pair of the (sub-)batch has both sequences
+ * non-empty, the shorter one at most 10 240 bases, and the static bound (n + m + 2) * 2 * max|penalty| below 2^30, with matrix
+ * entries s - 2 * gapExtend (constant gap: s - 2 * gapPen) and gapOpen inside +-16 000; beta from plain bytes or the packed resident
+ * reference.  Everything else -- GNX_AFFINE_GAP_LOCAL, gapOpen > 0, empty sequences in the high-memory modes, pairs beyond those
+ * bounds -- runs the route gnx_align_batch would take, and its CIGAR is dropped on the device before anything is copied back.
+ * Multi-context calls (gnx_init_devices) shard and gather like the align entries; only the score vector comes back. */
+int gnx_score_batch(const gnx_params *p, int64_t n_pairs, const uint8_t *alpha_cat, const int64_t *alpha_off,
+                    const uint8_t *beta_cat, const int64_t *beta_off, int64_t *out_score);
+int gnx_score_batch_windows(const gnx_params *p, int64_t n_pairs,
+                            const uint8_t *alpha_buf, int64_t alpha_buf_len, const int64_t *alpha_start, const int64_t *alpha_len,
+                            const uint8_t *beta_buf, int64_t beta_buf_len, const int64_t *beta_start, const int64_t *beta_len, int64_t *out_score);
+/* beta = windows of the resident reference (gnx_set_reference; read packed, 2 bits per base) */
+int gnx_score_batch_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *alpha_cat, const int64_t *alpha_off,
+                              const int64_t *ref_start, const int64_t *ref_len, int64_t *out_score);
+/* device-resident twin of gnx_align_batch_device: d_score[n_pairs] is device memory, the call returns after the kernels finished */
+int gnx_score_batch_device(const gnx_params *p, int64_t n_pairs,
+                           const uint8_t *d_alpha_buf, const int64_t *d_alpha_start, const int64_t *d_alpha_len,
+                           const uint8_t *d_beta_buf, const int64_t *d_beta_start, const int64_t *d_beta_len,
+                           const int64_t *h_alpha_len, const int64_t *h_beta_len, int64_t *d_score, void *stream);
 
 int gnx_get_timing(gnx_timing *out);
 /* Diagnostics (tests only; nothing in the reference corresponds to it): launch n_workgroups workgroups that each hold one CU's whole

@@ -16,6 +16,7 @@
 #ifndef GONOMICS_ALIGN_HPP
 #define GONOMICS_ALIGN_HPP
 
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <stdexcept>
@@ -135,6 +136,35 @@ inline void AlignBatch(int mode, const ScoreMatrix &scores, int64_t gapOpen, int
     out_routes.assign((size_t)n, {});
     for (int64_t k = 0; k < n; k++) for (int64_t x = off[k]; x < off[k + 1]; x++) out_routes[(size_t)k].push_back(Cigar{ops[x].run_length, ops[x].op});
     gnx_free(ops); gnx_free(off);
+}
+
+// ---- score-only calls (gnx_score_*; an extension: no Go function of the reference returns a score alone) ----
+// The scores AlignBatch would return for these pairs, without their routes.
+inline std::vector<int64_t> ScoreBatch(int mode, const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend,
+                                       const std::vector<std::vector<dna::Base>> &alphas, const std::vector<std::vector<dna::Base>> &betas) {
+    const int64_t n = (int64_t)alphas.size();
+    std::vector<int64_t> aoff((size_t)n + 1, 0), boff((size_t)n + 1, 0);
+    for (int64_t k = 0; k < n; k++) { aoff[(size_t)k + 1] = aoff[(size_t)k] + (int64_t)alphas[(size_t)k].size(); boff[(size_t)k + 1] = boff[(size_t)k] + (int64_t)betas[(size_t)k].size(); }
+    std::vector<dna::Base> acat((size_t)aoff[(size_t)n] + 1), bcat((size_t)boff[(size_t)n] + 1);
+    for (int64_t k = 0; k < n; k++) {
+        std::copy(alphas[(size_t)k].begin(), alphas[(size_t)k].end(), acat.begin() + aoff[(size_t)k]);
+        std::copy(betas[(size_t)k].begin(), betas[(size_t)k].end(), bcat.begin() + boff[(size_t)k]);
+    }
+    const gnx_params p = detail::params(mode, scores, gapOpen, gapExtend, 10000, 10000);
+    std::vector<int64_t> out((size_t)std::max<int64_t>(n, 1), 0);
+    const int rc = gnx_score_batch(&p, n, acat.data(), aoff.data(), bcat.data(), boff.data(), out.data());
+    if (rc) detail::raise(rc);
+    out.resize((size_t)n);
+    return out;
+}
+inline int64_t AffineGapScore(const std::vector<dna::Base> &alpha, const std::vector<dna::Base> &beta, const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend) {
+    return ScoreBatch(GNX_AFFINE_GAP, scores, gapOpen, gapExtend, {alpha}, {beta})[0];
+}
+inline int64_t ConstGapScore(const std::vector<dna::Base> &alpha, const std::vector<dna::Base> &beta, const ScoreMatrix &scores, int64_t gapPen) {
+    return ScoreBatch(GNX_CONST_GAP, scores, gapPen, 0, {alpha}, {beta})[0];
+}
+inline int64_t AffineGapLocalScore(const std::vector<dna::Base> &target, const std::vector<dna::Base> &query, const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend) {
+    return ScoreBatch(GNX_AFFINE_GAP_LOCAL, scores, gapOpen, gapExtend, {target}, {query})[0];
 }
 
 inline void AffineGapLocalEngine(const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, std::vector<TargetQueryPair> &pairs) {
