@@ -133,6 +133,24 @@ def AffineGapLocalScore(target, query, scores, gapOpen, gapExtend):
     return _one_score(_lib.make_params(_lib.GNX_AFFINE_GAP_LOCAL, scores, gapOpen, gapExtend), target, query)
 
 
+# ---- locate calls (gnx_locate_*): where in the target a query ends, without a route ------------------------------------------------
+def LocateBatch(params, targets, queries):
+    """AffineGapLocal's score and target end for every (target, query) pair: ([score, ...], [targetEnd, ...]) in input order.
+    targetEnd = len(target) minus the trailing ColD run of the route AffineGapLocal returns: the target position just after the
+    last aligned column.  params.mode must be GNX_AFFINE_GAP_LOCAL."""
+    try:
+        scores, ends = _lib.locate_batch(params, targets, queries)
+    except _lib.GnxError as e:
+        _raise(e)
+    return [int(x) for x in scores], [int(x) for x in ends]
+
+
+def AffineGapLocalEnd(target, query, scores, gapOpen, gapExtend):
+    """(score, targetEnd) of AffineGapLocal(target, query, ...) without its route."""
+    sc, ends = LocateBatch(_lib.make_params(_lib.GNX_AFFINE_GAP_LOCAL, scores, gapOpen, gapExtend), [target], [query])
+    return sc[0], ends[0]
+
+
 def ScoreAllPairs(seqs, params):
     """Scores of all x < y pairs of `seqs` from one device call: {(x, y): score} (what a distance matrix or the choice of the
     nearest pair of a progressive-alignment round needs)."""

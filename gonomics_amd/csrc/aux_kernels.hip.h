@@ -304,5 +304,14 @@ __global__ __launch_bounds__(256) void add_offset_kernel(int64_t *__restrict__ o
     const int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (x < n) off[x] += base;
 }
+// gnx_locate_* on the routes that produce a CIGAR: end[p] = target length minus the trailing GNX_COL_D run of pair p's CIGAR
+__global__ __launch_bounds__(256) void cigar_target_end_kernel(const gnx_cigar *__restrict__ ops, const int64_t *__restrict__ off, const int64_t *__restrict__ target_len,
+                                                               int64_t n, int64_t *__restrict__ end) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    int64_t e = target_len[p];
+    if (off[p + 1] > off[p]) { const gnx_cigar last = ops[off[p + 1] - 1]; if (last.op == GNX_COL_D) e -= last.run_length; }
+    end[p] = e;
+}
 
 } // namespace

@@ -133,6 +133,7 @@ struct Ctx {
     // pipelined host entry (gnx_host.hip.h): double-buffered inputs, results accumulated on the device, the resident reference
     DevBuf pin_a[2], pin_as[2], pin_b[2], pin_bs[2], res_score, res_off, res_ops, ref, gat_score, gat_off, gat_ops;
     // resident seed index of the graph aligner (gnx_seed_index_set)
+    DevBuf ss_len, res_end, gat_end; // gnx_locate_*: target lengths for the end read off a CIGAR, the ends of a host job, their gather on device 0
     DevBuf ss_plans, ss_rowbuf, ss_prog, ss_err, ss_off; // the score-only sweep (score_sweep.hip.h): plans, hand-over rows, progress / claim words, error flags; offsets of a dropped CIGAR
     DevBuf sd_keys, sd_locs, sd_nodes, sd_node_off, sd_word_off, sd_words, sd_tmp[8];
     int64_t sd_n = -1, sd_nodes_n = 0; int sd_seed_len = 0;
@@ -2391,19 +2392,24 @@ int run_host_windows(const gnx_params *prm, int64_t n_pairs,
 // One pass over the batch: pairs sorted by (row blocks, columns) so that the four pairs of a wave are alike, one launch per number
 // of row blocks.  Returns GNX_OK, an error, or -1 when the batch is not the sweep's (the caller then takes the ordinary route and
 // leaves the CIGAR on the device).  Writes d_score[pair] only.
+// AffineGapLocal (fast_path 8): the rows are the QUERY whatever the lengths -- beta, or alpha when
+// query_is_alpha (gnx_locate_batch_by_offset: alpha = reads, beta = target windows of the resident reference; prm->scores is
+// scores[target * 5 + query] either way) -- at most SS_MAX_LEVELS * 160 bases, with gapExtend <= 0 and -2 * gapExtend inside int16
+// as well; d_end != nullptr also receives the target end of every pair.
 int run_score_sweep(const gnx_params *prm, int64_t n_pairs, const uint8_t *d_a, const int64_t *d_as, const uint8_t *d_b, const int64_t *d_bs,
-                    const int64_t *h_alen, const int64_t *h_blen, int64_t *d_score, hipStream_t stream) {
+                    const int64_t *h_alen, const int64_t *h_blen, int64_t *d_score, hipStream_t stream, int64_t *d_end = nullptr, bool query_is_alpha = false) {
     Ctx &c = g_ctx;
     KParams kp; TbParams tp; bool affine, local, lowmem;
     int rc = check_params(prm, kp, tp, affine, local, lowmem);
     if (rc) return rc;
-    if (local || prm->gap_open > 0 || prm->gap_open < -16000 || n_pairs <= 0 || n_pairs > 0x7ffffff0) return -1;
+    if (prm->gap_open > 0 || prm->gap_open < -16000 || n_pairs <= 0 || n_pairs > 0x7ffffff0) return -1;
+    if (local && (prm->gap_extend > 0 || prm->gap_extend < -8000)) return -1;
     if (const char *e = getenv("GNX_SCORE_SWEEP")) if (e[0] == '0') return -1; // (A/B: every score call through the ordinary routes)
     if (lowmem && prm->checkersize_i != prm->checkersize_j) return -1;          // (run_device refuses some of these: let it say so)
     ScoreParams sp;
     const int64_t reb = affine ? prm->gap_extend : prm->gap_open;
     for (int x = 0; x < 25; x++) {
-        const int64_t v = prm->scores[x] - 2 * reb;
+        const int64_t v = prm->scores[(local && query_is_alpha) ? (x % 5) * 5 + x / 5 : x] - 2 * reb; // (the kernel indexes [row base][column base] when the rows are alpha)
         if (v < -16000 || v > 16000) return -1;
         sp.sc[x] = (int)v;
     }
@@ -2417,10 +2423,11 @@ int run_score_sweep(const gnx_params *prm, int64_t n_pairs, const uint8_t *d_a, 
     for (int64_t p = 0; p < n_pairs; p++) {
         const int64_t n = h_alen[p], m = h_blen[p];
         if (n < 1 || m < 1 || n > 0x3fffffff || m > 0x3fffffff) return -1;
-        const int64_t ns = std::min(n, m), ml = std::max(n, m);
+        const bool rows_b = local ? !query_is_alpha : n > m;
+        const int64_t ns = rows_b ? m : n, ml = rows_b ? n : m;
         if (ns > (int64_t)SS_MAX_LEVELS * HB || (n + m + 2) * 2 * maxpen >= ((int64_t)1 << 30)) return -1;
         ScorePlan &pl = plans[(size_t)p];
-        pl.n = (int32_t)ns; pl.m = (int32_t)ml; pl.src = (int32_t)p; pl.swap = n > m ? 1 : 0; pl.rowbuf_off = 0; pl.levels = (int32_t)((ns + HB - 1) / HB); pl._pad = 0;
+        pl.n = (int32_t)ns; pl.m = (int32_t)ml; pl.src = (int32_t)p; pl.swap = rows_b ? 1 : 0; pl.rowbuf_off = 0; pl.levels = (int32_t)((ns + HB - 1) / HB); pl._pad = 0;
         cells += n * m;
         if (p > 0) { const ScorePlan &q = plans[(size_t)p - 1]; if (q.levels > pl.levels || (q.levels == pl.levels && q.m > pl.m)) sorted = false; }
     }
@@ -2462,10 +2469,28 @@ int run_score_sweep(const gnx_params *prm, int64_t n_pairs, const uint8_t *d_a, 
         for (const Group &gq : groups) {
             const ScorePlan *gp = dpl + gq.q0 * 4;
             const int W = (int)gq.nq, S = gq.S;
-            if (S == 1) {
+            if (S == 1 && local) {
+                hipLaunchKernelGGL(score_local_kernel, dim3((unsigned)W), dim3(64), 0, stream, gp, d_a, d_as, d_b, d_bs, kp, sp, d_score, d_end, d_err);
+                launches++;
+            } else if (S == 1) {
                 auto k = affine ? score_sweep_kernel<true> : score_sweep_kernel<false>;
                 hipLaunchKernelGGL(k, dim3((unsigned)W), dim3(64), 0, stream, gp, d_a, d_as, d_b, d_bs, kp, sp, d_score, d_err);
                 launches++;
+            } else if (local) {
+                ScoreLocalLevelsArgs la{gp, d_a, d_as, d_b, d_bs, kp, sp, d_score, d_end, d_err, rb, S, W, 0, 1, prog};
+                if (piped) {
+                    HIPCHK(hipMemsetAsync(prog, 0, ((size_t)S * W * 2 + 2) * 4, stream)); // progress words, claim words, test switch
+                    if ((rc = claim_test_switch(prog + (size_t)S * W * 2, stream))) return rc;
+                    hipLaunchKernelGGL(score_local_levels_kernel, dim3((unsigned)((int64_t)S * W)), dim3(64), 0, stream, la);
+                    launches++;
+                } else {
+                    la.piped = 0;
+                    for (int level = 0; level < S; level++) {
+                        la.level0 = level;
+                        hipLaunchKernelGGL(score_local_levels_kernel, dim3((unsigned)W), dim3(64), 0, stream, la);
+                        launches++;
+                    }
+                }
             } else {
                 auto k = affine ? score_sweep_levels_kernel<true> : score_sweep_levels_kernel<false>;
                 ScoreLevelsArgs la{gp, d_a, d_as, d_b, d_bs, kp, sp, d_score, d_err, rb, S, W, 0, 1, prog};
@@ -2506,7 +2531,7 @@ int run_score_sweep(const gnx_params *prm, int64_t n_pairs, const uint8_t *d_a, 
     if (getenv("GNX_DEBUG")) fprintf(stderr, "[gnx score] score sweep: %lld pairs, %d group(s), %lld launch(es), %.3f ms\n", (long long)n_pairs, (int)groups.size(), (long long)launches, ms);
     c.timing = gnx_timing{};
     c.timing.fill_ms = ms; c.timing.total_ms = ms; c.timing.cells = cells; c.timing.n_launches = 1; c.timing.trace_bytes = 0;
-    c.timing.dominant_ms = ms; c.timing.dominant_launches = launches; c.timing.fast_path = 7;
+    c.timing.dominant_ms = ms; c.timing.dominant_launches = launches; c.timing.fast_path = local ? 8 : 7;
     if (ef & 1) { set_err("a base >= 5 was found: the reference would panic (index out of range)%s", ""); return GNX_EBASE; }
     return GNX_OK;
 }
@@ -2602,7 +2627,7 @@ void gnx_shutdown(void) {
                           &c.fp_wplans[0], &c.fp_wplans[1], &c.fp_active[0], &c.fp_active[1], &c.trace, &c.hcol, &c.rowbuf, &c.dcol, &c.plans, &c.nops, &c.misc, &c.in_a, &c.in_b,
                           &c.in_as, &c.in_al, &c.in_bs, &c.in_bl, &c.out_score, &c.out_off, &c.out_ops, &c.out_end, &c.sc_pairs, &c.sc_mat, &c.sc_err,
                           &c.pin_a[0], &c.pin_a[1], &c.pin_as[0], &c.pin_as[1], &c.pin_b[0], &c.pin_b[1], &c.pin_bs[0], &c.pin_bs[1], &c.res_score, &c.res_off, &c.res_ops,
-                          &c.ref, &c.ref_flag, &c.ref_rank, &c.ref_exc, &c.unpk_b, &c.unpk_off, &c.cl_bases, &c.sc_prof_a, &c.sc_prof_b, &c.mega_rows, &c.mega_state, &c.farm, &c.mega_arena, &c.gat_score, &c.gat_off, &c.gat_ops, &c.ss_plans, &c.ss_rowbuf, &c.ss_prog, &c.ss_err, &c.ss_off, &c.sd_keys, &c.sd_locs, &c.sd_nodes, &c.sd_node_off, &c.sd_word_off, &c.sd_words,
+                          &c.ref, &c.ref_flag, &c.ref_rank, &c.ref_exc, &c.unpk_b, &c.unpk_off, &c.cl_bases, &c.sc_prof_a, &c.sc_prof_b, &c.mega_rows, &c.mega_state, &c.farm, &c.mega_arena, &c.gat_score, &c.gat_off, &c.gat_ops, &c.ss_plans, &c.ss_rowbuf, &c.ss_prog, &c.ss_err, &c.ss_off, &c.ss_len, &c.res_end, &c.gat_end, &c.sd_keys, &c.sd_locs, &c.sd_nodes, &c.sd_node_off, &c.sd_word_off, &c.sd_words,
                           &c.sd_tmp[0], &c.sd_tmp[1], &c.sd_tmp[2], &c.sd_tmp[3], &c.sd_tmp[4], &c.sd_tmp[5], &c.sd_tmp[6], &c.sd_tmp[7]};
         for (DevBuf *b : bufs) b->release();
         PinBuf *pins[] = {&c.h_plans, &c.st_a[0], &c.st_a[1], &c.st_as[0], &c.st_as[1], &c.st_b[0], &c.st_b[1], &c.st_bs[0], &c.st_bs[1]};
@@ -2717,6 +2742,37 @@ int gnx_score_batch(const gnx_params *p, int64_t n_pairs, const uint8_t *alpha_c
     std::vector<int64_t> al((size_t)n_pairs), bl((size_t)n_pairs);
     for (int64_t q = 0; q < n_pairs; q++) { al[(size_t)q] = alpha_off[q + 1] - alpha_off[q]; bl[(size_t)q] = beta_off[q + 1] - beta_off[q]; }
     return gnx_score_batch_windows(p, n_pairs, alpha_cat, alpha_off[n_pairs], alpha_off, al.data(), beta_cat, beta_off[n_pairs], beta_off, bl.data(), out_score);
+}
+
+/* ---- locate entries: AffineGapLocal's score and target end (gnx_align.h) ---- */
+int gnx_locate_batch_windows(const gnx_params *p, int64_t n_pairs,
+                             const uint8_t *target_buf, int64_t target_buf_len, const int64_t *target_start, const int64_t *target_len,
+                             const uint8_t *query_buf, int64_t query_buf_len, const int64_t *query_start, const int64_t *query_len,
+                             int64_t *out_score, int64_t *out_target_end) {
+    std::lock_guard<std::mutex> api(g_api_mu);
+    g_err[0] = 0;
+    static const uint8_t none = 0;
+    if (!out_target_end) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    return run_host_sharded(p, n_pairs, target_buf ? target_buf : &none, target_buf_len, target_start, target_len, query_buf ? query_buf : &none, query_buf_len, query_start, query_len,
+                            out_score, nullptr, nullptr, true, out_target_end, 1);
+}
+
+int gnx_locate_batch(const gnx_params *p, int64_t n_pairs, const uint8_t *target_cat, const int64_t *target_off,
+                     const uint8_t *query_cat, const int64_t *query_off, int64_t *out_score, int64_t *out_target_end) {
+    if (n_pairs < 0 || !target_off || !query_off) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    std::vector<int64_t> tl((size_t)n_pairs), ql((size_t)n_pairs);
+    for (int64_t q = 0; q < n_pairs; q++) { tl[(size_t)q] = target_off[q + 1] - target_off[q]; ql[(size_t)q] = query_off[q + 1] - query_off[q]; }
+    return gnx_locate_batch_windows(p, n_pairs, target_cat, target_off[n_pairs], target_off, tl.data(), query_cat, query_off[n_pairs], query_off, ql.data(), out_score, out_target_end);
+}
+
+int gnx_locate_batch_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *query_cat, const int64_t *query_off,
+                               const int64_t *ref_start, const int64_t *ref_len, int64_t *out_score, int64_t *out_target_end) {
+    std::lock_guard<std::mutex> api(g_api_mu);
+    g_err[0] = 0;
+    if (n_pairs < 0 || !query_off || !out_target_end || (n_pairs > 0 && (!ref_start || !ref_len))) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    std::vector<int64_t> ql((size_t)n_pairs);
+    for (int64_t q = 0; q < n_pairs; q++) ql[(size_t)q] = query_off[q + 1] - query_off[q];
+    return run_host_sharded(p, n_pairs, query_cat, query_off[n_pairs], query_off, ql.data(), nullptr, 0, ref_start, ref_len, out_score, nullptr, nullptr, true, out_target_end, 2);
 }
 
 int gnx_score_batch_device(const gnx_params *p, int64_t n_pairs,

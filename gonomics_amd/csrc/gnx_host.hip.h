@@ -283,6 +283,7 @@ struct HostJob {
     const uint8_t *b_dev = nullptr; // != nullptr: the whole beta buffer / the resident reference is on this context's device
     bool packed = false;            // b_dev is the PACKED resident reference (beta windows = base positions in it)
     bool score_only = false;        // gnx_score_*: scores only (the score sweep, or the ordinary route with its CIGAR left on the device)
+    int locate = 0;                 // gnx_locate_* (score_only as well): 1: alpha = target, beta = query; 2: alpha = query, beta = target (windows of the resident reference)
     int64_t total_ops = 0;
     int rc = GNX_OK;
     char err[512] = "";
@@ -305,9 +306,11 @@ int grow_ops(Ctx &c, int64_t keep_elems, int64_t want_elems, hipStream_t st) {
 
 // A batch of a score-only call on the current context: the score sweep where it applies (run_score_sweep), else the ordinary
 // route, whose CIGAR goes into the context's result buffer and simply stays there.  Sets c.timing like run_device.
+// d_end != nullptr (gnx_locate_*, alpha = target): also the target end of every pair, from the sweep or read off the CIGAR on the
+// device.  try_sweep = false: the caller has tried the sweep already.
 int score_or_fallback(Ctx &c, const gnx_params *prm, int64_t cnt, const uint8_t *d_a, const int64_t *d_as, const uint8_t *d_b, const int64_t *d_bs,
-                      const int64_t *h_alen, const int64_t *h_blen, int64_t *d_score, hipStream_t stream) {
-    int rc = run_score_sweep(prm, cnt, d_a, d_as, d_b, d_bs, h_alen, h_blen, d_score, stream);
+                      const int64_t *h_alen, const int64_t *h_blen, int64_t *d_score, hipStream_t stream, int64_t *d_end = nullptr, bool try_sweep = true) {
+    int rc = try_sweep ? run_score_sweep(prm, cnt, d_a, d_as, d_b, d_bs, h_alen, h_blen, d_score, stream, d_end) : -1;
     if (rc != -1) return rc;
     if ((rc = c.ss_off.ensure((size_t)(std::max<int64_t>(cnt, 0) + 1) * 8))) return rc;
     if ((rc = grow_ops(c, 0, std::max<int64_t>((int64_t)1 << 20, 64 * cnt), stream))) return rc;
@@ -316,6 +319,14 @@ int score_or_fallback(Ctx &c, const gnx_params *prm, int64_t cnt, const uint8_t 
         rc = run_device(prm, cnt, d_a, d_as, d_b, d_bs, h_alen, h_blen, d_score, (gnx_cigar *)c.res_ops.p, (int64_t)(c.res_ops.cap / sizeof(gnx_cigar)), (int64_t *)c.ss_off.p, &tot, stream);
         if (rc != GNX_ECAPACITY || attempt >= 8) break;
         if ((rc = grow_ops(c, 0, tot + 1024, stream))) break;
+    }
+    if (rc == GNX_OK && d_end && cnt > 0) {
+        if ((rc = c.ss_len.ensure((size_t)cnt * 8))) return rc;
+        HIPCHK(hipMemcpyAsync(c.ss_len.p, h_alen, (size_t)cnt * 8, hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(cigar_target_end_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, (const gnx_cigar *)c.res_ops.p, (const int64_t *)c.ss_off.p,
+                           (const int64_t *)c.ss_len.p, cnt, d_end);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(stream)); // h_alen is the caller's
     }
     return rc;
 }
@@ -327,6 +338,7 @@ int run_host_job(HostJob &j) {
     int rc;
     if ((rc = c.res_score.ensure((size_t)std::max<int64_t>(n, 1) * 8))) return rc;
     if ((rc = c.res_off.ensure((size_t)(n + 1) * 8))) return rc;
+    if (j.locate && (rc = c.res_end.ensure((size_t)std::max<int64_t>(n, 1) * 8))) return rc;
     if (n == 0) { HIPCHK(hipMemsetAsync(c.res_off.p, 0, 8, c.own_stream)); HIPCHK(hipStreamSynchronize(c.own_stream)); return GNX_OK; }
     int64_t sub = 131072;
     if (const char *e = getenv("GNX_HOST_SUB")) sub = (std::max<int64_t>(atoll(e), 8) + 7) & ~(int64_t)7;
@@ -407,25 +419,34 @@ int run_host_job(HostJob &j) {
         const uint8_t *db = j.b_dev ? j.b_dev : (const uint8_t *)c.pin_b[slot].p;
         const int64_t *dbs = (const int64_t *)c.pin_bs[slot].p;
         bool packed = j.packed;
-        if (packed && rc == GNX_OK && (j.prm->mode == GNX_AFFINE_GAP_LOCAL || getenv("GNX_REF_UNPACK"))) {
-            // the windows as bytes (AffineGapLocal's transposed fast path reads the long sequence as the kernels' alpha; GNX_REF_UNPACK: A/B)
+        // the windows as bytes (AffineGapLocal's transposed fast path reads the long sequence as the kernels' alpha; GNX_REF_UNPACK: A/B)
+        auto unpack_windows = [&]() -> int {
             std::vector<int64_t> uoff((size_t)cnt + 1, 0);
             for (int64_t q = 0; q < cnt; q++) { uoff[(size_t)q + 1] = uoff[(size_t)q] + bl[b + q]; }
-            if ((rc = c.in_b.ensure((size_t)uoff[(size_t)cnt] + 64)) == GNX_OK && (rc = c.in_bl.ensure((size_t)(cnt + 1) * 8)) == GNX_OK) {
-                KParams ukp;
-                memset(&ukp, 0, sizeof(ukp));
-                ukp.b2 = (const unsigned *)c.ref.p; ukp.bflag = (const unsigned long long *)c.ref_flag.p; ukp.brank = (const unsigned *)c.ref_rank.p; ukp.bexc = (const unsigned long long *)c.ref_exc.p;
-                if (hipMemcpyAsync(c.in_bl.p, uoff.data(), (size_t)(cnt + 1) * 8, hipMemcpyHostToDevice, c.own_stream) != hipSuccess || hipStreamSynchronize(c.own_stream) != hipSuccess) { set_err("upload of the window table failed%s", ""); rc = GNX_EDEVICE; }
-                else {
-                    hipLaunchKernelGGL(unpack_windows_kernel, dim3((unsigned)cnt), dim3(256), 0, c.own_stream, ukp, dbs, (const int64_t *)c.in_bl.p, (int)cnt, (uint8_t *)c.in_b.p);
-                    if (hipGetLastError() != hipSuccess) { set_err("unpack_windows_kernel failed to launch%s", ""); rc = GNX_EDEVICE; }
-                    db = (const uint8_t *)c.in_b.p; dbs = (const int64_t *)c.in_bl.p; packed = false;
-                }
-            }
-        }
-        if (j.score_only && rc == GNX_OK) {
+            int r;
+            if ((r = c.in_b.ensure((size_t)uoff[(size_t)cnt] + 64)) || (r = c.in_bl.ensure((size_t)(cnt + 1) * 8))) return r;
+            KParams ukp;
+            memset(&ukp, 0, sizeof(ukp));
+            ukp.b2 = (const unsigned *)c.ref.p; ukp.bflag = (const unsigned long long *)c.ref_flag.p; ukp.brank = (const unsigned *)c.ref_rank.p; ukp.bexc = (const unsigned long long *)c.ref_exc.p;
+            if (hipMemcpyAsync(c.in_bl.p, uoff.data(), (size_t)(cnt + 1) * 8, hipMemcpyHostToDevice, c.own_stream) != hipSuccess || hipStreamSynchronize(c.own_stream) != hipSuccess) { set_err("upload of the window table failed%s", ""); return GNX_EDEVICE; }
+            hipLaunchKernelGGL(unpack_windows_kernel, dim3((unsigned)cnt), dim3(256), 0, c.own_stream, ukp, dbs, (const int64_t *)c.in_bl.p, (int)cnt, (uint8_t *)c.in_b.p);
+            if (hipGetLastError() != hipSuccess) { set_err("unpack_windows_kernel failed to launch%s", ""); return GNX_EDEVICE; }
+            db = (const uint8_t *)c.in_b.p; dbs = (const int64_t *)c.in_bl.p; packed = false;
+            return GNX_OK;
+        };
+        // (gnx_locate_batch_by_offset: the local sweep reads its target packed; only its fallback needs bytes)
+        if (packed && rc == GNX_OK && j.locate != 2 && (j.prm->mode == GNX_AFFINE_GAP_LOCAL || getenv("GNX_REF_UNPACK"))) rc = unpack_windows();
+        if (j.score_only && j.locate == 2 && rc == GNX_OK) { // alpha = queries, beta = targets: the sweep as it is, the ordinary route with the two swapped
+            int64_t *d_sc = (int64_t *)c.res_score.p + done, *d_en = (int64_t *)c.res_end.p + done;
             c.beta_packed = packed;
-            rc = score_or_fallback(c, j.prm, cnt, (const uint8_t *)c.pin_a[slot].p, (const int64_t *)c.pin_as[slot].p, db, dbs, al + b, bl + b, (int64_t *)c.res_score.p + done, c.own_stream);
+            rc = run_score_sweep(j.prm, cnt, (const uint8_t *)c.pin_a[slot].p, (const int64_t *)c.pin_as[slot].p, db, dbs, al + b, bl + b, d_sc, c.own_stream, d_en, true);
+            c.beta_packed = false;
+            if (rc == -1 && (!packed || (rc = unpack_windows()) == GNX_OK))
+                rc = score_or_fallback(c, j.prm, cnt, db, dbs, (const uint8_t *)c.pin_a[slot].p, (const int64_t *)c.pin_as[slot].p, bl + b, al + b, d_sc, c.own_stream, d_en, false);
+        } else if (j.score_only && rc == GNX_OK) {
+            c.beta_packed = packed;
+            rc = score_or_fallback(c, j.prm, cnt, (const uint8_t *)c.pin_a[slot].p, (const int64_t *)c.pin_as[slot].p, db, dbs, al + b, bl + b, (int64_t *)c.res_score.p + done, c.own_stream,
+                                   j.locate ? (int64_t *)c.res_end.p + done : nullptr);
             c.beta_packed = false;
         }
         for (int attempt = 0; rc == GNX_OK && !j.score_only; attempt++) {
@@ -566,10 +587,12 @@ int ensure_reference(int nc) {
 int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
                      const uint8_t *a_buf, int64_t a_len_total, const int64_t *a_start, const int64_t *a_lens,
                      const uint8_t *b_buf, int64_t b_len_total, const int64_t *b_start, const int64_t *b_lens,
-                     int64_t *out_score, gnx_cigar **out_ops, int64_t **out_ops_off, bool score_only = false) {
+                     int64_t *out_score, gnx_cigar **out_ops, int64_t **out_ops_off, bool score_only = false, int64_t *out_end = nullptr, int locate = 0) {
     const auto t_entry = std::chrono::steady_clock::now();
     if (!prm || n_pairs < 0 || !out_score || (!score_only && (!out_ops || !out_ops_off)) || a_len_total < 0 || b_len_total < 0) { set_err("bad argument%s", ""); return GNX_EINVAL; }
     if (n_pairs > 0 && (!a_start || !a_lens || !b_start || !b_lens)) { set_err("null window table%s", ""); return GNX_EINVAL; }
+    if (locate && (!score_only || !out_end)) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (locate && prm->mode != GNX_AFFINE_GAP_LOCAL) { set_err("gnx_locate_*: the mode must be GNX_AFFINE_GAP_LOCAL%s", ""); return GNX_EINVAL; }
     const bool resident = (b_buf == nullptr);
     Ctx &c0 = ctx_at(0);
     int rc;
@@ -617,6 +640,7 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
         j.b_dev = (const uint8_t *)bdev[(size_t)d];
         j.packed = resident;
         j.score_only = score_only;
+        j.locate = locate;
     }
     auto work = [](HostJob *j) {
         CtxScope sc(*j->c);
@@ -647,6 +671,7 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
         if ((rc = c0.gat_score.ensure((size_t)std::max<int64_t>(n_pairs, 1) * 8))) return fail(rc);
         if ((rc = c0.gat_off.ensure((size_t)(n_pairs + nc) * 8))) return fail(rc);
         if ((rc = c0.gat_ops.ensure((size_t)std::max<int64_t>(total, 1) * sizeof(gnx_cigar)))) return fail(rc);
+        if (locate && (rc = c0.gat_end.ensure((size_t)std::max<int64_t>(n_pairs, 1) * 8))) return fail(rc);
         // context 0's own share never goes through RCCL (no send-to-self): a device-to-device copy on its stream
         auto gather_local = [&]() -> int {
             HostJob &j = jobs[0];
@@ -655,6 +680,7 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
             if (nd > 0) {
                 HIPCHK(hipMemcpyAsync((int64_t *)c0.gat_score.p + j.p0, c0.res_score.p, (size_t)nd * 8, hipMemcpyDeviceToDevice, c0.own_stream));
                 HIPCHK(hipMemcpyAsync((int64_t *)c0.gat_off.p + j.p0, c0.res_off.p, (size_t)(nd + 1) * 8, hipMemcpyDeviceToDevice, c0.own_stream));
+                if (locate) HIPCHK(hipMemcpyAsync((int64_t *)c0.gat_end.p + j.p0, c0.res_end.p, (size_t)nd * 8, hipMemcpyDeviceToDevice, c0.own_stream));
             }
             if (j.total_ops > 0) HIPCHK(hipMemcpyAsync(c0.gat_ops.p, c0.res_ops.p, (size_t)j.total_ops * sizeof(gnx_cigar), hipMemcpyDeviceToDevice, c0.own_stream));
             return GNX_OK;
@@ -670,6 +696,7 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
                     if (nd > 0) {
                         RCCLCHK(g_rccl.Send(c.res_score.p, (size_t)nd, ncclInt64, 0, g_rccl.comms[(size_t)d], c.own_stream));
                         RCCLCHK(g_rccl.Send(c.res_off.p, (size_t)nd + 1, ncclInt64, 0, g_rccl.comms[(size_t)d], c.own_stream));
+                        if (locate) RCCLCHK(g_rccl.Send(c.res_end.p, (size_t)nd, ncclInt64, 0, g_rccl.comms[(size_t)d], c.own_stream));
                     }
                     if (d == 1 && rccl_injected_failure(2)) return GNX_EDEVICE; // (a send is enqueued, its receive is not)
                     if (j.total_ops > 0) RCCLCHK(g_rccl.Send(c.res_ops.p, (size_t)j.total_ops * 2, ncclInt64, 0, g_rccl.comms[(size_t)d], c.own_stream));
@@ -677,6 +704,7 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
                     if (nd > 0) {
                         RCCLCHK(g_rccl.Recv((int64_t *)c0.gat_score.p + j.p0, (size_t)nd, ncclInt64, d, g_rccl.comms[0], c0.own_stream));
                         RCCLCHK(g_rccl.Recv((int64_t *)c0.gat_off.p + j.p0 + d, (size_t)nd + 1, ncclInt64, d, g_rccl.comms[0], c0.own_stream));
+                        if (locate) RCCLCHK(g_rccl.Recv((int64_t *)c0.gat_end.p + j.p0, (size_t)nd, ncclInt64, d, g_rccl.comms[0], c0.own_stream));
                     }
                     if (j.total_ops > 0) RCCLCHK(g_rccl.Recv((gnx_cigar *)c0.gat_ops.p + obase, (size_t)j.total_ops * 2, ncclInt64, d, g_rccl.comms[0], c0.own_stream));
                     obase += j.total_ops;
@@ -697,6 +725,7 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
                 if (nd > 0) {
                     HIPCHK(hipMemcpyPeer((int64_t *)c0.gat_score.p + j.p0, c0.device, c.res_score.p, c.device, (size_t)nd * 8));
                     HIPCHK(hipMemcpyPeer((int64_t *)c0.gat_off.p + j.p0 + d, c0.device, c.res_off.p, c.device, (size_t)(nd + 1) * 8));
+                    if (locate) HIPCHK(hipMemcpyPeer((int64_t *)c0.gat_end.p + j.p0, c0.device, c.res_end.p, c.device, (size_t)nd * 8));
                 }
                 if (j.total_ops > 0) HIPCHK(hipMemcpyPeer((gnx_cigar *)c0.gat_ops.p + obase, c0.device, c.res_ops.p, c.device, (size_t)j.total_ops * sizeof(gnx_cigar)));
                 obase += j.total_ops;
@@ -723,6 +752,7 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
     auto fetch = [&]() -> int {
         hipStream_t st = c0.own_stream;
         if (n_pairs) HIPCHK(hipMemcpyAsync(out_score, d_score, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
+        if (n_pairs && locate) HIPCHK(hipMemcpyAsync(out_end, nc > 1 ? c0.gat_end.p : c0.res_end.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
         if (total) HIPCHK(hipMemcpyAsync(ops, d_ops, (size_t)total * sizeof(gnx_cigar), hipMemcpyDeviceToHost, st));
         if (score_only) { /* only the score vector comes back */ }
         else if (nc == 1) HIPCHK(hipMemcpyAsync(off, d_off, (size_t)(n_pairs + 1) * 8, hipMemcpyDeviceToHost, st));

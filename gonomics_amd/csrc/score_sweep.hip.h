@@ -67,13 +67,26 @@ __device__ __forceinline__ void score_table_to_lds(int *lds, const ScoreParams &
 // TAKES / HANDS: the block takes the row above it from the row buffer / hands its bottom row down (compile-time constants in the
 // one-block kernel; wave-uniform run-time values in the levels kernel, which holds ONE copy of the body: three inlined copies leave it
 // short of scalar registers)
-template <int RR, bool AFF>
+// what only the LOCAL body carries (an empty struct otherwise: the global instantiations hold nothing of it)
+template <bool LOCAL> struct SweepLocal {};
+template <> struct SweepLocal<true> {
+    int zrow;   // level 0: the slot above the first one holds h = 0 at every column: h'(c) = -e * (c - P), stepped along with t (the first lane is at column t)
+    int bshift; // the last row's running maximum of max(M, I) in the frame of the NEXT column (minus e per step); column 0 is I(0, n) = o + n * e
+    int end_t;  // the step of its last >= update (the last lane is at column t - 15)
+    int vE;     // gapExtend in a vector register (the levels kernel has no scalar register to spare)
+};
+// where a LOCAL body finds its two result vectors when it is done (the levels kernel reads them from its argument segment then)
+struct NoOuts { __device__ __forceinline__ int64_t *score() const { return nullptr; } __device__ __forceinline__ int64_t *end() const { return nullptr; } };
+
+template <int RR, bool AFF, bool LOCAL = false, class Outs = NoOuts>
 __device__ __forceinline__ void score_sweep_body(int *__restrict__ lds, const int quad, const ScorePlan *__restrict__ plans,
                                                  const uint8_t *__restrict__ a_buf, const int64_t *__restrict__ a_start,
                                                  const uint8_t *__restrict__ b_buf, const int64_t *__restrict__ b_start,
                                                  const KParams &kp, const int sp_o, const int sp_e, int64_t *__restrict__ out_score, int *__restrict__ err,
-                                                 int2 *__restrict__ rowbuf, const int level, const bool TAKES, const bool HANDS, const bool piped, const int *prog_in, int *prog_out) {
+                                                 int2 *__restrict__ rowbuf, const int level, const bool TAKES, const bool HANDS, const bool piped, const int *prog_in, int *prog_out,
+                                                 const Outs outs = Outs()) {
     static_assert(RR == 2 * (SS_LW - 1), "profile words per lane");
+    static_assert(AFF || !LOCAL, "the local sweep is affine");
     constexpr int HB = G * RR; // rows of a block
     const int lane = threadIdx.x;
     const int g = lane >> 4, lp = lane & 15;
@@ -123,16 +136,23 @@ __device__ __forceinline__ void score_sweep_body(int *__restrict__ lds, const in
         }
     }
     // column 0 (see the head of the file): real row: h' = D' = o, I'(i,1) = 2o; padding: h' = I' = o; the slot above row 1: h'(0,0) = 0
-    auto hcol0 = [&](int q) { return (AFF && q != P - 1) ? O : 0; };
+    // LOCAL: row 0 and every padding slot hold h = 0, rebased -e * (slot - P + 1); their I' starts at h' + o (a gap that never wins)
+    auto hcol0 = [&](int q) { if constexpr (LOCAL) return q >= P ? O : -sp_e * (q - P + 1); else return (AFF && q != P - 1) ? O : 0; };
     int rt[RR], hold[RR];
 #pragma unroll
     for (int r = 0; r < RR; r++) {
         hold[r] = hcol0(q0 + r);
-        rt[r] = (q0 + r >= P) ? 2 * O : O;
+        if constexpr (LOCAL) rt[r] = (q0 + r >= P) ? 2 * O : hcol0(q0 + r) + O;
+        else rt[r] = (q0 + r >= P) ? 2 * O : O;
     }
     int diag0 = hcol0(q0 - 1);
     int dn_out = 0, h_out = 0;
     int up_dn = 2 * O, up_h = O; // level 0: the first lane keeps the row-0 constants as the `old` operand of its DPP moves
+    SweepLocal<LOCAL> lo;
+    if constexpr (LOCAL) {
+        lo.zrow = sp_e * P; lo.bshift = O - sp_e; lo.end_t = lp;
+        asm volatile("v_mov_b32 %0, %1" : "=v"(lo.vE) : "s"(sp_e));
+    }
     int vO;
     asm volatile("v_mov_b32 %0, %1" : "=v"(vO) : "s"(O));
 
@@ -185,8 +205,14 @@ __device__ __forceinline__ void score_sweep_body(int *__restrict__ lds, const in
 
     auto step = [&](const int t, auto chk) {
         constexpr bool CHECK = decltype(chk)::value; // false: every lane of the wave is inside its matrix
-        if (AFF) up_dn = dpp_shr1(TAKES ? rq.x : up_dn, dn_out);
-        up_h = dpp_shr1(TAKES ? rq.y : up_h, h_out);
+        if constexpr (LOCAL) {
+            up_dn = dpp_shr1(TAKES ? rq.x : lo.zrow + vO, dn_out);
+            up_h = dpp_shr1(TAKES ? rq.y : lo.zrow, h_out);
+            lo.zrow -= lo.vE;
+        } else {
+            if (AFF) up_dn = dpp_shr1(TAKES ? rq.x : up_dn, dn_out);
+            up_h = dpp_shr1(TAKES ? rq.y : up_h, h_out);
+        }
         const int pbn = dpp_shr1(bnext, pb); // base of step t + 1
         bnext = bring[(t + 2) & (SS_RING - 1)];
         if (TAKES) { rq = rq1; rq1 = hring[(t + 2) & (SS_RING - 1)]; }
@@ -201,6 +227,11 @@ __device__ __forceinline__ void score_sweep_body(int *__restrict__ lds, const in
                 const int S = (r & 1) ? (wq[r >> 1] >> 16) : (int)(short)(wq[r >> 1] & 0xffff);
                 const int M = hd + S;
                 hd = hold[r];
+                if constexpr (LOCAL) if (r == RR - 1) { // the last slot of a lane: row n in the last lane of the last level (elsewhere the result is not read)
+                    const int cand = max(M, dnu);
+                    lo.end_t = cand >= lo.bshift ? t : lo.end_t;
+                    lo.bshift = max(cand, lo.bshift) - lo.vE;
+                }
                 if (AFF) {
                     const int hnew = max3i(M, rt[r], dnu);
                     const int ho = hnew + vO;
@@ -252,7 +283,13 @@ __device__ __forceinline__ void score_sweep_body(int *__restrict__ lds, const in
         hand_down(t0);
     }
     if (HANDS && piped) rb_publish(prog_out, 0x7fffffff, lane);
-    if (!HANDS && lp == G - 1 && valid) out_score[pl.src] = (int64_t)hold[RR - 1] + (int64_t)sp_e * ((int64_t)pl.n + pl.m);
+    if constexpr (LOCAL) {
+        if (!HANDS && lp == G - 1 && valid) {
+            outs.score()[pl.src] = (int64_t)lo.bshift + (int64_t)sp_e * ((int64_t)pl.n + pl.m + 1);
+            int64_t *out_end = outs.end();
+            if (out_end) out_end[pl.src] = lo.end_t - lp;
+        }
+    } else if (!HANDS && lp == G - 1 && valid) out_score[pl.src] = (int64_t)hold[RR - 1] + (int64_t)sp_e * ((int64_t)pl.n + pl.m);
     if (bad) atomicOr(err, 1);
 }
 
@@ -305,6 +342,60 @@ __global__ __launch_bounds__(64) void score_sweep_levels_kernel(ScoreLevelsArgs 
         if (lv != lv_own - n_stolen) __syncthreads(); // the LDS profile of the level before is no longer read
         score_sweep_body<SS_RR, AFF>(lds, w, ka->plans, ka->a_buf, ka->a_start, ka->b_buf, ka->b_start, kp, ka->sp.o, ka->sp.e, ka->out_score, ka->err, ka->rowbuf,
                                      level, level > 0, level < S - 1, ka->piped != 0, pi, po);
+    }
+}
+
+// ---- AffineGapLocal: score and target end ------------------------------------------------------------------
+// The same sweep with LOCAL set: rows (lanes) are always the QUERY, columns the target whose ends are free (ScorePlan::swap only says
+// which of the two buffers holds the rows).  Row 0 and the padding above it hold h = 0 on every column (profile entry -2e: a diagonal
+// move of score 0; needs gapOpen <= 0 and gapExtend <= 0), the last row keeps the running maximum of max(M, I) over the columns and
+// the column of its last >= update: the score of AffineGapLocal(target, query) and the target position behind its last aligned column.
+__global__ __launch_bounds__(64) void score_local_kernel(const ScorePlan *__restrict__ plans, const uint8_t *__restrict__ a_buf, const int64_t *__restrict__ a_start,
+                                                         const uint8_t *__restrict__ b_buf, const int64_t *__restrict__ b_start, KParams kp, ScoreParams sp,
+                                                         int64_t *__restrict__ out_score, int64_t *__restrict__ out_end, int *__restrict__ err) {
+    __shared__ __attribute__((aligned(16))) int lds[SS_LDS];
+    {
+        const int lane = threadIdx.x;
+        if (lane < 25) lds[lane] = sp.sc[lane];
+        else if (lane < 32) lds[lane] = -2 * sp.e; // padding rows: a diagonal move of score 0
+    }
+    struct Outs { int64_t *s, *e; __device__ __forceinline__ int64_t *score() const { return s; } __device__ __forceinline__ int64_t *end() const { return e; } };
+    score_sweep_body<SS_RR, true, true>(lds, (int)blockIdx.x, plans, a_buf, a_start, b_buf, b_start, kp, sp.o, sp.e, nullptr, err, nullptr, 0, false, false, false, nullptr, nullptr, Outs{out_score, out_end});
+}
+
+struct ScoreLocalLevelsArgs {
+    const ScorePlan *plans; const uint8_t *a_buf; const int64_t *a_start; const uint8_t *b_buf; const int64_t *b_start;
+    KParams kp; ScoreParams sp;
+    int64_t *out_score; int64_t *out_end; int *err; int2 *rowbuf;
+    int S, W, level0, piped;
+    int *prog;
+};
+// grid, claims and arguments as in score_sweep_levels_kernel
+__global__ __launch_bounds__(64) void score_local_levels_kernel(ScoreLocalLevelsArgs by_value) {
+    __shared__ __attribute__((aligned(16))) int lds[SS_LDS];
+    (void)by_value;
+    typedef const __attribute__((address_space(4))) ScoreLocalLevelsArgs *ArgPtr;
+    struct Outs { ArgPtr ka; __device__ __forceinline__ int64_t *score() const { return ka->out_score; } __device__ __forceinline__ int64_t *end() const { return ka->out_end; } };
+    ArgPtr ka = (ArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    const int W = ka->W;
+    const int lv_own = (int)blockIdx.x / W, w = (int)blockIdx.x - lv_own * W;
+    int n_stolen = 0;
+    if (ka->piped) { n_stolen = claim_items(ka->prog + (int64_t)ka->S * W, W, lv_own); if (n_stolen < 0) return; }
+    {
+        const int lane = threadIdx.x;
+        if (lane < 25) lds[lane] = ka->sp.sc[lane];
+        else if (lane < 32) lds[lane] = -2 * ka->sp.e; // padding rows: a diagonal move of score 0
+    }
+    for (int lv = lv_own - n_stolen; lv <= lv_own; lv++) {
+        asm volatile("" : "+s"(ka));
+        const int S = ka->S, Wk = ka->W, level = ka->level0 + lv;
+        int *po = ka->prog + (int64_t)level * Wk + w;
+        const int *pi = po - Wk;
+        KParams kp;
+        kp.b2 = ka->kp.b2; kp.bflag = ka->kp.bflag; kp.brank = ka->kp.brank; kp.bexc = ka->kp.bexc;
+        if (lv != lv_own - n_stolen) __syncthreads(); // the LDS profile of the level before is no longer read
+        score_sweep_body<SS_RR, true, true>(lds, w, ka->plans, ka->a_buf, ka->a_start, ka->b_buf, ka->b_start, kp, ka->sp.o, ka->sp.e, nullptr, ka->err, ka->rowbuf,
+                                            level, level > 0, level < S - 1, ka->piped != 0, pi, po, Outs{ka});
     }
 }
 

@@ -98,7 +98,8 @@ typedef struct gnx_timing {
                             2: the constant-gap path without a stored direction matrix (const_long.hip.h); 0: full direction matrix;
                             3 / 4: the latency geometry (few pairs) in its int32 / int64 form; 5: the 64-lane affine snapshot path;
                             6: the constant-gap snapshot path in its 64-lane form; 7: the score-only sweep ran (gnx_score_* entries,
-                            score_sweep.hip.h).  Multi-context score calls report the maximum over contexts. */
+                            score_sweep.hip.h); 8: its AffineGapLocal variant ran (gnx_score_* with GNX_AFFINE_GAP_LOCAL, gnx_locate_*).
+                            Multi-context score calls report the maximum over contexts. */
     int32_t _pad;
     /* host-buffer entry points only (wall clock inside the library): */
     double host_ms;      /* entry to return of the whole call */
@@ -204,7 +205,9 @@ int gnx_align_batch_device(const gnx_params *p, int64_t n_pairs,
  * (GNX_AFFINE_GAP, GNX_CONST_GAP and their _HIGHMEM twins) with gapOpen <= 0 when every pair of the (sub-)batch has both sequences
  * non-empty, the shorter one at most 10 240 bases, and the static bound (n + m + 2) * 2 * max|penalty| below 2^30, with matrix
  * entries s - 2 * gapExtend (constant gap: s - 2 * gapPen) and gapOpen inside +-16 000; beta from plain bytes or the packed resident
- * reference.  Everything else -- GNX_AFFINE_GAP_LOCAL, gapOpen > 0, empty sequences in the high-memory modes, pairs beyond those
+ * reference.  GNX_AFFINE_GAP_LOCAL (alpha = target, beta = query, as in gnx_align_batch) takes the local variant of the sweep (8)
+ * under the conditions listed at gnx_locate_batch below.  Everything else -- gapOpen > 0, a local call with gapExtend > 0, empty
+ * sequences in the high-memory modes, pairs beyond those
  * bounds -- runs the route gnx_align_batch would take, and its CIGAR is dropped on the device before anything is copied back.
  * Multi-context calls (gnx_init_devices) shard and gather like the align entries; only the score vector comes back. */
 int gnx_score_batch(const gnx_params *p, int64_t n_pairs, const uint8_t *alpha_cat, const int64_t *alpha_off,
@@ -220,6 +223,31 @@ int gnx_score_batch_device(const gnx_params *p, int64_t n_pairs,
                            const uint8_t *d_alpha_buf, const int64_t *d_alpha_start, const int64_t *d_alpha_len,
                            const uint8_t *d_beta_buf, const int64_t *d_beta_start, const int64_t *d_beta_len,
                            const int64_t *h_alpha_len, const int64_t *h_beta_len, int64_t *d_score, void *stream);
+
+/* ---- locate entries: AffineGapLocal's score and the target END of its alignment, without a CIGAR (an extension, no Go signature) -- */
+/* Arguments are named by ROLE: the query is aligned end to end, the target's ends are free (AffineGapLocal(target, query); the
+ * reference's "150bp sequencing read to a 1kb reference sequence").  p->mode must be GNX_AFFINE_GAP_LOCAL (else GNX_EINVAL); both
+ * out_score[n_pairs] and out_target_end[n_pairs] are required.  p->scores stays scores[target * 5 + query].
+ * Contract: out_score[p] equals the score gnx_align_batch returns for AffineGapLocal(target, query); out_target_end[p] equals
+ * len(target) minus the run length of that CIGAR's trailing GNX_COL_D run (0 if it does not end in one): the target position just
+ * after the last aligned column.  An empty query gives end 0.  Validation and error codes are those of the align twin (GNX_EBASE,
+ * GNX_EINVAL, GNX_EDEVICE); never GNX_ERANGE; no CPU fallback.
+ * Routes: the local score sweep (gnx_timing.fast_path == 8) when gapOpen <= 0 and gapExtend <= 0, every pair of the (sub-)batch has
+ * both sequences non-empty, the QUERY is at most 10 240 bases (the target may have any length, also shorter than the query),
+ * s - 2 * gapExtend, -2 * gapExtend and gapOpen are inside +-16 000 and (n + m + 2) * 2 * max|penalty| is below 2^30; GNX_SCORE_SWEEP=0
+ * switches it off.  Everything else runs the route gnx_align_batch takes, and a small kernel reads the end off the CIGAR on the
+ * device: the end is defined identically on every route.  Multi-context calls shard and gather both vectors. */
+int gnx_locate_batch(const gnx_params *p, int64_t n_pairs, const uint8_t *target_cat, const int64_t *target_off,
+                     const uint8_t *query_cat, const int64_t *query_off, int64_t *out_score, int64_t *out_target_end);
+int gnx_locate_batch_windows(const gnx_params *p, int64_t n_pairs,
+                             const uint8_t *target_buf, int64_t target_buf_len, const int64_t *target_start, const int64_t *target_len,
+                             const uint8_t *query_buf, int64_t query_buf_len, const int64_t *query_start, const int64_t *query_len,
+                             int64_t *out_score, int64_t *out_target_end);
+/* The read-mapping case: the TARGET is the window (ref_start[p], ref_len[p]) of the resident reference (gnx_set_reference; read
+ * packed, 2 bits per base), the reads are the QUERIES.  Mind that gnx_align_batch_by_offset with GNX_AFFINE_GAP_LOCAL has the roles
+ * the other way round (its alpha, the reads, is the target there). */
+int gnx_locate_batch_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *query_cat, const int64_t *query_off,
+                               const int64_t *ref_start, const int64_t *ref_len, int64_t *out_score, int64_t *out_target_end);
 
 int gnx_get_timing(gnx_timing *out);
 /* Diagnostics (tests only; nothing in the reference corresponds to it): launch n_workgroups workgroups that each hold one CU's whole

@@ -167,6 +167,32 @@ inline int64_t AffineGapLocalScore(const std::vector<dna::Base> &target, const s
     return ScoreBatch(GNX_AFFINE_GAP_LOCAL, scores, gapOpen, gapExtend, {target}, {query})[0];
 }
 
+// ---- locate calls (gnx_locate_*; an extension) ----
+// AffineGapLocal's score and target end for every (target, query) pair: {scores, targetEnds}; targetEnd = target length minus the
+// trailing ColD run of the route AffineGapLocal returns (the target position just after the last aligned column).
+inline std::pair<std::vector<int64_t>, std::vector<int64_t>> LocateBatch(const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend,
+                                                                         const std::vector<std::vector<dna::Base>> &targets, const std::vector<std::vector<dna::Base>> &queries) {
+    const int64_t n = (int64_t)targets.size();
+    std::vector<int64_t> toff((size_t)n + 1, 0), qoff((size_t)n + 1, 0);
+    for (int64_t k = 0; k < n; k++) { toff[(size_t)k + 1] = toff[(size_t)k] + (int64_t)targets[(size_t)k].size(); qoff[(size_t)k + 1] = qoff[(size_t)k] + (int64_t)queries[(size_t)k].size(); }
+    std::vector<dna::Base> tcat((size_t)toff[(size_t)n] + 1), qcat((size_t)qoff[(size_t)n] + 1);
+    for (int64_t k = 0; k < n; k++) {
+        std::copy(targets[(size_t)k].begin(), targets[(size_t)k].end(), tcat.begin() + toff[(size_t)k]);
+        std::copy(queries[(size_t)k].begin(), queries[(size_t)k].end(), qcat.begin() + qoff[(size_t)k]);
+    }
+    const gnx_params p = detail::params(GNX_AFFINE_GAP_LOCAL, scores, gapOpen, gapExtend, 10000, 10000);
+    std::vector<int64_t> sc((size_t)std::max<int64_t>(n, 1), 0), end((size_t)std::max<int64_t>(n, 1), 0);
+    const int rc = gnx_locate_batch(&p, n, tcat.data(), toff.data(), qcat.data(), qoff.data(), sc.data(), end.data());
+    if (rc) detail::raise(rc);
+    sc.resize((size_t)n); end.resize((size_t)n);
+    return {sc, end};
+}
+// {score, targetEnd} of AffineGapLocal(target, query, ...) without its route
+inline std::pair<int64_t, int64_t> AffineGapLocalEnd(const std::vector<dna::Base> &target, const std::vector<dna::Base> &query, const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend) {
+    const auto r = LocateBatch(scores, gapOpen, gapExtend, {target}, {query});
+    return {r.first[0], r.second[0]};
+}
+
 inline void AffineGapLocalEngine(const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, std::vector<TargetQueryPair> &pairs) {
     std::vector<std::vector<dna::Base>> t, q;
     for (auto &p : pairs) { t.push_back(p.Target); q.push_back(p.Query); }
