@@ -20,7 +20,8 @@ EXPORTS = ["gnx_device_count", "gnx_init", "gnx_shutdown", "gnx_last_error", "gn
            "gnx_init_devices", "gnx_n_devices", "gnx_set_reference", "gnx_set_reference_synthetic", "gnx_align_batch_by_offset",
            "gnx_seed_index_build", "gnx_seed_index_set", "gnx_seed_find_batch", "gnx_seed_index_set_gen", "gnx_seed_find_batch_gen", "gnx_gsw_graph_create", "gnx_gsw_graph_free", "gnx_gsw_map_reads", "gnx_debug_occupy", "gnx_debug_counter", "gnx_reference_info",
            "gnx_score_batch", "gnx_score_batch_windows", "gnx_score_batch_by_offset", "gnx_score_batch_device",
-           "gnx_locate_batch", "gnx_locate_batch_windows", "gnx_locate_batch_by_offset"]
+           "gnx_locate_batch", "gnx_locate_batch_windows", "gnx_locate_batch_by_offset",
+           "gnx_affine_gap_chunk_score_batch", "gnx_multiple_affine_gap_score_batch"]
 
 
 class GnxCigar(ctypes.Structure):
@@ -88,6 +89,11 @@ def lib():
         L.gnx_multiple_affine_gap_batch.argtypes = [ctypes.POINTER(GnxParams), i64, i64, c_p, c_p, c_p, c_p, i64, c_p, c_p, c_p,
                                                     ctypes.POINTER(c_p), ctypes.POINTER(c_p)]
         L.gnx_multiple_affine_gap_batch.restype = ctypes.c_int
+        if hasattr(L, "gnx_affine_gap_chunk_score_batch"):  # (absent from older builds loaded through GNX_LIB_PATH for A/B runs)
+            L.gnx_affine_gap_chunk_score_batch.argtypes = [ctypes.POINTER(GnxParams), i64, i64, c_p, c_p, c_p, c_p, c_p]
+            L.gnx_affine_gap_chunk_score_batch.restype = ctypes.c_int
+            L.gnx_multiple_affine_gap_score_batch.argtypes = [ctypes.POINTER(GnxParams), i64, i64, c_p, c_p, c_p, c_p, i64, c_p, c_p, c_p]
+            L.gnx_multiple_affine_gap_score_batch.restype = ctypes.c_int
         L.gnx_gsw_extend_batch.argtypes = [ctypes.c_int, c_p, i64, i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                            ctypes.POINTER(c_p), ctypes.POINTER(c_p)]
         L.gnx_gsw_extend_batch.restype = ctypes.c_int
@@ -403,9 +409,7 @@ def locate_batch(params, targets, queries):
     return scores[:n], ends[:n]
 
 
-def affine_gap_chunk_batch(params, chunk_size, alphas, betas):
-    """align.AffineGapChunk over a batch of pairs.  Returns (scores, ops, off)."""
-    L = lib()
+def _chunk_pairs(alphas, betas):
     n = len(alphas)
     a_off = np.zeros(n + 1, dtype=np.int64)
     b_off = np.zeros(n + 1, dtype=np.int64)
@@ -414,7 +418,21 @@ def affine_gap_chunk_batch(params, chunk_size, alphas, betas):
         b_off[1:] = np.cumsum([len(b) for b in betas])
     a_cat = _u8(np.concatenate([_u8(a) for a in alphas] + [np.zeros(1, np.uint8)]))
     b_cat = _u8(np.concatenate([_u8(b) for b in betas] + [np.zeros(1, np.uint8)]))
-    scores = np.zeros(max(n, 1), dtype=np.int64)
+    return n, a_cat, a_off, b_cat, b_off, np.zeros(max(n, 1), dtype=np.int64)
+
+
+def affine_gap_chunk_score_batch(params, chunk_size, alphas, betas):
+    """The scores of affine_gap_chunk_batch alone (no CIGAR is built where the score sweep takes the call)."""
+    n, a_cat, a_off, b_cat, b_off, scores = _chunk_pairs(alphas, betas)
+    check(lib().gnx_affine_gap_chunk_score_batch(ctypes.byref(params), int(chunk_size), n, a_cat.ctypes.data, a_off.ctypes.data, b_cat.ctypes.data,
+                                                 b_off.ctypes.data, scores.ctypes.data))
+    return scores[:n]
+
+
+def affine_gap_chunk_batch(params, chunk_size, alphas, betas):
+    """align.AffineGapChunk over a batch of pairs.  Returns (scores, ops, off)."""
+    L = lib()
+    n, a_cat, a_off, b_cat, b_off, scores = _chunk_pairs(alphas, betas)
     ops_p, off_p = ctypes.c_void_p(), ctypes.c_void_p()
     check(L.gnx_affine_gap_chunk_batch(ctypes.byref(params), int(chunk_size), n, a_cat.ctypes.data, a_off.ctypes.data, b_cat.ctypes.data,
                                        b_off.ctypes.data, scores.ctypes.data, ctypes.byref(ops_p), ctypes.byref(off_p)))
@@ -422,10 +440,7 @@ def affine_gap_chunk_batch(params, chunk_size, alphas, betas):
     return scores[:n], ops, off
 
 
-def multiple_affine_gap_batch(params, chunk_size, groups, pairs):
-    """groups: list of 2-D uint8 arrays (nseq x len, alignment blocks); pairs: list of (a, b) group indices.
-    align.multipleAffineGap (chunk_size 1) / multipleAffineGapChunk for every pair.  Returns (scores, ops, off)."""
-    L = lib()
+def _group_pairs(groups, pairs):
     g = len(groups)
     blocks = [np.ascontiguousarray(x, dtype=np.uint8).reshape(x.shape[0], -1) for x in groups]
     g_off = np.zeros(g + 1, dtype=np.int64)
@@ -437,7 +452,22 @@ def multiple_affine_gap_batch(params, chunk_size, groups, pairs):
     n = len(pairs)
     pa = np.asarray([a for a, _ in pairs] + [0], dtype=np.int32)
     pb = np.asarray([b for _, b in pairs] + [0], dtype=np.int32)
-    scores = np.zeros(max(n, 1), dtype=np.int64)
+    return g, bases, g_off, g_nseq, g_len, n, pa, pb, np.zeros(max(n, 1), dtype=np.int64)
+
+
+def multiple_affine_gap_score_batch(params, chunk_size, groups, pairs):
+    """The scores of multiple_affine_gap_batch alone (same arguments; no CIGAR is built where the score sweep takes the call)."""
+    g, bases, g_off, g_nseq, g_len, n, pa, pb, scores = _group_pairs(groups, pairs)
+    check(lib().gnx_multiple_affine_gap_score_batch(ctypes.byref(params), int(chunk_size), g, bases.ctypes.data, g_off.ctypes.data, g_nseq.ctypes.data,
+                                                    g_len.ctypes.data, n, pa.ctypes.data, pb.ctypes.data, scores.ctypes.data))
+    return scores[:n]
+
+
+def multiple_affine_gap_batch(params, chunk_size, groups, pairs):
+    """groups: list of 2-D uint8 arrays (nseq x len, alignment blocks); pairs: list of (a, b) group indices.
+    align.multipleAffineGap (chunk_size 1) / multipleAffineGapChunk for every pair.  Returns (scores, ops, off)."""
+    L = lib()
+    g, bases, g_off, g_nseq, g_len, n, pa, pb, scores = _group_pairs(groups, pairs)
     ops_p, off_p = ctypes.c_void_p(), ctypes.c_void_p()
     check(L.gnx_multiple_affine_gap_batch(ctypes.byref(params), int(chunk_size), g, bases.ctypes.data, g_off.ctypes.data, g_nseq.ctypes.data,
                                           g_len.ctypes.data, n, pa.ctypes.data, pb.ctypes.data, scores.ctypes.data,

@@ -15,6 +15,7 @@ Every alignment call goes through the C ABI into the HIP kernels (gonomics_amd/_
 pair is a batch of one.  Go panics map to exceptions: base >= 5 -> IndexError (index out of range),
 empty input to a low-memory function (the Go code never terminates) -> ValueError.
 """
+import os
 from collections import namedtuple
 
 import numpy as np
@@ -249,32 +250,94 @@ def mergeMultipleAlignments(alpha, beta, route):
     return [Fasta(f.Name, rows[k]) for k, f in enumerate(list(alpha) + list(beta))]
 
 
-def _all_seq(records, scoreMatrix, gapOpen, gapExtend, chunkSize, batch_fn):
+def AffineGapChunkScore(alpha, beta, scores, gapOpen, gapExtend, chunkSize):
+    """The score AffineGapChunk returns, without its route."""
+    try:
+        sc = _lib.affine_gap_chunk_score_batch(_lib.make_params(_lib.GNX_AFFINE_GAP_HIGHMEM, scores, gapOpen, gapExtend), chunkSize, [alpha], [beta])
+    except _lib.GnxError as e:
+        _raise(e)
+    return int(sc[0])
+
+
+def multipleAffineGapScoreBatch(groups, pairs, scores, gapOpen, gapExtend, chunkSize=1):
+    """The scores multipleAffineGapBatch returns for the same arguments, as a list of ints, without the routes."""
+    try:
+        sc = _lib.multiple_affine_gap_score_batch(_lib.make_params(_lib.GNX_AFFINE_GAP_HIGHMEM, scores, gapOpen, gapExtend), chunkSize,
+                                                  _groups_to_blocks(groups), pairs)
+    except _lib.GnxError as e:
+        _raise(e)
+    return [int(x) for x in sc]
+
+
+def _is_symmetric(scoreMatrix):
+    m = [list(row) for row in scoreMatrix]
+    return all(m[a][b] == m[b][a] for a in range(len(m)) for b in range(len(m)))
+
+
+def _all_seq(records, scoreMatrix, gapOpen, gapExtend, chunkSize, batch_fn=None, score_fn=None):
     # multiAlign.go:27-78: progressive alignment, merging the best-scoring pair of groups each round
-    # (first strict maximum in x<y order, nearestGroups :27-41); one batched call per round.
+    # (first strict maximum in x<y order, nearestGroups :27-41).
+    # Score first: a round scores the pairs it has no score for in one score_fn call, and only its winner goes through batch_fn for the
+    # route.  Scores are remembered under (id of the x group, id of the y group); a merged group gets a fresh id.  groups[y] = groups[-1]
+    # moves the last group forward, so later rounds meet pairs with their sides exchanged: score(A, B, S) == score(B, A, S^T), so an
+    # exchanged pair reuses its score when the matrix equals its transpose (all four matrices of align.go do).
+    # GNX_N1_SCORE_FIRST (read per call): 1 = score first; 0 or unset = every pair with its route, every round, through batch_fn alone.
+    # That is the default because it measured faster on cmd/faChunkAlign's workload (8 x 30 kb, chunk 3: 0.072 s against 0.082 s,
+    # DESIGN.md 4.17): a call of a few long pairs is bound by the latency of one pair, where the stored-matrix kernel is the quicker one.
+    batch_fn = batch_fn or multipleAffineGapBatch
+    score_fn = score_fn or multipleAffineGapScoreBatch
+    score_first = os.environ.get("GNX_N1_SCORE_FIRST", "0") not in ("0", "")
+    symmetric = _is_symmetric(scoreMatrix)
     groups = [[r] for r in records]
+    ids = list(range(len(groups)))
+    next_id = len(groups)
+    known = {}
     while len(groups) > 1:
         pairs = [(x, y) for x in range(len(groups) - 1) for y in range(x + 1, len(groups))]
-        res = batch_fn(groups, pairs, scoreMatrix, gapOpen, gapExtend, chunkSize)
-        best, best_score = None, None
-        for (x, y), (score, route) in zip(pairs, res):
-            if best_score is None or score > best_score:
-                best, best_score = (x, y, route), score
-        x, y, route = best
+        if score_first:
+            def remembered(x, y):
+                s = known.get((ids[x], ids[y]))
+                return known.get((ids[y], ids[x])) if s is None and symmetric else s
+            todo = [(x, y) for x, y in pairs if remembered(x, y) is None]
+            if todo:
+                for (x, y), s in zip(todo, score_fn(groups, todo, scoreMatrix, gapOpen, gapExtend, chunkSize)):
+                    known[(ids[x], ids[y])] = int(s)
+            best, best_score = None, None
+            for x, y in pairs:
+                score = remembered(x, y)
+                if best_score is None or score > best_score:
+                    best, best_score = (x, y), score
+            x, y = best
+            (score, route), = batch_fn(groups, [(x, y)], scoreMatrix, gapOpen, gapExtend, chunkSize)
+            if score != best_score:
+                raise RuntimeError("progressive alignment: the alignment of groups %d and %d scores %d, their score call gave %d" % (x, y, score, best_score))
+        else:
+            res = batch_fn(groups, pairs, scoreMatrix, gapOpen, gapExtend, chunkSize)
+            best, best_score = None, None
+            for (x, y), (score, route) in zip(pairs, res):
+                if best_score is None or score > best_score:
+                    best, best_score = (x, y, route), score
+            x, y, route = best
         groups[x] = mergeMultipleAlignments(groups[x], groups[y], route)
+        ids[x] = next_id
+        next_id += 1
         groups[y] = groups[-1]
+        ids[y] = ids[-1]
         groups = groups[:-1]
+        ids = ids[:-1]
+        live = set(ids)
+        known = {k: v for k, v in known.items() if k[0] in live and k[1] in live}
     return groups[0]
 
 
 def AllSeqAffine(records, scoreMatrix, gapOpen, gapExtend):
     """align.AllSeqAffine (/root/reference/align/multiAlign.go:59-66)."""
-    return _all_seq(records, scoreMatrix, gapOpen, gapExtend, 1, multipleAffineGapBatch)
+    return _all_seq(records, scoreMatrix, gapOpen, gapExtend, 1)
 
 
 def AllSeqAffineChunk(records, scoreMatrix, gapOpen, gapExtend, chunkSize):
     """align.AllSeqAffineChunk (/root/reference/align/multiAlign.go:70-78)."""
-    return _all_seq(records, scoreMatrix, gapOpen, gapExtend, chunkSize, multipleAffineGapBatch)
+    return _all_seq(records, scoreMatrix, gapOpen, gapExtend, chunkSize)
 
 
 class TargetQueryPair:

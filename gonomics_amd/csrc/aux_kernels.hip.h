@@ -14,9 +14,19 @@ namespace {
 struct GroupDesc { int64_t off; int32_t nseq; int32_t len; };
 struct ScorePair { int64_t a_off, b_off; int32_t a_nseq, b_nseq, a_len, b_len; int32_t nc, mc; int64_t s_off, s_pitch; int64_t pa_off, pb_off; }; // pa_off / pb_off: column profiles of the two groups (score_profiles_kernel), in entries
 
+// the SWP store of four rows of a column (see score_matrix_kernel): rows >= nc are not written (the next column's padding follows),
+// the thread of row 0 also writes the column's padding
+__device__ __forceinline__ void sweep_store4(short *__restrict__ dst, const int (&out)[4], int i0, int nc) {
+#pragma unroll
+    for (int r = 0; r < 4; r++) if (i0 + r < nc) dst[r] = (short)(out[r] >> 2);
+    if (i0 == 0) { const int pad = (10 - nc % 10) % 10; for (int k = 1; k <= pad; k++) dst[-k] = (short)-32768; }
+}
+
 // S16: every 4*score fits int16 (host check: 4 * chunk * max|score| <= 32767) -- the matrix is stored as int16, which halves the
 // HBM traffic of the SCORED fill (it reads one entry per cell and is bandwidth-bound with 4-byte entries)
-template <bool S16>
+// SWP: the layout of the score-only sweep (n1_sweep.hip.h): plain int16 entries s - 2e (bias4 = -8e), a column = [pad entries of
+// -32768][rows 0 .. nc - 1] with pad = (10 - nc % 10) % 10; s_off is the entry of row 0 of column 0 and s_pitch = nc + pad (no slack)
+template <bool S16, bool SWP = false>
 __global__ __launch_bounds__(256) void score_matrix_kernel(const ScorePair *__restrict__ sp, const uint8_t *__restrict__ bases, KParams kp, int chunk,
                                                            int groups, int bias4, int *__restrict__ smat, int *__restrict__ err) {
     // bias4 = -2 * 4 * gapExtend * chunk when the fill runs on rebased keys (fill_affine_kernel, HFORM), else 0
@@ -63,7 +73,8 @@ __global__ __launch_bounds__(256) void score_matrix_kernel(const ScorePair *__re
                 out[r] = (int)(4 * total) + bias4;
             }
             const int64_t at = q.s_off + (int64_t)j * q.s_pitch + i0; // multiple of 4: s_off and s_pitch are multiples of 160
-            if (S16) *reinterpret_cast<uint2 *>(reinterpret_cast<short *>(smat) + at) = make_uint2((unsigned)(out[0] & 0xffff) | ((unsigned)out[1] << 16), (unsigned)(out[2] & 0xffff) | ((unsigned)out[3] << 16));
+            if constexpr (SWP) sweep_store4(reinterpret_cast<short *>(smat) + at, out, i0, q.nc);
+            else if (S16) *reinterpret_cast<uint2 *>(reinterpret_cast<short *>(smat) + at) = make_uint2((unsigned)(out[0] & 0xffff) | ((unsigned)out[1] << 16), (unsigned)(out[2] & 0xffff) | ((unsigned)out[3] << 16));
             else *reinterpret_cast<int4 *>(smat + at) = make_int4(out[0], out[1], out[2], out[3]);
         }
     }
@@ -73,7 +84,7 @@ __global__ __launch_bounds__(256) void score_matrix_kernel(const ScorePair *__re
 // what the callers use: a thread keeps the bases of its four rows in registers and walks the columns (the general kernel above
 // re-reads them, with 64-bit index arithmetic, for every cell: 6 ms for 4096 pairs of 160 x 3000 chunks, more than the fill).
 // block = 64 x 4 threads: x = groups of four rows, y = 4 columns; a block walks the columns blockIdx.x * 4 + y, + 4 * gridDim.x, ...
-template <bool S16, int CH>
+template <bool S16, int CH, bool SWP = false>
 __global__ __launch_bounds__(256) void score_matrix_pairs_kernel(const ScorePair *__restrict__ sp, const uint8_t *__restrict__ bases, KParams kp, int bias4,
                                                                  int *__restrict__ smat, int *__restrict__ err) {
     __shared__ int sc[32];
@@ -104,7 +115,8 @@ __global__ __launch_bounds__(256) void score_matrix_pairs_kernel(const ScorePair
                 for (int r = 0; r < 4; r++) out[r] += sc[a5[r][k] + b];
             }
             const int64_t at = q.s_off + (int64_t)j * q.s_pitch + i0;
-            if (S16) *reinterpret_cast<uint2 *>(reinterpret_cast<short *>(smat) + at) = make_uint2((unsigned)(out[0] & 0xffff) | ((unsigned)out[1] << 16), (unsigned)(out[2] & 0xffff) | ((unsigned)out[3] << 16));
+            if constexpr (SWP) sweep_store4(reinterpret_cast<short *>(smat) + at, out, i0, q.nc);
+            else if (S16) *reinterpret_cast<uint2 *>(reinterpret_cast<short *>(smat) + at) = make_uint2((unsigned)(out[0] & 0xffff) | ((unsigned)out[1] << 16), (unsigned)(out[2] & 0xffff) | ((unsigned)out[3] << 16));
             else *reinterpret_cast<int4 *>(smat + at) = make_int4(out[0], out[1], out[2], out[3]);
         }
     }
@@ -156,7 +168,7 @@ __global__ __launch_bounds__(256) void score_profiles_kernel(const ScorePair *__
     }
 }
 // block = 64 x 4 threads: x = groups of four chunk rows (their column profiles stay in registers), y = 4 chunk columns; see score_matrix_pairs_kernel
-template <bool S16, int CH>
+template <bool S16, int CH, bool SWP = false>
 __global__ __launch_bounds__(256) void score_matrix_groups_kernel(const ScorePair *__restrict__ sp, KParams kp, int bias4, const ColProfA *__restrict__ pa,
                                                                   const ColProfB *__restrict__ pb, int *__restrict__ smat, int *__restrict__ err) {
     const ScorePair q = sp[blockIdx.y];
@@ -197,7 +209,8 @@ __global__ __launch_bounds__(256) void score_matrix_groups_kernel(const ScorePai
 #pragma unroll
             for (int r = 0; r < 4; r++) out[r] = 4 * out[r] + bias4;
             const int64_t at = q.s_off + (int64_t)j * q.s_pitch + i0;
-            if (S16) *reinterpret_cast<uint2 *>(reinterpret_cast<short *>(smat) + at) = make_uint2((unsigned)(out[0] & 0xffff) | ((unsigned)out[1] << 16), (unsigned)(out[2] & 0xffff) | ((unsigned)out[3] << 16));
+            if constexpr (SWP) sweep_store4(reinterpret_cast<short *>(smat) + at, out, i0, q.nc);
+            else if (S16) *reinterpret_cast<uint2 *>(reinterpret_cast<short *>(smat) + at) = make_uint2((unsigned)(out[0] & 0xffff) | ((unsigned)out[1] << 16), (unsigned)(out[2] & 0xffff) | ((unsigned)out[3] << 16));
             else *reinterpret_cast<int4 *>(smat + at) = make_int4(out[0], out[1], out[2], out[3]);
         }
     }

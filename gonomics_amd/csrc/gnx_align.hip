@@ -51,6 +51,7 @@
 #include "lat_wide.hip.h"
 #include "seed_kernels.hip.h"
 #include "score_sweep.hip.h"
+#include "n1_sweep.hip.h"
 
 namespace {
 
@@ -2106,14 +2107,128 @@ int run_device(const gnx_params *prm, int64_t n_pairs,
     return GNX_OK;
 }
 
+// ---- score-only chunk / multiple-alignment calls: the sweep with explicit cell scores (n1_sweep.hip.h) -------
+// What the sweep takes (prm2 = the scaled parameters the DP sees: gapExtend * chunk, scores * chunk): gapOpen <= 0, both sides of every
+// pair non-empty, the shorter side <= SS_MAX_LEVELS * 160 chunk cells, the rebased keys inside int32 ((nc + mc + 2) * 2 * max|penalty|
+// < 2^30), every entry s - 2e (a chunk cell is a sum of `chunk` scores or of averages of scores: inside chunk * [min, max] of the table)
+// and gapOpen inside +-16 000.  GNX_SCORE_SWEEP=0: never (A/B).
+bool n1_sweep_fits(const gnx_params *prm2, int64_t n_pairs, const std::vector<ScorePair> &sp) {
+    if (n_pairs <= 0 || n_pairs > 0x7ffffff0) return false;
+    if (prm2->gap_open > 0 || prm2->gap_open < -16000) return false;
+    if (const char *e = getenv("GNX_SCORE_SWEEP")) if (e[0] == '0') return false;
+    for (int x = 0; x < 25; x++) {
+        const int64_t v = prm2->scores[x] - 2 * prm2->gap_extend;
+        if (v < -16000 || v > 16000) return false;
+    }
+    const int64_t maxpen = std::max<int64_t>(max_abs_pen(prm2, true), 1);
+    for (int64_t p = 0; p < n_pairs; p++) {
+        const int64_t n = sp[(size_t)p].nc, m = sp[(size_t)p].mc;
+        if (n < 1 || m < 1) return false;
+        if (std::min(n, m) > (int64_t)SS_MAX_LEVELS * G * SS_RR || (n + m + 2) * 2 * maxpen >= ((int64_t)1 << 30)) return false;
+    }
+    return true;
+}
+
+// plans: n (rows, <= m), m, src, mat_off and pitch of every pair, in any order.  Sorted by (levels, columns), cut into quads, one
+// launch per number of levels (run_score_sweep).  Writes d_score[src] only; fast_path 9.
+int run_n1_sweep(const gnx_params *prm2, std::vector<N1Plan> plans, const short *d_mat, int64_t *d_score, hipStream_t stream) {
+    Ctx &c = g_ctx;
+    int rc;
+    constexpr int HB = G * SS_RR;
+    const int64_t n_pairs = (int64_t)plans.size();
+    int64_t cells = 0;
+    for (N1Plan &pl : plans) { pl.levels = (int32_t)((pl.n + HB - 1) / HB); cells += (int64_t)pl.n * pl.m; }
+    std::sort(plans.begin(), plans.end(), [](const N1Plan &x, const N1Plan &y) { return x.levels != y.levels ? x.levels < y.levels : (x.m != y.m ? x.m < y.m : x.src < y.src); });
+    // quads: four consecutive pairs, all with the row blocks of the tallest (the last) of them; the last quad is filled with empty slots
+    const int64_t n_quads = (n_pairs + 3) / 4;
+    N1Plan empty = {}; empty.levels = 1;
+    plans.resize((size_t)n_quads * 4, empty);
+    struct Group { int64_t q0, nq; int S; };
+    std::vector<Group> groups;
+    int64_t rb_total = 0, prog_max = 0;
+    for (int64_t q = 0; q < n_quads; q++) {
+        int S = 1;
+        for (int k = 0; k < 4; k++) S = std::max(S, (int)plans[(size_t)(q * 4 + k)].levels);
+        for (int k = 0; k < 4; k++) {
+            N1Plan &pl = plans[(size_t)(q * 4 + k)];
+            pl.levels = S;
+            if (S > 1 && pl.n > 0) { pl.rowbuf_off = rb_total; rb_total += 2 * ((int64_t)pl.m + 1); }
+        }
+        if (groups.empty() || groups.back().S != S) groups.push_back(Group{q, 0, S});
+        groups.back().nq++;
+    }
+    for (const Group &gq : groups) if (gq.S > 1) prog_max = std::max<int64_t>(prog_max, (int64_t)gq.S * gq.nq * 2 + 2);
+    if ((rc = c.ss_plans.ensure(plans.size() * sizeof(N1Plan)))) return rc;
+    if ((rc = c.ss_err.ensure(64))) return rc;
+    if (rb_total && (rc = c.ss_rowbuf.ensure((size_t)rb_total * sizeof(int2)))) return rc;
+    if (prog_max && (rc = c.ss_prog.ensure((size_t)prog_max * 4))) return rc;
+    const N1Plan *dpl = reinterpret_cast<const N1Plan *>(c.ss_plans.p);
+    int *d_err = reinterpret_cast<int *>(c.ss_err.p);
+    int2 *rb = reinterpret_cast<int2 *>(c.ss_rowbuf.p);
+    int *prog = reinterpret_cast<int *>(c.ss_prog.p);
+    HIPCHK(hipMemcpyAsync(c.ss_plans.p, plans.data(), plans.size() * sizeof(N1Plan), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemsetAsync(d_err, 0, 64, stream));
+    const int o = (int)prm2->gap_open, e = (int)prm2->gap_extend;
+    int64_t launches = 0;
+    auto sweep = [&](bool piped) -> int {
+        for (const Group &gq : groups) {
+            const N1Plan *gp = dpl + gq.q0 * 4;
+            const int W = (int)gq.nq, S = gq.S;
+            if (S == 1) {
+                hipLaunchKernelGGL(n1_sweep_kernel, dim3((unsigned)W), dim3(64), 0, stream, gp, d_mat, o, e, d_score, d_err);
+                launches++;
+            } else {
+                N1LevelsArgs la{gp, d_mat, o, e, d_score, d_err, rb, S, W, 0, 1, prog};
+                if (piped) {
+                    HIPCHK(hipMemsetAsync(prog, 0, ((size_t)S * W * 2 + 2) * 4, stream)); // progress words, claim words, test switch
+                    if ((rc = claim_test_switch(prog + (size_t)S * W * 2, stream))) return rc;
+                    hipLaunchKernelGGL(n1_sweep_levels_kernel, dim3((unsigned)((int64_t)S * W)), dim3(64), 0, stream, la);
+                    launches++;
+                } else {
+                    la.piped = 0;
+                    for (int level = 0; level < S; level++) {
+                        la.level0 = level;
+                        hipLaunchKernelGGL(n1_sweep_levels_kernel, dim3((unsigned)W), dim3(64), 0, stream, la);
+                        launches++;
+                    }
+                }
+            }
+            HIPCHK(hipGetLastError());
+        }
+        return GNX_OK;
+    };
+    HIPCHK(hipEventRecord(c.ev[0], stream));
+    if ((rc = sweep(!no_pipe()))) return rc;
+    HIPCHK(hipEventRecord(c.ev[1], stream));
+    int ef = 0;
+    HIPCHK(hipMemcpyAsync(&ef, d_err, 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (ef & 16) { // a level that waited 5 s for the one above it (a bug trap): sweep again, level by level
+        if (getenv("GNX_DEBUG")) fprintf(stderr, "[gnx score] a row block timed out waiting for the one above it -> one launch per level\n");
+        HIPCHK(hipMemsetAsync(d_err, 0, 64, stream));
+        if ((rc = sweep(false))) return rc;
+        HIPCHK(hipEventRecord(c.ev[1], stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+    if (getenv("GNX_DEBUG")) fprintf(stderr, "[gnx score] scored sweep: %lld pairs, %d group(s), %lld launch(es), %.3f ms\n", (long long)n_pairs, (int)groups.size(), (long long)launches, ms);
+    c.timing = gnx_timing{};
+    c.timing.fill_ms = ms; c.timing.total_ms = ms; c.timing.cells = cells; c.timing.n_launches = 1; c.timing.trace_bytes = 0;
+    c.timing.dominant_ms = ms; c.timing.dominant_launches = launches; c.timing.fast_path = 9;
+    return GNX_OK;
+}
+
 // N1 host flow: bases (pairwise sequences or alignment blocks) -> score matrices on the device -> SCORED fill + the
 // ordinary highMem traceback -> run lengths times chunk size.  `sp` describes the pairs (offsets into `bases`).
 int run_host_scored(const gnx_params *prm, int64_t chunk, bool groups, int64_t n_pairs, std::vector<ScorePair> &sp,
                     const uint8_t *bases, int64_t bases_len, int64_t *out_score, gnx_cigar **out_ops, int64_t **out_ops_off,
-                    const uint8_t *bases2 = nullptr, int64_t bases2_len = 0) {
+                    const uint8_t *bases2 = nullptr, int64_t bases2_len = 0, bool score_only = false) {
     // bases2: a second host buffer that follows `bases` on the device (the pairwise entry point: alpha_cat, then beta_cat -- no host copy)
+    // score_only (gnx_*_score_batch): out_score alone.  The same validation, errors and score matrices; the DP is the score sweep of
+    // n1_sweep.hip.h (fast_path 9) when n1_sweep_fits() says so, else the route below with the CIGAR left on the device.
     Ctx &c = g_ctx;
-    if (!prm || !out_score || !out_ops || !out_ops_off || n_pairs < 0 || chunk < 1 || chunk > (1 << 20)) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (!prm || !out_score || (!score_only && (!out_ops || !out_ops_off)) || n_pairs < 0 || chunk < 1 || chunk > (1 << 20)) { set_err("bad argument%s", ""); return GNX_EINVAL; }
     if (prm->mode != GNX_AFFINE_GAP_HIGHMEM) { set_err("the chunk / multiple-alignment variants have AffineGap_highMem semantics (mode %s%lld)", "", (long long)GNX_AFFINE_GAP_HIGHMEM); return GNX_EINVAL; }
     KParams kp0; TbParams tp0; bool aff, loc, low;
     int rc = check_params(prm, kp0, tp0, aff, loc, low);
@@ -2140,7 +2255,26 @@ int run_host_scored(const gnx_params *prm, int64_t chunk, bool groups, int64_t n
     t_scored_wide = wide_sc;
     struct ScoredWideReset { ~ScoredWideReset() { t_scored_wide = false; } } scored_wide_reset;
     const bool hform_sc = !wide_sc && prm2.gap_open <= 0 && !getenv("GNX_NO_HFORM");
-    const int64_t bias4 = hform_sc ? -8 * prm2.gap_extend : 0;
+    const bool sweep = score_only && !wide_sc && n1_sweep_fits(&prm2, n_pairs, sp);
+    const int64_t bias4 = (hform_sc || sweep) ? -8 * prm2.gap_extend : 0;
+    // the sweep holds the shorter side in lanes: those pairs swap their two sides (and meet the transposed 5 x 5 table), descriptors
+    // [0, n_straight) keep theirs; the matrix of a pair is then written the way the sweep reads it, never across its pitch
+    std::vector<N1Plan> n1_plans;
+    int64_t n_straight = n_pairs;
+    if (sweep) {
+        std::vector<ScorePair> sw;
+        std::vector<int64_t> src_a, src_b;
+        n_straight = 0;
+        for (int64_t p = 0; p < n_pairs; p++) {
+            ScorePair q = sp[(size_t)p];
+            if (q.nc > q.mc) { std::swap(q.a_off, q.b_off); std::swap(q.a_nseq, q.b_nseq); std::swap(q.a_len, q.b_len); std::swap(q.nc, q.mc); sw.push_back(q); src_b.push_back(p); }
+            else { sp[(size_t)n_straight++] = q; src_a.push_back(p); }
+        }
+        std::copy(sw.begin(), sw.end(), sp.begin() + n_straight);
+        src_a.insert(src_a.end(), src_b.begin(), src_b.end());
+        n1_plans.resize((size_t)n_pairs);
+        for (int64_t p = 0; p < n_pairs; p++) { N1Plan &pl = n1_plans[(size_t)p]; pl = N1Plan{}; pl.n = sp[(size_t)p].nc; pl.m = sp[(size_t)p].mc; pl.src = (int32_t)src_a[(size_t)p]; }
+    }
     const bool s16 = !wide_sc && 4 * chunk * smax + llabs((long long)bias4) <= 32767;
     std::vector<int64_t> hn((size_t)n_pairs), hm((size_t)n_pairs), hso((size_t)n_pairs);
     int64_t stot = 0, worst = 0, maxcols = 1, maxrows = 1, prof_a = 0, prof_b = 0, max_nseq = 1;
@@ -2149,6 +2283,12 @@ int run_host_scored(const gnx_params *prm, int64_t chunk, bool groups, int64_t n
         maxrows = std::max<int64_t>(maxrows, q.nc);
         const int64_t strips = std::max<int64_t>((q.nc + H - 1) / H, 1);
         q.s_pitch = strips * H; q.s_off = stot;
+        if (sweep) { // int16 entries; a column = [pad][rows], rows right-aligned to a lane of SS_RR (n1_sweep.hip.h)
+            const int64_t pad = (SS_RR - q.nc % SS_RR) % SS_RR;
+            N1Plan &pl = n1_plans[(size_t)p];
+            pl.pitch = (int32_t)(q.nc + pad); pl.mat_off = N1_PADBLOCK + stot;
+            q.s_pitch = pl.pitch; q.s_off = pl.mat_off + pad;
+        }
         q.pa_off = prof_a; q.pb_off = prof_b; prof_a += q.a_len; prof_b += q.b_len; // (groups: column profiles, score_profiles_kernel)
         max_nseq = std::max<int64_t>(max_nseq, std::max(q.a_nseq, q.b_nseq));
         stot += (int64_t)q.mc * q.s_pitch;
@@ -2158,7 +2298,7 @@ int run_host_scored(const gnx_params *prm, int64_t chunk, bool groups, int64_t n
     }
     if ((rc = c.in_a.ensure((size_t)(bases_len + bases2_len) + 16))) return rc;
     if ((rc = c.sc_pairs.ensure((size_t)std::max<int64_t>(n_pairs, 1) * sizeof(ScorePair)))) return rc;
-    if ((rc = c.sc_mat.ensure((size_t)std::max<int64_t>(stot, 1) * 4 + 4096))) return rc; // (+ slack: the latency geometry's last strip reads up to 127 padding rows past a column)
+    if ((rc = c.sc_mat.ensure(sweep ? (size_t)(stot + N1_PADBLOCK) * 2 + 64 : (size_t)std::max<int64_t>(stot, 1) * 4 + 4096))) return rc; // (+ slack: the latency geometry's last strip reads up to 127 padding rows past a column)
     if ((rc = c.sc_err.ensure(16))) return rc;
     const size_t np = (size_t)std::max<int64_t>(n_pairs, 1);
     if ((rc = c.out_score.ensure(np * 8))) return rc;
@@ -2170,7 +2310,7 @@ int run_host_scored(const gnx_params *prm, int64_t chunk, bool groups, int64_t n
     // A sub-batch must still fill the GPU on its own (4 pairs per wave, one wave per group of strips: 8192 pairs = 2048 waves) -- 4096
     // pairs cut in four ran 7.9 instead of 5.1 ms: each quarter takes as long as the whole.  GNX_SCORED_SUB=k forces k sub-batches (tests).
     int K = 1;
-    if (!groups && bases2 && n_pairs >= 2) {
+    if (!groups && bases2 && n_pairs >= 2 && !sweep) {
         if (bases_len + bases2_len >= ((int64_t)8 << 20)) K = (int)std::min<int64_t>(4, n_pairs / 8192);
         if (const char *e = getenv("GNX_SCORED_SUB")) K = atoi(e);
         K = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(K, 16), n_pairs));
@@ -2216,7 +2356,7 @@ int run_host_scored(const gnx_params *prm, int64_t chunk, bool groups, int64_t n
         uploader = std::thread([&, dev]() { if (hipSetDevice(dev) != hipSuccess) { up_rc.store(1); uploaded.store(K, std::memory_order_release); return; } upload(); });
     } else upload();
     int64_t cap = std::max<int64_t>(std::min<int64_t>(worst, std::max<int64_t>((int64_t)1 << 20, 64 * n_pairs)), 1);
-    if ((rc = c.out_ops.ensure((size_t)cap * sizeof(gnx_cigar)))) return rc;
+    if (!sweep && (rc = c.out_ops.ensure((size_t)cap * sizeof(gnx_cigar)))) return rc;
     int64_t total = 0;
     gnx_timing tsum = {};
     bool redo = false; // a sub-batch did not fit the CIGAR buffer: once everything is uploaded, the whole batch runs again as one
@@ -2230,7 +2370,12 @@ int run_host_scored(const gnx_params *prm, int64_t chunk, bool groups, int64_t n
         if ((rc = c.sc_prof_a.ensure((size_t)std::max<int64_t>(prof_a, 1) * sizeof(ColProfA)))) return rc;
         if ((rc = c.sc_prof_b.ensure((size_t)std::max<int64_t>(prof_b, 1) * sizeof(ColProfB)))) return rc;
     }
-    auto score_matrices = [&](int64_t p0, int64_t p1) {
+    KParams kpT = kp0; // the swapped pairs of the sweep: the transposed table
+    for (int x = 0; x < 25; x++) kpT.sc4[x] = kp0.sc4[(x % 5) * 5 + x / 5];
+    const KParams &kp_call = kp0;
+    auto score_matrices = [&](int64_t p0, int64_t p1, const KParams *kp_sweep = nullptr) { // kp_sweep: the sweep's layout (SWP) with that table
+        const bool swp = kp_sweep != nullptr;
+        const KParams &kp0 = swp ? *kp_sweep : kp_call;
         for (int64_t b = p0; b < p1; b += 32768) {
             const unsigned ny = (unsigned)std::min<int64_t>(32768, p1 - b);
             const unsigned nx = (unsigned)std::min<int64_t>((maxcols + 3) / 4, 1024);
@@ -2242,20 +2387,26 @@ int run_host_scored(const gnx_params *prm, int64_t chunk, bool groups, int64_t n
                                    reinterpret_cast<ColProfA *>(c.sc_prof_a.p), reinterpret_cast<ColProfB *>(c.sc_prof_b.p));
                 const dim3 grid((unsigned)std::min<int64_t>((maxcols + 63) / 64, 1024), ny), blk(64, 4);
 #define GNX_SMG(S, C) hipLaunchKernelGGL((score_matrix_groups_kernel<S, C>), grid, blk, 0, st, spd, kp0, (int)bias4, dpa, dpb, sm, se)
-                if (s16) { if (chunk == 1) GNX_SMG(true, 1); else if (chunk == 2) GNX_SMG(true, 2); else if (chunk == 3) GNX_SMG(true, 3); else GNX_SMG(true, 4); }
+#define GNX_SMGW(C) hipLaunchKernelGGL((score_matrix_groups_kernel<true, C, true>), grid, blk, 0, st, spd, kp0, (int)bias4, dpa, dpb, sm, se)
+                if (swp) { if (chunk == 1) GNX_SMGW(1); else if (chunk == 2) GNX_SMGW(2); else if (chunk == 3) GNX_SMGW(3); else GNX_SMGW(4); }
+                else if (s16) { if (chunk == 1) GNX_SMG(true, 1); else if (chunk == 2) GNX_SMG(true, 2); else if (chunk == 3) GNX_SMG(true, 3); else GNX_SMG(true, 4); }
                 else { if (chunk == 1) GNX_SMG(false, 1); else if (chunk == 2) GNX_SMG(false, 2); else if (chunk == 3) GNX_SMG(false, 3); else GNX_SMG(false, 4); }
 #undef GNX_SMG
+#undef GNX_SMGW
                 continue;
             }
             if (!groups && chunk <= 4 && maxrows * chunk < ((int64_t)1 << 30) && maxcols * chunk < ((int64_t)1 << 30) && !getenv("GNX_SCORE_GENERIC")) {
                 // a block walks ~16 column quads, so that the rows' bases it keeps in registers are loaded once per 64 columns
                 const dim3 grid((unsigned)std::min<int64_t>((maxcols + 63) / 64, 1024), ny), blk(64, 4);
 #define GNX_SMP(S, C) hipLaunchKernelGGL((score_matrix_pairs_kernel<S, C>), grid, blk, 0, st, spd, bd, kp0, (int)bias4, sm, se)
-                if (s16) { if (chunk == 1) GNX_SMP(true, 1); else if (chunk == 2) GNX_SMP(true, 2); else if (chunk == 3) GNX_SMP(true, 3); else GNX_SMP(true, 4); }
+#define GNX_SMPW(C) hipLaunchKernelGGL((score_matrix_pairs_kernel<true, C, true>), grid, blk, 0, st, spd, bd, kp0, (int)bias4, sm, se)
+                if (swp) { if (chunk == 1) GNX_SMPW(1); else if (chunk == 2) GNX_SMPW(2); else if (chunk == 3) GNX_SMPW(3); else GNX_SMPW(4); }
+                else if (s16) { if (chunk == 1) GNX_SMP(true, 1); else if (chunk == 2) GNX_SMP(true, 2); else if (chunk == 3) GNX_SMP(true, 3); else GNX_SMP(true, 4); }
                 else { if (chunk == 1) GNX_SMP(false, 1); else if (chunk == 2) GNX_SMP(false, 2); else if (chunk == 3) GNX_SMP(false, 3); else GNX_SMP(false, 4); }
 #undef GNX_SMP
+#undef GNX_SMPW
             } else {
-                auto ksm = s16 ? score_matrix_kernel<true> : score_matrix_kernel<false>;
+                auto ksm = swp ? score_matrix_kernel<true, true> : s16 ? score_matrix_kernel<true> : score_matrix_kernel<false>;
                 hipLaunchKernelGGL(ksm, dim3(nx, ny), dim3(64, 4), 0, st, spd, bd, kp0, (int)chunk, groups ? 1 : 0, (int)bias4, sm, se);
             }
         }
@@ -2266,7 +2417,11 @@ int run_host_scored(const gnx_params *prm, int64_t chunk, bool groups, int64_t n
         if (up_rc.load()) { set_err("upload of the bases failed%s", ""); return GNX_EDEVICE; }
         HIPCHK(hipStreamWaitEvent(st, evs[(size_t)k], 0));
         const int64_t p0 = kb[(size_t)k], p1 = kb[(size_t)k + 1], cnt = p1 - p0;
-        score_matrices(p0, p1);
+        if (sweep) { // (K == 1) the pad block, then the pairs that kept their sides and the swapped ones
+            HIPCHK(hipMemsetD16Async((hipDeviceptr_t)c.sc_mat.p, (unsigned short)0x8000, N1_PADBLOCK, st));
+            if (n_straight > 0) score_matrices(0, n_straight, &kp0);
+            if (n_straight < n_pairs) score_matrices(n_straight, n_pairs, &kpT);
+        } else score_matrices(p0, p1);
         HIPCHK(hipGetLastError());
         if (K == 1) { // one batch: errors of the score kernels are reported before the DP runs (sub-batches: after it; bad bases were read as 'A')
             int f[4] = {0, 0, 0, 0};
@@ -2276,6 +2431,14 @@ int run_host_scored(const gnx_params *prm, int64_t chunk, bool groups, int64_t n
             if (f[0] & 16) { set_err("scoreColumnMatch over gap-only columns: the reference panics (integer divide by zero)%s", ""); return GNX_EDIVZERO; }
         }
         if (k == 0) t_scores = ms_since(t_begin);
+        if (sweep) { // errors of the score kernels have been reported above: the DP of the score-only route
+            if ((rc = run_n1_sweep(&prm2, n1_plans, reinterpret_cast<const short *>(c.sc_mat.p), (int64_t *)c.out_score.p, st))) return rc;
+            HIPCHK(hipMemcpyAsync(out_score, c.out_score.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            if (dbg) fprintf(stderr, "[gnx] scored batch of %lld pairs, scores only: upload + score matrices %.3f ms, sweep %.3f ms on the device, results on the host at %.3f ms\n",
+                             (long long)n_pairs, t_scores, c.timing.fill_ms, ms_since(t_begin));
+            return GNX_OK;
+        }
         if (redo || cnt == 0) continue;
         int64_t tot = 0;
         rc = run_device(&prm2, cnt, nullptr, nullptr, nullptr, nullptr, hn.data() + p0, hm.data() + p0, (int64_t *)c.out_score.p + p0, (gnx_cigar *)c.out_ops.p + total, cap - total,
@@ -2309,6 +2472,11 @@ int run_host_scored(const gnx_params *prm, int64_t chunk, bool groups, int64_t n
     } else c.timing = tsum;
     if (rc) return rc;
     const double t_dp = ms_since(t_begin);
+    if (score_only) { // the CIGAR stays on the device
+        if (n_pairs) HIPCHK(hipMemcpyAsync(out_score, c.out_score.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return GNX_OK;
+    }
     if (chunk > 1 && total > 0) hipLaunchKernelGGL(scale_runs_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (gnx_cigar *)c.out_ops.p, total, chunk);
     struct HostArr { void *p; explicit HostArr(size_t b) : p(malloc(b)) {} ~HostArr() { free(p); } void *release() { void *q = p; p = nullptr; return q; } };
     HostArr ops_h((size_t)std::max<int64_t>(total, 1) * sizeof(gnx_cigar)), off_h((size_t)(n_pairs + 1) * 8); // freed on every early return below
@@ -3023,6 +3191,64 @@ int gnx_multiple_affine_gap_batch(const gnx_params *p, int64_t chunk_size, int64
         s.nc = (int32_t)(group_len[a] / chunk_size); s.mc = (int32_t)(group_len[b] / chunk_size); s.s_off = 0; s.s_pitch = 0;
     }
     return run_host_scored(p, chunk_size, true, n_pairs, sp, group_bases, n_groups ? group_off[n_groups] : 0, out_score, out_ops, out_ops_off);
+}
+
+// score-only twins: the same validation, the same errors, out_score alone (run_host_scored, score_only)
+int gnx_affine_gap_chunk_score_batch(const gnx_params *p, int64_t chunk_size, int64_t n_pairs,
+                                     const uint8_t *alpha_cat, const int64_t *alpha_off, const uint8_t *beta_cat, const int64_t *beta_off, int64_t *out_score) {
+    std::lock_guard<std::mutex> api(g_api_mu);
+    CtxScope sc(ctx_at(0));
+    g_err[0] = 0;
+    // (what needs no device is refused before one is looked for)
+    if (!p || !out_score || n_pairs < 0 || chunk_size < 1 || chunk_size > (1 << 20) || (n_pairs > 0 && (!alpha_off || !beta_off))) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (p->mode != GNX_AFFINE_GAP_HIGHMEM) { set_err("the chunk / multiple-alignment variants have AffineGap_highMem semantics (mode %s%lld)", "", (long long)GNX_AFFINE_GAP_HIGHMEM); return GNX_EINVAL; }
+    int rc = ensure_init();
+    if (rc) return rc;
+    const int64_t la = n_pairs ? alpha_off[n_pairs] : 0, lb = n_pairs ? beta_off[n_pairs] : 0;
+    std::vector<ScorePair> sp((size_t)n_pairs);
+    for (int64_t q = 0; q < n_pairs; q++) {
+        const int64_t n = alpha_off[q + 1] - alpha_off[q], m = beta_off[q + 1] - beta_off[q];
+        if (n < 0 || m < 0 || n > 0x3fffffff || m > 0x3fffffff) { set_err("bad sequence length at pair %s%lld", "", (long long)q); return GNX_EINVAL; }
+        if (n % chunk_size != 0 || m % chunk_size != 0) { // log.Fatalf in the reference (affineGap_highMem.go:229-234)
+            set_err("pair %s%lld: sequence length is not a multiple of the chunk size", "", (long long)q); return GNX_EINVAL;
+        }
+        ScorePair &s = sp[(size_t)q];
+        s.a_off = alpha_off[q]; s.b_off = la + beta_off[q]; s.a_nseq = 1; s.b_nseq = 1; s.a_len = (int32_t)n; s.b_len = (int32_t)m;
+        s.nc = (int32_t)(n / chunk_size); s.mc = (int32_t)(m / chunk_size); s.s_off = 0; s.s_pitch = 0;
+    }
+    return run_host_scored(p, chunk_size, false, n_pairs, sp, alpha_cat, la, out_score, nullptr, nullptr, beta_cat, lb, true);
+}
+
+int gnx_multiple_affine_gap_score_batch(const gnx_params *p, int64_t chunk_size, int64_t n_groups, const uint8_t *group_bases,
+                                        const int64_t *group_off, const int32_t *group_nseq, const int64_t *group_len,
+                                        int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b, int64_t *out_score) {
+    std::lock_guard<std::mutex> api(g_api_mu);
+    CtxScope sc(ctx_at(0));
+    g_err[0] = 0;
+    if (!p || !out_score || n_pairs < 0 || n_groups < 0 || chunk_size < 1 || chunk_size > (1 << 20) || (n_groups > 0 && (!group_off || !group_nseq || !group_len)) || (n_pairs > 0 && (!pair_a || !pair_b))) {
+        set_err("bad argument%s", ""); return GNX_EINVAL;
+    }
+    if (p->mode != GNX_AFFINE_GAP_HIGHMEM) { set_err("the chunk / multiple-alignment variants have AffineGap_highMem semantics (mode %s%lld)", "", (long long)GNX_AFFINE_GAP_HIGHMEM); return GNX_EINVAL; }
+    int rc = ensure_init();
+    if (rc) return rc;
+    for (int64_t g = 0; g < n_groups; g++) {
+        if (group_nseq[g] < 1 || group_len[g] < 0 || group_len[g] > 0x3fffffff || group_off[g + 1] - group_off[g] != (int64_t)group_nseq[g] * group_len[g]) {
+            set_err("group %s%lld: bases do not match nseq x len", "", (long long)g); return GNX_EINVAL;
+        }
+    }
+    std::vector<ScorePair> sp((size_t)n_pairs);
+    for (int64_t q = 0; q < n_pairs; q++) {
+        const int32_t a = pair_a[q], b = pair_b[q];
+        if (a < 0 || b < 0 || a >= n_groups || b >= n_groups) { set_err("pair %s%lld: group index out of range", "", (long long)q); return GNX_EINVAL; }
+        if (group_len[a] % chunk_size != 0 || group_len[b] % chunk_size != 0) { // log.Fatalf (affineGap_highMem.go:310-315)
+            set_err("pair %s%lld: alignment length is not a multiple of the chunk size", "", (long long)q); return GNX_EINVAL;
+        }
+        ScorePair &s = sp[(size_t)q];
+        s.a_off = group_off[a]; s.b_off = group_off[b]; s.a_nseq = group_nseq[a]; s.b_nseq = group_nseq[b];
+        s.a_len = (int32_t)group_len[a]; s.b_len = (int32_t)group_len[b];
+        s.nc = (int32_t)(group_len[a] / chunk_size); s.mc = (int32_t)(group_len[b] / chunk_size); s.s_off = 0; s.s_pitch = 0;
+    }
+    return run_host_scored(p, chunk_size, true, n_pairs, sp, group_bases, n_groups ? group_off[n_groups] : 0, out_score, nullptr, nullptr, nullptr, 0, true);
 }
 
 /* ---- "next" row N4: seed index and seed search of the graph aligner (see seed_kernels.hip.h) ---- */

@@ -98,7 +98,9 @@ typedef struct gnx_timing {
                             2: the constant-gap path without a stored direction matrix (const_long.hip.h); 0: full direction matrix;
                             3 / 4: the latency geometry (few pairs) in its int32 / int64 form; 5: the 64-lane affine snapshot path;
                             6: the constant-gap snapshot path in its 64-lane form; 7: the score-only sweep ran (gnx_score_* entries,
-                            score_sweep.hip.h); 8: its AffineGapLocal variant ran (gnx_score_* with GNX_AFFINE_GAP_LOCAL, gnx_locate_*).
+                            score_sweep.hip.h); 8: its AffineGapLocal variant ran (gnx_score_* with GNX_AFFINE_GAP_LOCAL, gnx_locate_*);
+                            9: the score-only sweep with explicit cell scores ran (gnx_affine_gap_chunk_score_batch,
+                            gnx_multiple_affine_gap_score_batch; n1_sweep.hip.h).
                             Multi-context score calls report the maximum over contexts. */
     int32_t _pad;
     /* host-buffer entry points only (wall clock inside the library): */
@@ -281,6 +283,24 @@ int gnx_multiple_affine_gap_batch(const gnx_params *p, int64_t chunk_size, int64
                                   const int64_t *group_off, const int32_t *group_nseq, const int64_t *group_len,
                                   int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b,
                                   int64_t *out_score, gnx_cigar **out_ops, int64_t **out_ops_off);
+
+/* Score-only twins of the two entries above (an extension: what a progressive-alignment round needs to choose its pair): the same
+ * arguments minus out_ops / out_ops_off, the same validation and the same return codes for the same inputs (GNX_EINVAL for another
+ * mode, lengths that are not multiples of chunk_size or bad pointers, GNX_EBASE, GNX_EDIVZERO, GNX_ERANGE only where the twin returns
+ * it; GNX_EBASE and GNX_EDIVZERO are reported before any score is written; GNX_EDEVICE without a device, after the argument, mode and
+ * chunk-size checks).  Contract: out_score[q] equals the score the twin returns for pair q.  One context, like the twins.
+ * The score-matrix stage is the twins'.  The DP is the score sweep with explicit cell scores (gnx_timing.fast_path == 9) when
+ * gapOpen <= 0, every pair has both sides non-empty, the shorter side is at most 10 240 chunk cells, (nc + mc + 2) * 2 * max|penalty|
+ * is below 2^30 and every entry s - 2e and gapOpen are inside +-16 000 -- penalties and scores scaled by chunk_size, e = gapExtend *
+ * chunk_size; that route allocates no CIGAR, no direction words and no traceback buffers.  Everything else (gapOpen > 0, an empty
+ * side, a call the twin runs in int64, pairs beyond those bounds, GNX_SCORE_SWEEP=0) runs the route the twin takes and leaves the
+ * CIGAR on the device. */
+int gnx_affine_gap_chunk_score_batch(const gnx_params *p, int64_t chunk_size, int64_t n_pairs,
+                                     const uint8_t *alpha_cat, const int64_t *alpha_off, const uint8_t *beta_cat, const int64_t *beta_off,
+                                     int64_t *out_score);
+int gnx_multiple_affine_gap_score_batch(const gnx_params *p, int64_t chunk_size, int64_t n_groups, const uint8_t *group_bases,
+                                        const int64_t *group_off, const int32_t *group_nseq, const int64_t *group_len,
+                                        int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b, int64_t *out_score);
 
 /* ---- "next" row N2: the seed-extension DPs of the graph aligner (what cmd/gsw spends its DP time in) ------------------ */
 /* genomeGraph.LeftDynamicAln  (/root/reference/genomeGraph/search.go:234-276): constant gap, borders 0, cell values clamped
