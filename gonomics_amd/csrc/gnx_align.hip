@@ -2129,19 +2129,23 @@ bool n1_sweep_fits(const gnx_params *prm2, int64_t n_pairs, const std::vector<Sc
     return true;
 }
 
-// plans: n (rows, <= m), m, src, mat_off and pitch of every pair, in any order.  Sorted by (levels, columns), cut into quads, one
-// launch per number of levels (run_score_sweep).  Writes d_score[src] only; fast_path 9.
-int run_n1_sweep(const gnx_params *prm2, std::vector<N1Plan> plans, const short *d_mat, int64_t *d_score, hipStream_t stream) {
+// ---- the host driver of the score sweeps (score_sweep.hip.h, n1_sweep.hip.h) -------------------------------
+// plans: n (rows), m, src, levels = the pair's own row blocks, and what the kernel's source reads, for every pair in any order.
+// Sorted by (levels, columns, src) unless they already are, cut into quads, one launch per number of levels through the caller's two
+// launchers:  one_block(plans, W)  for the quads of one row block,  levels(plans, S, W, level0, piped, grid)  for the others -- ONE
+// piped launch of all levels, or one launch per level (GNX_NO_PIPE, and again after a level timed out waiting: err bit 16).  The
+// launchers find the error word, the hand-over rows and the progress / claim words in ss_err, ss_rowbuf and ss_prog.
+// Leaves the error word of the sweep that counts in `ef` and fills gnx_timing.
+template <class Plan, class OneBlock, class Levels>
+int run_sweep_plans(std::vector<Plan> &plans, hipStream_t stream, int fast_path, int64_t cells, int &ef, OneBlock one_block, Levels levels) {
     Ctx &c = g_ctx;
     int rc;
-    constexpr int HB = G * SS_RR;
     const int64_t n_pairs = (int64_t)plans.size();
-    int64_t cells = 0;
-    for (N1Plan &pl : plans) { pl.levels = (int32_t)((pl.n + HB - 1) / HB); cells += (int64_t)pl.n * pl.m; }
-    std::sort(plans.begin(), plans.end(), [](const N1Plan &x, const N1Plan &y) { return x.levels != y.levels ? x.levels < y.levels : (x.m != y.m ? x.m < y.m : x.src < y.src); });
+    auto before = [](const Plan &x, const Plan &y) { return x.levels != y.levels ? x.levels < y.levels : (x.m != y.m ? x.m < y.m : x.src < y.src); };
+    if (!std::is_sorted(plans.begin(), plans.end(), before)) std::sort(plans.begin(), plans.end(), before);
     // quads: four consecutive pairs, all with the row blocks of the tallest (the last) of them; the last quad is filled with empty slots
     const int64_t n_quads = (n_pairs + 3) / 4;
-    N1Plan empty = {}; empty.levels = 1;
+    Plan empty = {}; empty.levels = 1;
     plans.resize((size_t)n_quads * 4, empty);
     struct Group { int64_t q0, nq; int S; };
     std::vector<Group> groups;
@@ -2150,7 +2154,7 @@ int run_n1_sweep(const gnx_params *prm2, std::vector<N1Plan> plans, const short 
         int S = 1;
         for (int k = 0; k < 4; k++) S = std::max(S, (int)plans[(size_t)(q * 4 + k)].levels);
         for (int k = 0; k < 4; k++) {
-            N1Plan &pl = plans[(size_t)(q * 4 + k)];
+            Plan &pl = plans[(size_t)(q * 4 + k)];
             pl.levels = S;
             if (S > 1 && pl.n > 0) { pl.rowbuf_off = rb_total; rb_total += 2 * ((int64_t)pl.m + 1); }
         }
@@ -2158,65 +2162,71 @@ int run_n1_sweep(const gnx_params *prm2, std::vector<N1Plan> plans, const short 
         groups.back().nq++;
     }
     for (const Group &gq : groups) if (gq.S > 1) prog_max = std::max<int64_t>(prog_max, (int64_t)gq.S * gq.nq * 2 + 2);
-    if ((rc = c.ss_plans.ensure(plans.size() * sizeof(N1Plan)))) return rc;
+    if ((rc = c.ss_plans.ensure(plans.size() * sizeof(Plan)))) return rc;
     if ((rc = c.ss_err.ensure(64))) return rc;
     if (rb_total && (rc = c.ss_rowbuf.ensure((size_t)rb_total * sizeof(int2)))) return rc;
     if (prog_max && (rc = c.ss_prog.ensure((size_t)prog_max * 4))) return rc;
-    const N1Plan *dpl = reinterpret_cast<const N1Plan *>(c.ss_plans.p);
+    const Plan *dpl = reinterpret_cast<const Plan *>(c.ss_plans.p);
     int *d_err = reinterpret_cast<int *>(c.ss_err.p);
-    int2 *rb = reinterpret_cast<int2 *>(c.ss_rowbuf.p);
     int *prog = reinterpret_cast<int *>(c.ss_prog.p);
-    HIPCHK(hipMemcpyAsync(c.ss_plans.p, plans.data(), plans.size() * sizeof(N1Plan), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemsetAsync(d_err, 0, 64, stream));
-    const int o = (int)prm2->gap_open, e = (int)prm2->gap_extend;
+    HIPCHK(hipMemcpyAsync(c.ss_plans.p, plans.data(), plans.size() * sizeof(Plan), hipMemcpyHostToDevice, stream));
     int64_t launches = 0;
-    auto sweep = [&](bool piped) -> int {
+    auto sweep = [&](bool piped) -> int { // every group once; the error word comes back in `ef`
         for (const Group &gq : groups) {
-            const N1Plan *gp = dpl + gq.q0 * 4;
+            const Plan *gp = dpl + gq.q0 * 4;
             const int W = (int)gq.nq, S = gq.S;
             if (S == 1) {
-                hipLaunchKernelGGL(n1_sweep_kernel, dim3((unsigned)W), dim3(64), 0, stream, gp, d_mat, o, e, d_score, d_err);
+                one_block(gp, W);
+                launches++;
+            } else if (piped) {
+                HIPCHK(hipMemsetAsync(prog, 0, ((size_t)S * W * 2 + 2) * 4, stream)); // progress words, claim words, test switch
+                if ((rc = claim_test_switch(prog + (size_t)S * W * 2, stream))) return rc;
+                levels(gp, S, W, 0, 1, (unsigned)((int64_t)S * W));
                 launches++;
             } else {
-                N1LevelsArgs la{gp, d_mat, o, e, d_score, d_err, rb, S, W, 0, 1, prog};
-                if (piped) {
-                    HIPCHK(hipMemsetAsync(prog, 0, ((size_t)S * W * 2 + 2) * 4, stream)); // progress words, claim words, test switch
-                    if ((rc = claim_test_switch(prog + (size_t)S * W * 2, stream))) return rc;
-                    hipLaunchKernelGGL(n1_sweep_levels_kernel, dim3((unsigned)((int64_t)S * W)), dim3(64), 0, stream, la);
+                for (int level = 0; level < S; level++) {
+                    levels(gp, S, W, level, 0, (unsigned)W);
                     launches++;
-                } else {
-                    la.piped = 0;
-                    for (int level = 0; level < S; level++) {
-                        la.level0 = level;
-                        hipLaunchKernelGGL(n1_sweep_levels_kernel, dim3((unsigned)W), dim3(64), 0, stream, la);
-                        launches++;
-                    }
                 }
             }
             HIPCHK(hipGetLastError());
         }
+        HIPCHK(hipEventRecord(c.ev[1], stream));
+        HIPCHK(hipMemcpyAsync(&ef, d_err, 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
         return GNX_OK;
     };
+    HIPCHK(hipMemsetAsync(d_err, 0, 64, stream));
     HIPCHK(hipEventRecord(c.ev[0], stream));
     if ((rc = sweep(!no_pipe()))) return rc;
-    HIPCHK(hipEventRecord(c.ev[1], stream));
-    int ef = 0;
-    HIPCHK(hipMemcpyAsync(&ef, d_err, 4, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    if (ef & 16) { // a level that waited 5 s for the one above it (a bug trap): sweep again, level by level
+    if (ef & 16) { // a level that waited 5 s for the one above it (a bug trap, as on the fast path): sweep again, level by level
         if (getenv("GNX_DEBUG")) fprintf(stderr, "[gnx score] a row block timed out waiting for the one above it -> one launch per level\n");
         HIPCHK(hipMemsetAsync(d_err, 0, 64, stream));
         if ((rc = sweep(false))) return rc;
-        HIPCHK(hipEventRecord(c.ev[1], stream));
-        HIPCHK(hipStreamSynchronize(stream));
     }
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
-    if (getenv("GNX_DEBUG")) fprintf(stderr, "[gnx score] scored sweep: %lld pairs, %d group(s), %lld launch(es), %.3f ms\n", (long long)n_pairs, (int)groups.size(), (long long)launches, ms);
+    if (getenv("GNX_DEBUG")) fprintf(stderr, "[gnx score] %s sweep: %lld pairs, %d group(s), %lld launch(es), %.3f ms\n", fast_path == 9 ? "scored" : "score", (long long)n_pairs, (int)groups.size(), (long long)launches, ms);
     c.timing = gnx_timing{};
     c.timing.fill_ms = ms; c.timing.total_ms = ms; c.timing.cells = cells; c.timing.n_launches = 1; c.timing.trace_bytes = 0;
-    c.timing.dominant_ms = ms; c.timing.dominant_launches = launches; c.timing.fast_path = 9;
+    c.timing.dominant_ms = ms; c.timing.dominant_launches = launches; c.timing.fast_path = fast_path;
     return GNX_OK;
+}
+
+// plans: n (rows, <= m), m, src, mat_off and pitch of every pair, in any order.  Writes d_score[src] only; fast_path 9.
+int run_n1_sweep(const gnx_params *prm2, std::vector<N1Plan> plans, const short *d_mat, int64_t *d_score, hipStream_t stream) {
+    Ctx &c = g_ctx;
+    constexpr int HB = G * SS_RR;
+    int64_t cells = 0;
+    for (N1Plan &pl : plans) { pl.levels = (int32_t)((pl.n + HB - 1) / HB); cells += (int64_t)pl.n * pl.m; }
+    const int o = (int)prm2->gap_open, e = (int)prm2->gap_extend;
+    int ef = 0;
+    return run_sweep_plans(plans, stream, 9, cells, ef,
+        [&](const N1Plan *gp, int W) { hipLaunchKernelGGL(n1_sweep_kernel, dim3((unsigned)W), dim3(64), 0, stream, gp, d_mat, o, e, d_score, (int *)c.ss_err.p); },
+        [&](const N1Plan *gp, int S, int W, int level0, int piped, unsigned grid) {
+            N1LevelsArgs la{gp, d_mat, o, e, d_score, (int *)c.ss_err.p, (int2 *)c.ss_rowbuf.p, S, W, level0, piped, (int *)c.ss_prog.p};
+            hipLaunchKernelGGL(n1_sweep_levels_kernel, dim3(grid), dim3(64), 0, stream, la);
+        });
 }
 
 // N1 host flow: bases (pairwise sequences or alignment blocks) -> score matrices on the device -> SCORED fill + the
@@ -2558,7 +2568,7 @@ int run_host_windows(const gnx_params *prm, int64_t n_pairs,
 // Global affine / constant gap with gapOpen <= 0, both sequences non-empty, the shorter one <= SS_MAX_LEVELS * 160 bases, the profile
 // entries s - 2e and gapOpen inside int16 with room to spare, and the rebased keys inside int32: (n + m + 2) * 2 * max|penalty| < 2^30.
 // One pass over the batch: pairs sorted by (row blocks, columns) so that the four pairs of a wave are alike, one launch per number
-// of row blocks.  Returns GNX_OK, an error, or -1 when the batch is not the sweep's (the caller then takes the ordinary route and
+// of row blocks (run_sweep_plans).  Returns GNX_OK, an error, or -1 when the batch is not the sweep's (the caller then takes the ordinary route and
 // leaves the CIGAR on the device).  Writes d_score[pair] only.
 // AffineGapLocal (fast_path 8): the rows are the QUERY whatever the lengths -- beta, or alpha when
 // query_is_alpha (gnx_locate_batch_by_offset: alpha = reads, beta = target windows of the resident reference; prm->scores is
@@ -2587,7 +2597,6 @@ int run_score_sweep(const gnx_params *prm, int64_t n_pairs, const uint8_t *d_a, 
     constexpr int HB = G * SS_RR;
     std::vector<ScorePlan> plans((size_t)n_pairs);
     int64_t cells = 0;
-    bool sorted = true;
     for (int64_t p = 0; p < n_pairs; p++) {
         const int64_t n = h_alen[p], m = h_blen[p];
         if (n < 1 || m < 1 || n > 0x3fffffff || m > 0x3fffffff) return -1;
@@ -2597,109 +2606,30 @@ int run_score_sweep(const gnx_params *prm, int64_t n_pairs, const uint8_t *d_a, 
         ScorePlan &pl = plans[(size_t)p];
         pl.n = (int32_t)ns; pl.m = (int32_t)ml; pl.src = (int32_t)p; pl.swap = rows_b ? 1 : 0; pl.rowbuf_off = 0; pl.levels = (int32_t)((ns + HB - 1) / HB); pl._pad = 0;
         cells += n * m;
-        if (p > 0) { const ScorePlan &q = plans[(size_t)p - 1]; if (q.levels > pl.levels || (q.levels == pl.levels && q.m > pl.m)) sorted = false; }
     }
-    if (!sorted) std::sort(plans.begin(), plans.end(), [](const ScorePlan &x, const ScorePlan &y) { return x.levels != y.levels ? x.levels < y.levels : (x.m != y.m ? x.m < y.m : x.src < y.src); });
-    // quads: four consecutive pairs, all with the row blocks of the tallest (the last) of them; the last quad is filled with empty slots
-    const int64_t n_quads = (n_pairs + 3) / 4;
-    plans.resize((size_t)n_quads * 4, ScorePlan{0, 0, 0, 0, 0, 1, 0});
-    struct Group { int64_t q0, nq; int S; };
-    std::vector<Group> groups;
-    int64_t rb_total = 0, prog_max = 0;
-    for (int64_t q = 0; q < n_quads; q++) {
-        int S = 1;
-        for (int k = 0; k < 4; k++) S = std::max(S, (int)plans[(size_t)(q * 4 + k)].levels);
-        for (int k = 0; k < 4; k++) {
-            ScorePlan &pl = plans[(size_t)(q * 4 + k)];
-            pl.levels = S;
-            if (S > 1 && pl.n > 0) { pl.rowbuf_off = rb_total; rb_total += 2 * ((int64_t)pl.m + 1); }
-        }
-        if (groups.empty() || groups.back().S != S) groups.push_back(Group{q, 0, S});
-        groups.back().nq++;
-    }
-    for (const Group &gq : groups) if (gq.S > 1) prog_max = std::max<int64_t>(prog_max, (int64_t)gq.S * gq.nq * 2 + 2);
-    if ((rc = c.ss_plans.ensure(plans.size() * sizeof(ScorePlan)))) return rc;
-    if ((rc = c.ss_err.ensure(64))) return rc;
-    if (rb_total && (rc = c.ss_rowbuf.ensure((size_t)rb_total * sizeof(int2)))) return rc;
-    if (prog_max && (rc = c.ss_prog.ensure((size_t)prog_max * 4))) return rc;
     if (c.beta_packed) {
         kp.b2 = reinterpret_cast<const unsigned *>(c.ref.p); kp.bflag = reinterpret_cast<const unsigned long long *>(c.ref_flag.p);
         kp.brank = reinterpret_cast<const unsigned *>(c.ref_rank.p); kp.bexc = reinterpret_cast<const unsigned long long *>(c.ref_exc.p);
     }
-    const ScorePlan *dpl = reinterpret_cast<const ScorePlan *>(c.ss_plans.p);
-    int *d_err = reinterpret_cast<int *>(c.ss_err.p);
-    int2 *rb = reinterpret_cast<int2 *>(c.ss_rowbuf.p);
-    int *prog = reinterpret_cast<int *>(c.ss_prog.p);
-    HIPCHK(hipMemcpyAsync(c.ss_plans.p, plans.data(), plans.size() * sizeof(ScorePlan), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemsetAsync(d_err, 0, 64, stream));
-    int64_t launches = 0;
-    auto sweep = [&](bool piped) -> int {
-        for (const Group &gq : groups) {
-            const ScorePlan *gp = dpl + gq.q0 * 4;
-            const int W = (int)gq.nq, S = gq.S;
-            if (S == 1 && local) {
-                hipLaunchKernelGGL(score_local_kernel, dim3((unsigned)W), dim3(64), 0, stream, gp, d_a, d_as, d_b, d_bs, kp, sp, d_score, d_end, d_err);
-                launches++;
-            } else if (S == 1) {
-                auto k = affine ? score_sweep_kernel<true> : score_sweep_kernel<false>;
-                hipLaunchKernelGGL(k, dim3((unsigned)W), dim3(64), 0, stream, gp, d_a, d_as, d_b, d_bs, kp, sp, d_score, d_err);
-                launches++;
-            } else if (local) {
-                ScoreLocalLevelsArgs la{gp, d_a, d_as, d_b, d_bs, kp, sp, d_score, d_end, d_err, rb, S, W, 0, 1, prog};
-                if (piped) {
-                    HIPCHK(hipMemsetAsync(prog, 0, ((size_t)S * W * 2 + 2) * 4, stream)); // progress words, claim words, test switch
-                    if ((rc = claim_test_switch(prog + (size_t)S * W * 2, stream))) return rc;
-                    hipLaunchKernelGGL(score_local_levels_kernel, dim3((unsigned)((int64_t)S * W)), dim3(64), 0, stream, la);
-                    launches++;
-                } else {
-                    la.piped = 0;
-                    for (int level = 0; level < S; level++) {
-                        la.level0 = level;
-                        hipLaunchKernelGGL(score_local_levels_kernel, dim3((unsigned)W), dim3(64), 0, stream, la);
-                        launches++;
-                    }
-                }
-            } else {
-                auto k = affine ? score_sweep_levels_kernel<true> : score_sweep_levels_kernel<false>;
-                ScoreLevelsArgs la{gp, d_a, d_as, d_b, d_bs, kp, sp, d_score, d_err, rb, S, W, 0, 1, prog};
-                if (piped) {
-                    HIPCHK(hipMemsetAsync(prog, 0, ((size_t)S * W * 2 + 2) * 4, stream)); // progress words, claim words, test switch
-                    if ((rc = claim_test_switch(prog + (size_t)S * W * 2, stream))) return rc;
-                    hipLaunchKernelGGL(k, dim3((unsigned)((int64_t)S * W)), dim3(64), 0, stream, la);
-                    launches++;
-                } else {
-                    la.piped = 0;
-                    for (int level = 0; level < S; level++) {
-                        la.level0 = level;
-                        hipLaunchKernelGGL(k, dim3((unsigned)W), dim3(64), 0, stream, la);
-                        launches++;
-                    }
-                }
-            }
-            HIPCHK(hipGetLastError());
-        }
-        return GNX_OK;
-    };
-    HIPCHK(hipEventRecord(c.ev[0], stream));
-    if ((rc = sweep(!no_pipe()))) return rc;
-    HIPCHK(hipEventRecord(c.ev[1], stream));
     int ef = 0;
-    HIPCHK(hipMemcpyAsync(&ef, d_err, 4, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    if (ef & 16) { // a level that waited 5 s for the one above it (a bug trap, as on the fast path): sweep again, level by level
-        if (getenv("GNX_DEBUG")) fprintf(stderr, "[gnx score] a row block timed out waiting for the one above it -> one launch per level\n");
-        HIPCHK(hipMemsetAsync(d_err, 0, 64, stream));
-        if ((rc = sweep(false))) return rc;
-        HIPCHK(hipEventRecord(c.ev[1], stream));
-        HIPCHK(hipMemcpyAsync(&ef, d_err, 4, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-    }
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
-    if (getenv("GNX_DEBUG")) fprintf(stderr, "[gnx score] score sweep: %lld pairs, %d group(s), %lld launch(es), %.3f ms\n", (long long)n_pairs, (int)groups.size(), (long long)launches, ms);
-    c.timing = gnx_timing{};
-    c.timing.fill_ms = ms; c.timing.total_ms = ms; c.timing.cells = cells; c.timing.n_launches = 1; c.timing.trace_bytes = 0;
-    c.timing.dominant_ms = ms; c.timing.dominant_launches = launches; c.timing.fast_path = local ? 8 : 7;
+    rc = run_sweep_plans(plans, stream, local ? 8 : 7, cells, ef,
+        [&](const ScorePlan *gp, int W) {
+            int *d_err = (int *)c.ss_err.p;
+            if (local) hipLaunchKernelGGL(score_local_kernel, dim3((unsigned)W), dim3(64), 0, stream, gp, d_a, d_as, d_b, d_bs, kp, sp, d_score, d_end, d_err);
+            else hipLaunchKernelGGL(affine ? score_sweep_kernel<true> : score_sweep_kernel<false>, dim3((unsigned)W), dim3(64), 0, stream, gp, d_a, d_as, d_b, d_bs, kp, sp, d_score, d_err);
+        },
+        [&](const ScorePlan *gp, int S, int W, int level0, int piped, unsigned grid) {
+            int *d_err = (int *)c.ss_err.p, *prog = (int *)c.ss_prog.p;
+            int2 *rb = (int2 *)c.ss_rowbuf.p;
+            if (local) {
+                ScoreLocalLevelsArgs la{gp, d_a, d_as, d_b, d_bs, kp, sp, d_score, d_end, d_err, rb, S, W, level0, piped, prog};
+                hipLaunchKernelGGL(score_local_levels_kernel, dim3(grid), dim3(64), 0, stream, la);
+            } else {
+                ScoreLevelsArgs la{gp, d_a, d_as, d_b, d_bs, kp, sp, d_score, d_err, rb, S, W, level0, piped, prog};
+                hipLaunchKernelGGL(affine ? score_sweep_levels_kernel<true> : score_sweep_levels_kernel<false>, dim3(grid), dim3(64), 0, stream, la);
+            }
+        });
+    if (rc) return rc;
     if (ef & 1) { set_err("a base >= 5 was found: the reference would panic (index out of range)%s", ""); return GNX_EBASE; }
     return GNX_OK;
 }

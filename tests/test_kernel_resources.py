@@ -114,3 +114,27 @@ def test_lds_budgets(kernels):
             if name.startswith(prefix) and (k["group_segment_fixed_size"] + 1279) // 1280 > granules:
                 bad.append((name, k["group_segment_fixed_size"], granules))
     assert not bad, bad
+
+
+# The score-only sweeps (one body, score_sweep.hip.h, in eight kernels): the exact VGPRs and LDS bytes of each kernel
+# as built, and the waves per SIMD its registers allow.  The local one-block kernel has 97 registers, one more than five waves take (its global
+# twin: 93): the LDS of the profile sweeps (8 granules of 1280 B = 16 one-wave workgroups per CU) bounds both at four waves per SIMD anyway.
+# The kernels with explicit cell scores keep no profile in LDS and allow the waves of their global affine twins (4 / 3).
+SCORE_SWEEP_PINS = {
+    "score_sweep_kernel<true>": (93, 9856, 5), "score_sweep_kernel<false>": (69, 9856, 7),
+    "score_sweep_levels_kernel<true>": (135, 9856, 3), "score_sweep_levels_kernel<false>": (103, 9856, 4),
+    "score_local_kernel": (97, 9856, 4), "score_local_levels_kernel": (153, 9856, 3),
+    "n1_sweep_kernel": (109, 0, 4), "n1_sweep_levels_kernel": (161, 1536, 3),
+}
+
+
+def test_score_sweep_kernel_resources(kernels):
+    for name, (vgprs, lds, waves) in SCORE_SWEEP_PINS.items():
+        assert name in kernels, (name, sorted(kernels))
+        k = kernels[name]
+        assert k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0 and k["sgpr_spill_count"] == 0, (name, k)
+        assert k["agpr_count"] == 0, (name, k)
+        assert (k["vgpr_count"], k["group_segment_fixed_size"]) == (vgprs, lds), (name, k)
+        assert _waves_per_simd(k) == waves, (name, k["vgpr_count"], _waves_per_simd(k), waves)
+        # LDS in granules of 1280 B: at most 8, so that 16 one-wave workgroups (four waves per SIMD) fit a CU's 160 KB
+        assert (k["group_segment_fixed_size"] + 1279) // 1280 <= 8, (name, k["group_segment_fixed_size"])

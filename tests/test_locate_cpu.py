@@ -1,5 +1,5 @@
 """CPU-side checks of the locate entries (gnx_locate_*): symbols and bindings, the no-device and wrong-mode errors, the C++ mirror's
-build, and the resources of the local score sweep's kernels (score_sweep.hip.h)."""
+build.  The resources of the local score sweep's kernels: test_kernel_resources.py."""
 import ctypes
 import os
 import re
@@ -9,7 +9,6 @@ import numpy as np
 import pytest
 
 from gonomics_amd import _lib, align, dna
-from test_kernel_resources import LLVM, _kernels, _waves_per_simd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LOCATE_ENTRIES = ["gnx_locate_batch", "gnx_locate_batch_windows", "gnx_locate_batch_by_offset"]
@@ -61,25 +60,3 @@ def test_cpp_locate_mirror_builds_and_refuses_without_gpu():
     _build_cpp()
     rc = subprocess.call([BIN])
     assert rc in (0, 2)  # 2 == "no HIP device" (no CPU fallback); 0 on a GPU box
-
-
-@pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    if not os.path.exists(f"{LLVM}/llvm-readelf"):
-        pytest.skip("no llvm-readelf")
-    return _kernels(tmp_path_factory.mktemp("co_locate"))
-
-
-# waves per SIMD the registers of the local sweep's kernels allow, LDS in granules of 1280 B.  The one-block kernel has 97 registers,
-# one more than five waves take (its global twin: 93): the LDS of the sweep (8 granules = 16 waves per CU) bounds both at four waves per SIMD anyway
-LOCAL_BUDGET = [("score_local_kernel", 4), ("score_local_levels_kernel", 3)]
-
-
-def test_local_score_kernel_resources(kernels):
-    for prefix, waves in LOCAL_BUDGET:
-        ks = {n: k for n, k in kernels.items() if n == prefix}
-        assert len(ks) == 1, (prefix, sorted(ks))
-        for n, k in ks.items():
-            assert k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0 and k["sgpr_spill_count"] == 0, (n, k)
-            assert _waves_per_simd(k) == waves, (n, k["vgpr_count"], k["agpr_count"], _waves_per_simd(k), waves)
-            assert (k["group_segment_fixed_size"] + 1279) // 1280 <= 8, (n, k["group_segment_fixed_size"])

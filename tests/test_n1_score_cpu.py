@@ -1,5 +1,5 @@
 """CPU-side checks of the score-only chunk / multiple-alignment entries (gnx_*_score_batch) and of the score-first progressive
-driver: symbols and bindings, errors that need no device, the resources of the sweep's kernels (n1_sweep.hip.h),
+driver: symbols and bindings, errors that need no device (the resources of the sweep's kernels: test_kernel_resources.py),
 the driver on the CPU oracle (results, number of engine calls, reuse of remembered scores) and the identity behind that reuse."""
 import ctypes
 import os
@@ -11,7 +11,6 @@ import pytest
 import n1_helpers
 import oracle
 from gonomics_amd import _lib, align, dna, fasta
-from test_kernel_resources import LLVM, _kernels, _waves_per_simd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ["gnx_affine_gap_chunk_score_batch", "gnx_multiple_affine_gap_score_batch"]
@@ -60,30 +59,6 @@ def test_n1_score_errors_without_a_device():
     with pytest.raises(_lib.GnxError) as ei:
         align.AffineGapChunkScore(a, b, align.DefaultScoreMatrix, -400, -30, 3)
     assert ei.value.code == _lib.GNX_EDEVICE
-
-
-@pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    if not os.path.exists(f"{LLVM}/llvm-readelf"):
-        pytest.skip("no llvm-readelf")
-    return _kernels(tmp_path_factory.mktemp("co_n1_score"))
-
-
-# (VGPRs, LDS bytes) of the two kernels as built, and the waves per SIMD they must still allow (those of their 4.15 twins)
-N1_PINS = {"n1_sweep_kernel": (109, 0, 4), "n1_sweep_levels_kernel": (161, 1536, 3)}
-
-
-def test_n1_sweep_kernel_resources(kernels):
-    for prefix, (vgprs, lds, min_waves) in N1_PINS.items():
-        ks = {n: k for n, k in kernels.items() if n == prefix}
-        assert len(ks) == 1, (prefix, sorted(kernels))
-        (n, k), = ks.items()
-        assert k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0 and k["sgpr_spill_count"] == 0, (n, k)
-        assert k["agpr_count"] == 0, (n, k)
-        assert (k["vgpr_count"], k["group_segment_fixed_size"]) == (vgprs, lds), (n, k)
-        assert _waves_per_simd(k) >= min_waves, (n, k["vgpr_count"], _waves_per_simd(k))
-        # LDS in granules of 1280 B: min_waves per SIMD = 4 * min_waves one-wave workgroups per CU of 160 KB
-        assert (k["group_segment_fixed_size"] + 1279) // 1280 * 1280 * 4 * min_waves <= 160 * 1024, (n, k["group_segment_fixed_size"])
 
 
 # ---- the score-first driver on the oracle ------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """CPU-side checks of the score-only entries (gnx_score_*): symbols and bindings, the no-device error, the selection rule of
-AlignBestOf with stub score / align functions, and the resources of the score sweep's kernels (score_sweep.hip.h)."""
+AlignBestOf with stub score / align functions.  The resources of the sweep's kernels: test_kernel_resources.py."""
 import ctypes
 import os
 import re
@@ -8,7 +8,6 @@ import numpy as np
 import pytest
 
 from gonomics_amd import _lib, align, dna
-from test_kernel_resources import LLVM, _kernels, _waves_per_simd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCORE_ENTRIES = ["gnx_score_batch", "gnx_score_batch_windows", "gnx_score_batch_by_offset", "gnx_score_batch_device"]
@@ -82,24 +81,3 @@ def test_align_best_of_selection_rule(monkeypatch):
     with pytest.raises(ValueError):
         align._first_maxima([1], [1, 0])
     assert align.AlignBestOf(None, [], []) == []
-
-
-@pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    if not os.path.exists(f"{LLVM}/llvm-readelf"):
-        pytest.skip("no llvm-readelf")
-    return _kernels(tmp_path_factory.mktemp("co_score"))
-
-
-# waves per SIMD the registers of the score sweep's kernels allow, and their LDS in granules of 1280 B (8 granules = 16 waves per CU)
-SCORE_BUDGET = [("score_sweep_kernel<true>", 5), ("score_sweep_kernel<false>", 7), ("score_sweep_levels_kernel<true>", 3), ("score_sweep_levels_kernel<false>", 4)]
-
-
-def test_score_kernel_resources(kernels):
-    for prefix, waves in SCORE_BUDGET:
-        ks = {n: k for n, k in kernels.items() if n.startswith(prefix)}
-        assert ks, prefix
-        for n, k in ks.items():
-            assert k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0 and k["sgpr_spill_count"] == 0, (n, k)
-            assert _waves_per_simd(k) == waves, (n, k["vgpr_count"], k["agpr_count"], _waves_per_simd(k), waves)
-            assert (k["group_segment_fixed_size"] + 1279) // 1280 <= 8, (n, k["group_segment_fixed_size"])

@@ -10,8 +10,11 @@ taken.  Two stress legs, each over all piped kernels, results against the oracle
     sets GNX_CLAIM_GRACE_US=50 for the launch together with a delay of ~2 ms, so the upper half of the grid really claims and runs its
     predecessors' items (the s_lo .. s_own loops of the strip kernels, the level loop of fp_sweep_levels_kernel), and asserts through
     gnx_debug_counter(0) that at least one item was run by a workgroup other than its own.
+The three levels kernels of the score-only sweeps (score_sweep.hip.h, n1_sweep.hip.h) share one workgroup loop and are not reached
+by align_batch: test_score_levels_do_not_depend_on_dispatch_order drives them through their own entries, delay and steal legs.
 The bug trap (5 s spin timeout -> error flag 16 -> sequential re-run) must stay silent: the legs assert that the piped launch was
 the one that produced the result by checking that the call took far less than the timeout."""
+import functools
 import os
 import time
 
@@ -87,3 +90,67 @@ def test_piped_launches_do_not_depend_on_dispatch_order(gpu_lib, monkeypatch, le
     if stress == "steal" and not common.OUTER_ROUTE_SWITCH and "GNX_NO_PIPE" not in os.environ:
         assert stolen > 0, "%s: nobody ran a predecessor's item -- the n_stolen > 0 paths were not exercised" % name
     time.sleep(0.35)  # let the occupying workgroups end before the next test
+
+
+# ---- the score-only sweeps: score_sweep_levels_kernel<true>, score_local_levels_kernel, n1_sweep_levels_kernel ------------------------
+@functools.lru_cache(maxsize=None)
+def _score_levels_case():
+    """16 pairs = four quads of two and three row blocks, one quad of both (the side held in lanes: 161 .. 480 rows, one pair with
+    exactly 161 = one real row in its top block; 300 .. 500 columns = several publishes of 64), and what the oracle says of them."""
+    from test_locate_gpu import _ends
+    rng = np.random.default_rng(111)
+    n_rows = [161] + [int(x) for x in rng.integers(162, 321, size=6)] + [int(x) for x in rng.integers(321, 481, size=9)]
+    rows, cols = [], []
+    for n in n_rows:
+        m = int(rng.integers(max(n, 300), 501))
+        b = rng.integers(0, 4, size=m).astype(np.uint8)
+        a = common.mutate(rng, b[:n], sub=0.05, indel=0.02, geo=0.4, alphabet=4)
+        a = np.concatenate([a, rng.integers(0, 4, size=n).astype(np.uint8)])[:n]
+        rows.append(a); cols.append(b)
+    mx, go, ge = MX["HumanChimpTwo"], -600, -150
+    exp_global = oracle.align_batch(0, mx, go, ge, rows, cols, threads=8)[0]
+    sc, ops, off = oracle.align_batch(3, mx, go, ge, cols, rows, threads=8)
+    exp_chunk = np.asarray([oracle.affine_gap_chunk(mx, go, ge, 1, a, b)[0] for a, b in zip(rows, cols)], dtype=np.int64)
+    return rows, cols, {"global": (exp_global,), "local": (sc, _ends(ops, off, [len(t) for t in cols])), "chunk": (exp_chunk,)}
+
+
+@pytest.mark.parametrize("route", ["global", "local", "chunk"])
+@pytest.mark.parametrize("stress", ["delay", "steal"])
+def test_score_levels_do_not_depend_on_dispatch_order(gpu_lib, monkeypatch, route, stress):
+    rows, cols, expected = _score_levels_case()
+    exp = expected[route]
+    mx, go, ge = MX["HumanChimpTwo"], -600, -150
+    if route == "global":    # global affine score: the shorter sequence is held in lanes
+        p = gpu_lib.make_params(gpu_lib.GNX_AFFINE_GAP, mx, go, ge)
+        call, fast_path = (lambda: (gpu_lib.score_batch(p, rows, cols),)), 7
+    elif route == "local":   # local score and target end: the query is held in lanes
+        p = gpu_lib.make_params(gpu_lib.GNX_AFFINE_GAP_LOCAL, mx, go, ge)
+        call, fast_path = (lambda: gpu_lib.locate_batch(p, cols, rows)), 8
+    else:                    # chunk score with chunk 1: cell scores from a device matrix
+        p = gpu_lib.make_params(gpu_lib.GNX_AFFINE_GAP_HIGHMEM, mx, go, ge)
+        call, fast_path = (lambda: (gpu_lib.affine_gap_chunk_score_batch(p, 1, rows, cols),)), 9
+
+    def same(got, what):
+        assert len(got) == len(exp), what
+        for g, e in zip(got, exp):
+            assert np.array_equal(np.asarray(g, dtype=np.int64), e), (what, np.flatnonzero(np.asarray(g) != e)[:8])
+
+    monkeypatch.setenv("GNX_DEBUG_ENTRY", "1")
+    same(call(), route)
+    routed = not common.OUTER_ROUTE_SWITCH and "GNX_SCORE_SWEEP" not in os.environ
+    if routed:
+        assert gpu_lib.get_timing()["fast_path"] == fast_path, (route, gpu_lib.get_timing())
+    gpu_lib.debug_counter(0, reset=True)
+    if stress == "steal":
+        monkeypatch.setenv("GNX_TICKET_DELAY", "600")
+        monkeypatch.setenv("GNX_CLAIM_GRACE_US", "50")
+    else:
+        monkeypatch.setenv("GNX_TICKET_DELAY", "40")
+    t0 = time.time()
+    got = call()
+    dt = time.time() - t0
+    same(got, route + " / " + stress)
+    assert dt < 3.0, "%s: %.1f s -- the spin timeout fired, the pipeline did not make progress on its own" % (route, dt)
+    stolen = gpu_lib.debug_counter(0, reset=True)
+    if stress == "steal" and routed and "GNX_NO_PIPE" not in os.environ:
+        assert stolen > 0, "%s: nobody ran a predecessor's item -- the n_stolen > 0 paths were not exercised" % route
