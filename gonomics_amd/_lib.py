@@ -126,6 +126,10 @@ def lib():
         L.gnx_seed_index_set.restype = ctypes.c_int
         L.gnx_seed_find_batch.argtypes = [c_p, c_p, i64, ctypes.POINTER(c_p), ctypes.POINTER(c_p)]
         L.gnx_seed_find_batch.restype = ctypes.c_int
+        L.gnx_seed_index_set_gen.argtypes = [c_p, c_p, i64, c_p, c_p, i64, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
+        L.gnx_seed_index_set_gen.restype = ctypes.c_int
+        L.gnx_seed_find_batch_gen.argtypes = [ctypes.c_uint64, c_p, c_p, i64, ctypes.POINTER(c_p), ctypes.POINTER(c_p)]
+        L.gnx_seed_find_batch_gen.restype = ctypes.c_int
         if hasattr(L, "gnx_gsw_map_reads"):
             L.gnx_gsw_graph_create.argtypes = [c_p, c_p, i64, c_p, c_p, i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_p)]
             L.gnx_gsw_graph_create.restype = ctypes.c_int
@@ -593,7 +597,6 @@ class GswGraph:
         gp, np_, cp = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
         check(L.gnx_gsw_map_reads(self._h, rcat.ctypes.data, roff.ctypes.data, n, 1 if paired else 0, sc.ctypes.data, int(gap_pen), int(threads),
                                   ctypes.byref(gp), ctypes.byref(np_), ctypes.byref(cp)))
-        _seed_set[0] = None  # (the device's resident index is this graph's now)
 
         def take(ptr, dtype, count):
             if count == 0:
@@ -612,22 +615,40 @@ class GswGraph:
 
 
 SEED_HIT_DTYPE = np.dtype([("read_start", np.int32), ("strand", np.int32), ("node", np.int32), ("node_start", np.int32), ("q_start", np.int32), ("right", np.int32)])
+# The index this module uploaded last: (keys, locs, [node sequences], seed_len, generation).  The objects themselves are kept (while
+# they live their ids cannot be handed to other objects) and compared by identity; whether the upload is STILL the device's resident
+# index is not guessed here: the search names its generation and the library answers GNX_ESTALE when a build, another index, a graph
+# handle or a shutdown took its place (gnx_seed_index_set_gen / gnx_seed_find_batch_gen) -- then it is uploaded again.
 _seed_set = [None]
 
 
+def _seed_resident(keys, locs, node_seqs, seed_len):
+    cur = _seed_set[0]
+    return (cur is not None and cur[0] is keys and cur[1] is locs and cur[3] == seed_len and len(cur[2]) == len(node_seqs)
+            and all(a is b for a, b in zip(cur[2], node_seqs)))
+
+
 def seed_find_batch(keys, locs, node_seqs, read_seqs, seed_len):
-    """per read the list of hit tuples (read_start, strand, node, node_start, q_start, right) in the reference's order of discovery"""
+    """per read the list of hit tuples (read_start, strand, node, node_start, q_start, right) in the reference's order of discovery.
+    The index stays resident from call to call as long as the SAME arrays come in (keys, locs and every node sequence, by identity:
+    their contents must not be changed in place in between)."""
     L = lib()
     keys = np.ascontiguousarray(keys, dtype=np.uint64)
     locs = np.ascontiguousarray(locs, dtype=np.uint64)
-    tag = (keys.ctypes.data, locs.ctypes.data, keys.shape[0], id(node_seqs), seed_len)
-    if _seed_set[0] != tag:  # make the index resident once per index object
-        ncat, noff = _cat(node_seqs)
-        check(L.gnx_seed_index_set(keys.ctypes.data, locs.ctypes.data, keys.shape[0], ncat.ctypes.data, noff.ctypes.data, len(node_seqs), int(seed_len)))
-        _seed_set[0] = tag
+    seed_len = int(seed_len)
     rcat, roff = _cat(read_seqs)
     hp, op = ctypes.c_void_p(), ctypes.c_void_p()
-    check(L.gnx_seed_find_batch(rcat.ctypes.data, roff.ctypes.data, len(read_seqs), ctypes.byref(hp), ctypes.byref(op)))
+    for attempt in range(3):
+        if attempt or not _seed_resident(keys, locs, node_seqs, seed_len):
+            _seed_set[0] = None
+            ncat, noff = _cat(node_seqs)
+            gen = ctypes.c_uint64()
+            check(L.gnx_seed_index_set_gen(keys.ctypes.data, locs.ctypes.data, keys.shape[0], ncat.ctypes.data, noff.ctypes.data, len(node_seqs), seed_len, ctypes.byref(gen)))
+            _seed_set[0] = (keys, locs, list(node_seqs), seed_len, gen.value)
+        rc = L.gnx_seed_find_batch_gen(_seed_set[0][4], rcat.ctypes.data, roff.ctypes.data, len(read_seqs), ctypes.byref(hp), ctypes.byref(op))
+        if rc != GNX_ESTALE:  # (stale again right after an upload: another thread's index got in between -- once more, then the error)
+            break
+    check(rc)
     off = np.ctypeslib.as_array(ctypes.cast(op, ctypes.POINTER(ctypes.c_int64)), shape=(len(read_seqs) + 1,)).copy()
     total = int(off[-1])
     if total:

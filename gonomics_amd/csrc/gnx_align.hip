@@ -2710,6 +2710,7 @@ int gnx_init_devices(int n_devices, const int *devices, int64_t workspace_bytes)
 
 int gnx_n_devices(void) { std::lock_guard<std::mutex> api(g_api_mu); return g_nctx; }
 
+static uint64_t g_seed_gen = 0;      // generation of the resident seed index (0: none); guarded by g_api_mu (see gnx_seed_index_set_gen)
 void gnx_shutdown(void) {
     std::lock_guard<std::mutex> api(g_api_mu);
     rccl_drop_comms();
@@ -2731,6 +2732,7 @@ void gnx_shutdown(void) {
         PinBuf *pins[] = {&c.h_plans, &c.st_a[0], &c.st_a[1], &c.st_as[0], &c.st_as[1], &c.st_b[0], &c.st_b[1], &c.st_bs[0], &c.st_bs[1]};
         for (PinBuf *b : pins) b->release();
         c.fpc_ptr = nullptr; c.ref_len = -1; c.sd_n = -1;
+        g_seed_gen++; // (a holder of the old generation uploads again after the next init: GNX_ESTALE, not "no resident seed index")
         for (int i = 0; i < 8; i++) if (c.ev[i]) { (void)hipEventDestroy(c.ev[i]); c.ev[i] = nullptr; }
         for (int i = 0; i < 2; i++) if (c.ev_in[i]) { (void)hipEventDestroy(c.ev_in[i]); c.ev_in[i] = nullptr; }
         if (c.own_stream) { (void)hipStreamDestroy(c.own_stream); c.own_stream = nullptr; }
@@ -3203,6 +3205,7 @@ int gnx_seed_index_build(const uint8_t *node_cat, const int64_t *node_off, int64
     if (n_slots == 0) return GNX_OK;
     DevBuf *t = c.sd_tmp;
     c.sd_n = -1; // the build uploads its nodes into the buffers of the resident index: gnx_seed_find_batch needs a new gnx_seed_index_set
+    g_seed_gen++; // ... and a holder of the old generation hears GNX_ESTALE from gnx_seed_find_batch_gen and uploads again, instead of "no resident seed index"
     if ((rc = c.sd_nodes.ensure((size_t)total + 64))) return rc;
     if ((rc = c.sd_node_off.ensure((size_t)(n_nodes + 1) * 8))) return rc;
     if ((rc = t[0].ensure((size_t)(n_nodes + 1) * 8))) return rc;   // slot_off
@@ -3250,7 +3253,6 @@ int gnx_seed_index_build(const uint8_t *node_cat, const int64_t *node_off, int64
 // be sure it searches ITS index -- the read path of a graph handle, while other threads use other handles or the raw entry points --
 // sets with gnx_seed_index_set_gen and searches with gnx_seed_find_batch_gen(generation): a search against a replaced index is refused
 // with GNX_ESTALE, inside the same lock that runs the search (the check used to sit outside it), and the caller uploads again.
-static uint64_t g_seed_gen = 0;      // generation of the resident index (0: none); guarded by g_api_mu
 static int seed_index_set_locked(const uint64_t *keys, const uint64_t *locs, int64_t n_index, const uint8_t *node_cat, const int64_t *node_off, int64_t n_nodes, int seed_len);
 int gnx_seed_index_set(const uint64_t *keys, const uint64_t *locs, int64_t n_index, const uint8_t *node_cat, const int64_t *node_off, int64_t n_nodes, int seed_len) {
     std::lock_guard<std::mutex> api(g_api_mu);

@@ -350,7 +350,9 @@ int gnx_gsw_map_reads(gnx_gsw_graph *g, const uint8_t *read_cat, const int64_t *
  * node_cat[node_off[k] .. node_off[k+1]) (dna.Base bytes, N allowed); positions 0, seed_step, ... of every node; k-mers with an N
  * are skipped.  Output = the map as two arrays sorted by key (k-mer code, index.go `dnaToNumber`), equal keys in the reference's
  * insertion order (node, position); locations are `node << 32 | pos` (ChromAndPosToNumber).  malloc'd, gnx_free().  The k-mers
- * that run across node borders (index.go:34-38) are left to the host, which merges them and calls gnx_seed_index_set. */
+ * that run across node borders (index.go:34-38) are left to the host, which merges them and calls gnx_seed_index_set.
+ * A build that has k-mer positions to look at works in the buffers of the resident index: nothing is resident after it (a
+ * gnx_seed_find_batch answers GNX_EINVAL until the next set), and it ends the current generation (gnx_seed_find_batch_gen: GNX_ESTALE). */
 int gnx_seed_index_build(const uint8_t *node_cat, const int64_t *node_off, int64_t n_nodes, int seed_len, int seed_step,
                          uint64_t **out_keys, uint64_t **out_locs, int64_t *out_n);
 /* Make an index (+ the nodes, packed like dnaTwoBit does it) resident on the device for gnx_seed_find_batch. */
@@ -372,7 +374,8 @@ int gnx_seed_find_batch(const uint8_t *read_cat, const int64_t *read_off, int64_
 /* The device holds ONE resident index; gnx_seed_index_set + gnx_seed_find_batch are two calls, so another thread's set can land between
  * them.  Callers that share the process with other users of the index (gnx_gsw_map_reads does) use this pair instead: the set returns
  * the GENERATION it installed, the search names it and is refused with GNX_ESTALE -- inside the lock that runs the search -- when the
- * resident index is no longer that one; the caller then sets again.  (The plain pair above stays for single-threaded callers.) */
+ * resident index is no longer that one -- replaced by another set, taken by a gnx_seed_index_build, dropped by gnx_shutdown --; the
+ * caller then sets again.  (The plain pair above stays for single-threaded callers.) */
 int gnx_seed_index_set_gen(const uint64_t *keys, const uint64_t *locs, int64_t n_index, const uint8_t *node_cat, const int64_t *node_off,
                            int64_t n_nodes, int seed_len, uint64_t *out_generation);
 int gnx_seed_find_batch_gen(uint64_t generation, const uint8_t *read_cat, const int64_t *read_off, int64_t n_reads, gnx_seed_hit **out_hits, int64_t **out_hit_off);

@@ -282,6 +282,28 @@ def seed_map(index, nodes, rd, seed_len, sort=True):
     return final
 
 
+def raw_hits(index, nodes, rd, seed_len):
+    """What seedMapMemPool (search.go:549-582) knows about every index location BEFORE a seed is made of it: for each read position,
+    strand (0: plus, then 1: minus) and location in the map's order, the clamped left extension and the first CountRightMatches of
+    extendToTheRightDev (search.go:425-433) -> (read_start, strand, node, node_start, q_start, right), the tuples of the device's
+    seed search (gnx_seed_find_batch).  Built from this module's own count_left / count_right only."""
+    out = []
+    for read_start in range(0, len(rd["seq"]) - seed_len + 1):
+        key_idx = (read_start + 31) // 32
+        key_off = 31 - ((read_start + 31) % 32)
+        for strand, rain in ((0, rd["rb"]), (1, rd["rbrc"])):
+            key = rain[key_off][0][key_idx] >> (64 - 2 * seed_len)
+            for code in index.get(key, []):
+                nid, npos = code >> 32, code & 0xFFFFFFFF
+                ro = 31 - ((read_start - npos % 32 + 31) % 32)
+                left = min(read_start + 1, count_left(nodes[nid]["tb"], npos, rain[ro], read_start + ro))
+                q_start, node_start = read_start - (left - 1), npos - (left - 1)
+                ro = 31 - ((q_start - node_start % 32 + 31) % 32)
+                right = count_right(nodes[nid]["tb"], node_start, rain[ro], q_start + ro)
+                out.append((read_start, strand, nid, node_start, q_start, right))
+    return out
+
+
 def could_be_better(seed_len, best, perfect, qlen, mx, mn, lsm, lsc):
     seeds = qlen // (seed_len + 1)
     rem = qlen % (seed_len + 1)

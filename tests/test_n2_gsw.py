@@ -175,6 +175,97 @@ def test_gsw_gpu_parity(gpu_lib, side):
                                               (np.array([1, 2], np.uint8), np.zeros(0, np.uint8))])
 
 
+# ---- edges the fuzz above does not reach ------------------------------------------------------------------------------------------
+# RightDynamicAln's kernel keeps its running maximum packed as (score << 12 | 4095 - column) in one int; the host admits a pair when
+# (n + m + 2) * max|penalty| < 2^19 and n, m <= 4095.  HumanChimpTwo / -600: max|penalty| = 600, the last admitted n + m + 2 is 873
+# (873 * 600 = 523 800 < 524 288 <= 874 * 600); the cases above stop at n + m = 849.
+def _packed_boundary_pairs(extra):
+    """n + m + 2 = 873 + extra: an all-mismatch pair (A against C: the most negative cells the bound allows for) and an identical one"""
+    n, m = 436 + extra, 435
+    assert n + m + 2 == 873 + extra and int(np.abs(np.asarray(MX["HumanChimpTwo"])).max()) <= 600
+    same = np.random.default_rng(61).integers(0, 4, size=n).astype(np.uint8)
+    return [(np.zeros(n, np.uint8), np.ones(m, np.uint8)), (same, same[:m].copy()), (same[:m].copy(), same)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("side", [0, 1])
+def test_gsw_gpu_packed_range_boundary(gpu_lib, side):
+    _check_gpu(side, "HumanChimpTwo", -600, _packed_boundary_pairs(0))
+    one_more = _packed_boundary_pairs(1)
+    if side == 0:  # LeftDynamicAln packs nothing: one base more is still the oracle's
+        _check_gpu(0, "HumanChimpTwo", -600, one_more)
+    else:
+        for pair in one_more:
+            with pytest.raises(gpu_lib.GnxError) as e:
+                genomeGraph.DynamicAlnBatch("right", [pair[0]], [pair[1]], MX["HumanChimpTwo"], -600)
+            assert e.value.code == gpu_lib.GNX_ERANGE
+
+
+SMALL_MX = [[63 if a == b else -63 for b in range(5)] for a in range(5)]  # entries and gap <= 63 in magnitude: (4095 + 4095 + 2) * 63 < 2^19
+
+
+def _check_gpu_mx(side, sc, gap, pairs):
+    got = genomeGraph.DynamicAlnBatch("left" if side == 0 else "right", [a for a, _ in pairs], [b for _, b in pairs], sc, gap)
+    for (alpha, beta), (score, route, i, j) in zip(pairs, got):
+        es, er, ei, ej = oracle.gsw_extend(side, sc, gap, alpha, beta)
+        assert (score, i, j) == (es, ei, ej), (side, gap, len(alpha), len(beta))
+        assert [(c.RunLength, c.Op) for c in route] == [(r, cigar.from_col(o)) for r, o in er]
+    return got
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("side", [0, 1])
+def test_gsw_gpu_maximum_size(gpu_lib, side):
+    """one 4095 x 4095 pair, the largest the packed maximum takes: identical but for a few substitutions, so that the maximum sits in
+    the last column, where the packed column key (4095 - j) is 0"""
+    rng = np.random.default_rng(62)
+    alpha = rng.integers(0, 4, size=4095).astype(np.uint8)
+    beta = alpha.copy()
+    for p in (7, 1000, 2047, 2048, 4000):
+        beta[p] = (beta[p] + 1) % 4
+    assert (4095 + 4095 + 2) * 63 < (1 << 19)
+    got = _check_gpu_mx(side, SMALL_MX, -63, [(alpha, beta)])
+    if side == 1:
+        assert got[0][2:] == (4095, 4095)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("side", [0, 1])
+def test_gsw_gpu_strip_and_word_boundaries(gpu_lib, side):
+    """target lengths around the 160-row strips, read lengths around the 16-column words, on related sequences: the read is a copy with
+    errors of the target's anchored end (RightDynamicAln starts at (0, 0), LeftDynamicAln ends at (n, m))"""
+    rng = np.random.default_rng(63 + side)
+    pairs = []
+    for n in (1, 159, 160, 161, 319, 320, 321):
+        for m in (1, 15, 16, 17, 31, 32, 33):
+            alpha = rng.integers(0, 4, size=n).astype(np.uint8)
+            part = alpha[:m + 3] if side == 1 else alpha[max(n - m - 3, 0):]
+            beta = common.mutate(rng, part, 0.06, 0.04)
+            beta = beta[:m] if side == 1 else beta[max(len(beta) - m, 0):]
+            beta = np.concatenate([beta, rng.integers(0, 4, size=m - len(beta)).astype(np.uint8)])
+            assert (len(alpha), len(beta)) == (n, m)
+            pairs.append((alpha, beta))
+    _check_gpu(side, "HumanChimpTwo", -600, pairs)
+
+
+UNIT_MX = [[0 if 4 in (a, b) else (1 if a == b else -1) for b in range(5)] for a in range(5)]  # match +1, mismatch -1, N 0
+
+
+@pytest.mark.gpu
+def test_gsw_gpu_right_cross_strip_tie(gpu_lib):
+    """RightDynamicAln keeps the FIRST maximum in row-major order (`>`, search.go:296).  A x p + (C against G) x q + A x q with match +1,
+    mismatch -1, gap -1: the score reaches p at (p, p), falls to p - q and is p again at (p + 2q, p + 2q).  With 160-row strips the two
+    cells lie in strips 0 and 1 (p = 100, q = 100), both in strip 1 (p = 170, q = 50), in strips 1 and 2 (p = 170, q = 100)."""
+    pairs = []
+    for p, q in ((100, 100), (170, 50), (170, 100)):
+        alpha = np.concatenate([np.zeros(p, np.uint8), np.full(q, 1, np.uint8), np.zeros(q, np.uint8)])
+        beta = np.concatenate([np.zeros(p, np.uint8), np.full(q, 2, np.uint8), np.zeros(q, np.uint8)])
+        pairs.append((alpha, beta))
+    got = _check_gpu_mx(1, UNIT_MX, -1, pairs)
+    assert [(g[0], g[2], g[3]) for g in got] == [(100, 100, 100), (170, 170, 170), (170, 170, 170)]
+    _check_gpu_mx(0, UNIT_MX, -1, pairs)
+
+
 @pytest.mark.gpu
 def test_gsw_gpu_carry_over_and_single(gpu_lib):
     sc = MX["HumanChimpTwo"]
