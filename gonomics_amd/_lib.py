@@ -21,7 +21,8 @@ EXPORTS = ["gnx_device_count", "gnx_init", "gnx_shutdown", "gnx_last_error", "gn
            "gnx_seed_index_build", "gnx_seed_index_set", "gnx_seed_find_batch", "gnx_seed_index_set_gen", "gnx_seed_find_batch_gen", "gnx_gsw_graph_create", "gnx_gsw_graph_free", "gnx_gsw_map_reads", "gnx_debug_occupy", "gnx_debug_counter", "gnx_reference_info",
            "gnx_score_batch", "gnx_score_batch_windows", "gnx_score_batch_by_offset", "gnx_score_batch_device",
            "gnx_locate_batch", "gnx_locate_batch_windows", "gnx_locate_batch_by_offset",
-           "gnx_affine_gap_chunk_score_batch", "gnx_multiple_affine_gap_score_batch"]
+           "gnx_affine_gap_chunk_score_batch", "gnx_multiple_affine_gap_score_batch",
+           "gnx_best_of_by_offset", "gnx_best_of_windows"]
 
 
 class GnxCigar(ctypes.Structure):
@@ -120,6 +121,10 @@ def lib():
         L.gnx_locate_batch_windows.restype = ctypes.c_int
         L.gnx_locate_batch_by_offset.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, c_p, c_p, c_p, c_p, c_p]
         L.gnx_locate_batch_by_offset.restype = ctypes.c_int
+        L.gnx_best_of_by_offset.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_p)]
+        L.gnx_best_of_by_offset.restype = ctypes.c_int
+        L.gnx_best_of_windows.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, c_p, c_p, i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_p)]
+        L.gnx_best_of_windows.restype = ctypes.c_int
         L.gnx_seed_index_build.argtypes = [c_p, c_p, i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(i64)]
         L.gnx_seed_index_build.restype = ctypes.c_int
         L.gnx_seed_index_set.argtypes = [c_p, c_p, i64, c_p, c_p, i64, ctypes.c_int]
@@ -411,6 +416,40 @@ def locate_batch(params, targets, queries):
     ends = np.zeros(max(n, 1), dtype=np.int64)
     check(L.gnx_locate_batch(ctypes.byref(params), n, t_cat.ctypes.data, t_off.ctypes.data, q_cat.ctypes.data, q_off.ctypes.data, scores.ctypes.data, ends.ctypes.data))
     return scores[:n], ends[:n]
+
+
+# ---- best of K on both strands (gnx_best_of_*): score every candidate, keep the first maximum, align the winners ----
+def _best_of(params, read_cat, read_off, target, cand_off, cand_start, cand_len, cand_strand, cigar, target_end):
+    L = lib()
+    read_cat, read_off, cand_off = _u8(read_cat), _i64(read_off), _i64(cand_off)
+    cand_start, cand_len, cand_strand = _i64(cand_start), _i64(cand_len), _u8(cand_strand)
+    n, nc = int(read_off.shape[0]) - 1, int(cand_start.shape[0])
+    best = np.zeros(max(n, 1), dtype=np.int32)
+    scores, ends, cand = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(nc, 1), dtype=np.int64)
+    if target_end is None:
+        target_end = params.mode == GNX_AFFINE_GAP_LOCAL
+    ops_p, off_p = ctypes.c_void_p(), ctypes.c_void_p()
+    tail = [cand_off.ctypes.data, cand_start.ctypes.data, cand_len.ctypes.data, cand_strand.ctypes.data, best.ctypes.data, scores.ctypes.data,
+            ends.ctypes.data if target_end else None, cand.ctypes.data, ctypes.byref(ops_p) if cigar else None, ctypes.byref(off_p) if cigar else None]
+    if target is None:
+        check(L.gnx_best_of_by_offset(ctypes.byref(params), n, read_cat.ctypes.data, read_off.ctypes.data, *tail))
+    else:
+        target = _u8(target)
+        check(L.gnx_best_of_windows(ctypes.byref(params), n, read_cat.ctypes.data, read_off.ctypes.data, target.ctypes.data, target.shape[0], *tail))
+    ops, off = _take(ops_p, off_p, n) if cigar else (None, None)
+    return best[:n], scores[:n], (ends[:n] if target_end else None), cand[:nc], ops, off
+
+
+def best_of_by_offset(params, read_cat, read_off, cand_off, cand_start, cand_len, cand_strand, cigar=True, target_end=None):
+    """gnx_best_of_by_offset: reads against candidate windows (cand_start, cand_len, cand_strand) of the resident reference, candidates
+    of read r at cand_off[r] .. cand_off[r + 1].  Returns (best[int32], scores, target_ends or None, cand_scores, ops or None, off or
+    None); target_end=None asks for the ends exactly in GNX_AFFINE_GAP_LOCAL."""
+    return _best_of(params, read_cat, read_off, None, cand_off, cand_start, cand_len, cand_strand, cigar, target_end)
+
+
+def best_of_windows(params, read_cat, read_off, target_buf, cand_off, cand_start, cand_len, cand_strand, cigar=True, target_end=None):
+    """gnx_best_of_windows: the same with the windows taken from target_buf."""
+    return _best_of(params, read_cat, read_off, target_buf, cand_off, cand_start, cand_len, cand_strand, cigar, target_end)
 
 
 def _chunk_pairs(alphas, betas):

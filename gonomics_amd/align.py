@@ -205,6 +205,35 @@ def AlignBestOf(params, reads, candidates):
     return [(best[r], int(scores[r]), _to_route(ops[off[r]:off[r + 1]])) for r in range(len(reads))]
 
 
+def MapBestOf(params, reads, candidates, cigar=True):
+    """Best of K on both strands in ONE device call (gnx_best_of_*): candidates[r] is a list of (start, len, strand) windows of the
+    resident reference (_lib.set_reference), or of (target_bases, strand); strand 1 = the read's reverse complement.  Global modes
+    align the read (alpha) to the window (beta); GNX_AFFINE_GAP_LOCAL aligns the read as the query to the window as the target.
+    Returns [(best_index, score, route_or_None, target_end_or_None, cand_scores), ...]: per read the first maximum in candidate
+    order with the score and route AlignBatch gives for that pair (route None with cigar=False), the target end in local mode, and
+    every candidate's score.  A read without candidates gets (-1, 0, [] or None, 0 or None, [])."""
+    if not reads:
+        return []
+    counts = [len(c) for c in candidates]
+    flat = [c for cs in candidates for c in cs]
+    resident = bool(flat) and len(flat[0]) == 3
+    r_cat, r_off = _lib._cat(list(reads))
+    c_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    try:
+        if resident or not flat:
+            args = ([w[0] for w in flat], [w[1] for w in flat], [w[2] for w in flat])
+            out = _lib.best_of_by_offset(params, r_cat, r_off, c_off, *args, cigar=cigar) if flat else \
+                _lib.best_of_windows(params, r_cat, r_off, np.zeros(1, np.uint8), c_off, [], [], [], cigar=cigar)
+        else:
+            t_cat, t_off = _lib._cat([w[0] for w in flat])
+            out = _lib.best_of_windows(params, r_cat, r_off, t_cat[:-1], c_off, t_off[:-1], np.diff(t_off), [w[1] for w in flat], cigar=cigar)
+    except _lib.GnxError as e:
+        _raise(e)
+    best, scores, ends, cand, ops, off = out
+    return [(int(best[r]), int(scores[r]), _to_route(ops[off[r]:off[r + 1]]) if cigar else None, int(ends[r]) if ends is not None else None,
+             [int(x) for x in cand[c_off[r]:c_off[r + 1]]]) for r in range(len(reads))]
+
+
 def AffineGapChunk(alpha, beta, scores, gapOpen, gapExtend, chunkSize):
     """align.AffineGapChunk (/root/reference/align/affineGap_highMem.go:227-268)."""
     try:

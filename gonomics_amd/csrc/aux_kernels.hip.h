@@ -1,4 +1,4 @@
-// aux_kernels.hip.h -- N1 score matrices, run scaling, exclusive scan of the run counts
+// aux_kernels.hip.h -- N1 score matrices, run scaling, exclusive scan of the run counts, window unpacking, the best-of-K helpers
 // Part of libgonomics_align_hip.so; included by gnx_align.hip (one translation unit).  See DESIGN.md section 4.
 #pragma once
 #include "gnx_common.hip.h"
@@ -325,6 +325,48 @@ __global__ __launch_bounds__(256) void cigar_target_end_kernel(const gnx_cigar *
     int64_t e = target_len[p];
     if (off[p + 1] > off[p]) { const gnx_cigar last = ops[off[p + 1] - 1]; if (last.op == GNX_COL_D) e -= last.run_length; }
     end[p] = e;
+}
+
+// ---- gnx_best_of_*: reverse complements, per read the first maximum of its candidates, the winners' window tables ---------------
+// rc[read_off[r] + k] = complement of reads[read_off[r + 1] - 1 - k]: A <-> T, C <-> G, N stays N, a byte >= 5 stays what it is (and
+// still makes GNX_EBASE) -- dna.ReverseComplement on upper-case bases.  One wave per read, four reads per workgroup.
+__global__ __launch_bounds__(256) void revcomp_reads_kernel(const uint8_t *__restrict__ reads, const int64_t *__restrict__ read_off, int64_t n_reads,
+                                                            uint8_t *__restrict__ rc) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n_reads; r += (int64_t)gridDim.x * 4) {
+        const int64_t b = read_off[r], e = read_off[r + 1];
+        for (int64_t k = b + lane; k < e; k += 64) {
+            const uint8_t v = reads[e - 1 - (k - b)];
+            rc[k] = v < 4 ? (uint8_t)(3 - v) : v;
+        }
+    }
+}
+// best[r] = index, among the candidates cand_off[r] .. cand_off[r + 1] of read r, of the first maximum of score (ties: the lowest
+// index); best_score / best_end = that candidate's values (end may be nullptr).  No candidates: -1, 0, 0.  One thread per read.
+__global__ __launch_bounds__(256) void first_max_kernel(const int64_t *__restrict__ score, const int64_t *__restrict__ end, const int64_t *__restrict__ cand_off,
+                                                        int64_t n_reads, int32_t *__restrict__ best, int64_t *__restrict__ best_score, int64_t *__restrict__ best_end) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_reads) return;
+    const int64_t c0 = cand_off[r], c1 = cand_off[r + 1];
+    int64_t at = -1, s = 0;
+    for (int64_t c = c0; c < c1; c++) {
+        const int64_t v = score[c];
+        if (at < 0 || v > s) { at = c; s = v; }
+    }
+    best[r] = at < 0 ? -1 : (int32_t)(at - c0);
+    best_score[r] = s;
+    if (end) best_end[r] = at < 0 ? 0 : end[at];
+}
+// The pair tables of the CIGAR stage: winner w is read win_read[w] with its candidate best[read]; the read's start is the one the
+// score stage used (cand_rstart: in the forward or in the reverse-complement copy), the window's start is the candidate's.
+__global__ __launch_bounds__(256) void winner_tables_kernel(const int32_t *__restrict__ best, const int64_t *__restrict__ cand_off, const int64_t *__restrict__ win_read,
+                                                            const int64_t *__restrict__ cand_rstart, const int64_t *__restrict__ cand_wstart, int64_t n_win,
+                                                            int64_t *__restrict__ win_rstart, int64_t *__restrict__ win_wstart) {
+    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= n_win) return;
+    const int64_t r = win_read[w], c = cand_off[r] + best[r];
+    win_rstart[w] = cand_rstart[c];
+    win_wstart[w] = cand_wstart[c];
 }
 
 } // namespace

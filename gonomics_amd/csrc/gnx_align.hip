@@ -137,6 +137,7 @@ struct Ctx {
     DevBuf ss_len, res_end, gat_end; // gnx_locate_*: target lengths for the end read off a CIGAR, the ends of a host job, their gather on device 0
     DevBuf ss_plans, ss_rowbuf, ss_prog, ss_err, ss_off; // the score-only sweep (score_sweep.hip.h): plans, hand-over rows, progress / claim words, error flags; offsets of a dropped CIGAR
     DevBuf sd_keys, sd_locs, sd_nodes, sd_node_off, sd_word_off, sd_words, sd_tmp[8];
+    DevBuf bo[13]; // gnx_best_of_* (gnx_host.hip.h, BO_*): reads + reverse complements, candidate tables and scores, per-read winners, the winners' tables
     int64_t sd_n = -1, sd_nodes_n = 0; int sd_seed_len = 0;
     PinBuf h_plans; // host-side plans of the general path
     PinBuf st_a[2], st_as[2], st_b[2], st_bs[2];
@@ -2729,6 +2730,7 @@ void gnx_shutdown(void) {
                           &c.ref, &c.ref_flag, &c.ref_rank, &c.ref_exc, &c.unpk_b, &c.unpk_off, &c.cl_bases, &c.sc_prof_a, &c.sc_prof_b, &c.mega_rows, &c.mega_state, &c.farm, &c.mega_arena, &c.gat_score, &c.gat_off, &c.gat_ops, &c.ss_plans, &c.ss_rowbuf, &c.ss_prog, &c.ss_err, &c.ss_off, &c.ss_len, &c.res_end, &c.gat_end, &c.sd_keys, &c.sd_locs, &c.sd_nodes, &c.sd_node_off, &c.sd_word_off, &c.sd_words,
                           &c.sd_tmp[0], &c.sd_tmp[1], &c.sd_tmp[2], &c.sd_tmp[3], &c.sd_tmp[4], &c.sd_tmp[5], &c.sd_tmp[6], &c.sd_tmp[7]};
         for (DevBuf *b : bufs) b->release();
+        for (DevBuf &b : c.bo) b.release();
         PinBuf *pins[] = {&c.h_plans, &c.st_a[0], &c.st_a[1], &c.st_as[0], &c.st_as[1], &c.st_b[0], &c.st_b[1], &c.st_bs[0], &c.st_bs[1]};
         for (PinBuf *b : pins) b->release();
         c.fpc_ptr = nullptr; c.ref_len = -1; c.sd_n = -1;
@@ -2873,6 +2875,24 @@ int gnx_locate_batch_by_offset(const gnx_params *p, int64_t n_pairs, const uint8
     std::vector<int64_t> ql((size_t)n_pairs);
     for (int64_t q = 0; q < n_pairs; q++) ql[(size_t)q] = query_off[q + 1] - query_off[q];
     return run_host_sharded(p, n_pairs, query_cat, query_off[n_pairs], query_off, ql.data(), nullptr, 0, ref_start, ref_len, out_score, nullptr, nullptr, true, out_target_end, 2);
+}
+
+/* ---- best of K on both strands: score every candidate, keep the first maximum, align the winners (gnx_align.h) ---- */
+int gnx_best_of_by_offset(const gnx_params *p, int64_t n_reads, const uint8_t *read_cat, const int64_t *read_off,
+                          const int64_t *cand_off, const int64_t *cand_start, const int64_t *cand_len, const uint8_t *cand_strand,
+                          int32_t *out_best, int64_t *out_score, int64_t *out_target_end, int64_t *out_cand_score, gnx_cigar **out_ops, int64_t **out_ops_off) {
+    std::lock_guard<std::mutex> api(g_api_mu);
+    g_err[0] = 0;
+    return run_best_of(p, n_reads, read_cat, read_off, true, nullptr, 0, cand_off, cand_start, cand_len, cand_strand, out_best, out_score, out_target_end, out_cand_score, out_ops, out_ops_off);
+}
+
+int gnx_best_of_windows(const gnx_params *p, int64_t n_reads, const uint8_t *read_cat, const int64_t *read_off, const uint8_t *target_buf, int64_t target_buf_len,
+                        const int64_t *cand_off, const int64_t *cand_start, const int64_t *cand_len, const uint8_t *cand_strand,
+                        int32_t *out_best, int64_t *out_score, int64_t *out_target_end, int64_t *out_cand_score, gnx_cigar **out_ops, int64_t **out_ops_off) {
+    std::lock_guard<std::mutex> api(g_api_mu);
+    g_err[0] = 0;
+    return run_best_of(p, n_reads, read_cat, read_off, false, target_buf, target_buf_len, cand_off, cand_start, cand_len, cand_strand, out_best, out_score, out_target_end, out_cand_score,
+                       out_ops, out_ops_off);
 }
 
 int gnx_score_batch_device(const gnx_params *p, int64_t n_pairs,

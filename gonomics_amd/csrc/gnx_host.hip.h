@@ -792,4 +792,223 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
     return GNX_OK;
 }
 
+// ---- gnx_best_of_*: reads x candidate windows x strands -> per read the first best candidate and its CIGAR (gnx_align.h) ----------
+// One context (context 0).  The reads go up once; their reverse complements are written behind them on the device, so a candidate's
+// read is a window (start, len) of that buffer like any other alpha window, and both stages run the twins' own device drivers:
+//   score stage   score_or_fallback over the candidates, in sub-batches of GNX_HOST_SUB pairs (a read's candidates may straddle a cut)
+//   selection     first_max_kernel; only best[] (4 bytes per read) comes back: the host plans the CIGAR stage from the winners' lengths
+//   CIGAR stage   winner_tables_kernel builds the winners' start tables from what is resident, run_device aligns them in sub-batches
+// Nothing is written to the caller's outputs before both stages have succeeded.
+enum { BO_READS, BO_ROFF, BO_COFF, BO_WREAD, BO_RS, BO_WS, BO_CSCORE, BO_CEND, BO_BEST, BO_BSCORE, BO_BEND, BO_WR, BO_WW, BO_COUNT };
+static_assert(BO_COUNT == sizeof(Ctx::bo) / sizeof(DevBuf), "Ctx::bo holds one buffer per BO_* index");
+int run_best_of(const gnx_params *prm, int64_t n_reads, const uint8_t *read_cat, const int64_t *read_off, bool resident, const uint8_t *t_buf, int64_t t_len,
+                const int64_t *cand_off, const int64_t *cand_start, const int64_t *cand_len, const uint8_t *cand_strand,
+                int32_t *out_best, int64_t *out_score, int64_t *out_end, int64_t *out_cand_score, gnx_cigar **out_ops, int64_t **out_ops_off) {
+    const auto t_entry = std::chrono::steady_clock::now();
+    // ---- argument checks: everything that needs no device ----
+    if (!prm || n_reads < 0 || !read_off || !cand_off || !out_best || !out_score || t_len < 0) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if ((out_ops == nullptr) != (out_ops_off == nullptr)) { set_err("out_ops and out_ops_off must be given together%s", ""); return GNX_EINVAL; }
+    if (prm->mode < GNX_AFFINE_GAP || prm->mode > GNX_CONST_GAP_HIGHMEM) { set_err("unknown mode %s%lld", "", (long long)prm->mode); return GNX_EINVAL; }
+    const bool local = prm->mode == GNX_AFFINE_GAP_LOCAL, cigars = out_ops != nullptr;
+    if (out_end && !local) { set_err("out_target_end is defined for GNX_AFFINE_GAP_LOCAL only%s", ""); return GNX_EINVAL; }
+    if (read_off[0] < 0 || cand_off[0] != 0) { set_err("read_off must start at >= 0 and cand_off at 0%s", ""); return GNX_EINVAL; }
+    for (int64_t r = 0; r < n_reads; r++)
+        if (read_off[r + 1] < read_off[r] || cand_off[r + 1] < cand_off[r]) { set_err("decreasing offsets at read %s%lld", "", (long long)r); return GNX_EINVAL; }
+    const int64_t n_cand = cand_off[n_reads], r_lo = read_off[0], r_total = read_off[n_reads] - r_lo;
+    if ((n_cand > 0 && (!cand_start || !cand_len || !cand_strand)) || (r_total > 0 && !read_cat) || (!resident && t_len > 0 && !t_buf)) { set_err("null table or buffer%s", ""); return GNX_EINVAL; }
+    for (int64_t q = 0; q < n_cand; q++) {
+        if (cand_strand[q] > 1) { set_err("strand byte > 1 at candidate %s%lld", "", (long long)q); return GNX_EINVAL; }
+        if (cand_start[q] < 0 || cand_len[q] < 0 || (!resident && cand_len[q] > t_len - cand_start[q])) { set_err("window out of bounds at candidate %s%lld", "", (long long)q); return GNX_EINVAL; }
+    }
+    Ctx &c = ctx_at(0);
+    CtxScope scope(c);
+    int rc;
+    if ((rc = ensure_init())) return rc;
+    g_transport = 0; g_bcast_ms = 0;
+    if (resident) {
+        if (c.ref_len < 0) { set_err("no resident reference: call gnx_set_reference first%s", ""); return GNX_EINVAL; }
+        for (int64_t q = 0; q < n_cand; q++)
+            if (cand_len[q] > c.ref_len - cand_start[q]) { set_err("window out of bounds at candidate %s%lld", "", (long long)q); return GNX_EINVAL; }
+    }
+    hipStream_t st = c.own_stream;
+    int64_t sub = 131072;
+    if (const char *e = getenv("GNX_HOST_SUB")) sub = (std::max<int64_t>(atoll(e), 8) + 7) & ~(int64_t)7;
+    auto cut = [&](int64_t n) { const int64_t K0 = (n + sub - 1) / sub; return (((n + K0 - 1) / K0) + 7) & ~(int64_t)7; }; // equal sub-batches, whole waves (run_host_job)
+
+    // ---- host tables: per candidate its read as a window of [reads | reverse complements]; the reads that have candidates ----
+    std::vector<int64_t> h_rs((size_t)n_cand), h_rlen((size_t)n_cand), win_read;
+    for (int64_t r = 0; r < n_reads; r++) {
+        for (int64_t q = cand_off[r]; q < cand_off[r + 1]; q++) { h_rs[(size_t)q] = read_off[r] - r_lo + (cand_strand[q] ? r_total : 0); h_rlen[(size_t)q] = read_off[r + 1] - read_off[r]; }
+        if (cigars && cand_off[r + 1] > cand_off[r]) win_read.push_back(r);
+    }
+    const int64_t n_win = (int64_t)win_read.size();
+    std::vector<int64_t> h_roff;
+    if (r_lo) { h_roff.resize((size_t)n_reads + 1); for (int64_t r = 0; r <= n_reads; r++) h_roff[(size_t)r] = read_off[r] - r_lo; }
+
+    // ---- uploads: the reads once, 16 bytes of table per candidate, the offsets ----
+    DevBuf *bo = c.bo;
+    const size_t nr = (size_t)std::max<int64_t>(n_reads, 1), ncd = (size_t)std::max<int64_t>(n_cand, 1);
+    if ((rc = bo[BO_READS].ensure((size_t)r_total * 2 + 16)) || (rc = bo[BO_ROFF].ensure((nr + 1) * 8)) || (rc = bo[BO_COFF].ensure((nr + 1) * 8)) ||
+        (rc = bo[BO_RS].ensure(ncd * 8)) || (rc = bo[BO_WS].ensure(ncd * 8)) || (rc = bo[BO_CSCORE].ensure(ncd * 8)) || (local && (rc = bo[BO_CEND].ensure(ncd * 8))) ||
+        (rc = bo[BO_BEST].ensure(nr * 4)) || (rc = bo[BO_BSCORE].ensure(nr * 8)) || (rc = bo[BO_BEND].ensure(nr * 8))) return rc;
+    if (!resident && (rc = c.in_b.ensure((size_t)t_len + 16))) return rc;
+    uint8_t *d_reads = (uint8_t *)bo[BO_READS].p;
+    const uint8_t *d_tbuf = resident ? (const uint8_t *)c.ref.p : (const uint8_t *)c.in_b.p;
+    int64_t *d_rs = (int64_t *)bo[BO_RS].p, *d_ws = (int64_t *)bo[BO_WS].p, *d_cscore = (int64_t *)bo[BO_CSCORE].p, *d_cend = local ? (int64_t *)bo[BO_CEND].p : nullptr;
+    if (n_reads > 0 && n_cand > 0) {
+        if (r_total) HIPCHK(hipMemcpyAsync(d_reads, read_cat + r_lo, (size_t)r_total, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(bo[BO_ROFF].p, r_lo ? h_roff.data() : read_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(bo[BO_COFF].p, cand_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_rs, h_rs.data(), (size_t)n_cand * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_ws, cand_start, (size_t)n_cand * 8, hipMemcpyHostToDevice, st));
+        if (!resident && t_len) HIPCHK(hipMemcpyAsync(c.in_b.p, t_buf, (size_t)t_len, hipMemcpyHostToDevice, st));
+        if (r_total) {
+            hipLaunchKernelGGL(revcomp_reads_kernel, dim3((unsigned)std::min<int64_t>((n_reads + 3) / 4, 1 << 20)), dim3(256), 0, st, (const uint8_t *)d_reads, (const int64_t *)bo[BO_ROFF].p, n_reads, d_reads + r_total);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipStreamSynchronize(st)); // (the sources are pageable memory of the caller and locals of this call: no return while a copy may still read them)
+    }
+    // windows of the packed reference as bytes in c.in_b / c.in_bl (AffineGapLocal off the sweep reads its target as the kernels' alpha)
+    auto unpack = [&](const int64_t *d_starts, const int64_t *h_lens, int64_t cnt) -> int {
+        std::vector<int64_t> uoff((size_t)cnt + 1, 0);
+        for (int64_t q = 0; q < cnt; q++) uoff[(size_t)q + 1] = uoff[(size_t)q] + h_lens[q];
+        int r;
+        if ((r = c.in_b.ensure((size_t)uoff[(size_t)cnt] + 64)) || (r = c.in_bl.ensure((size_t)(cnt + 1) * 8))) return r;
+        KParams ukp;
+        memset(&ukp, 0, sizeof(ukp));
+        ukp.b2 = (const unsigned *)c.ref.p; ukp.bflag = (const unsigned long long *)c.ref_flag.p; ukp.brank = (const unsigned *)c.ref_rank.p; ukp.bexc = (const unsigned long long *)c.ref_exc.p;
+        HIPCHK(hipMemcpyAsync(c.in_bl.p, uoff.data(), (size_t)(cnt + 1) * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st)); // (uoff is a local)
+        hipLaunchKernelGGL(unpack_windows_kernel, dim3((unsigned)cnt), dim3(256), 0, st, ukp, d_starts, (const int64_t *)c.in_bl.p, (int)cnt, (uint8_t *)c.in_b.p);
+        HIPCHK(hipGetLastError());
+        return GNX_OK;
+    };
+
+    // ---- score stage ----
+    gnx_timing tsum = {};
+    if (n_cand > 0) {
+        const int64_t size = cut(n_cand);
+        for (int64_t b = 0; b < n_cand; b += size) {
+            const int64_t cnt = std::min(size, n_cand - b);
+            const int64_t *h_rl = h_rlen.data() + b, *h_wl = cand_len + b;
+            if (!local) { // alpha = the read or its reverse complement, beta = the window
+                c.beta_packed = resident;
+                rc = score_or_fallback(c, prm, cnt, d_reads, d_rs + b, d_tbuf, d_ws + b, h_rl, h_wl, d_cscore + b, st);
+                c.beta_packed = false;
+            } else if (!resident) { // target (alpha) = the window, query (beta) = the read
+                rc = score_or_fallback(c, prm, cnt, d_tbuf, d_ws + b, d_reads, d_rs + b, h_wl, h_rl, d_cscore + b, st, d_cend + b);
+            } else { // the local sweep reads its target packed (the kernels' beta); only its fallback needs bytes
+                c.beta_packed = true;
+                rc = run_score_sweep(prm, cnt, d_reads, d_rs + b, d_tbuf, d_ws + b, h_rl, h_wl, d_cscore + b, st, d_cend + b, true);
+                c.beta_packed = false;
+                if (rc == -1 && (rc = unpack(d_ws + b, h_wl, cnt)) == GNX_OK)
+                    rc = score_or_fallback(c, prm, cnt, (const uint8_t *)c.in_b.p, (const int64_t *)c.in_bl.p, d_reads, d_rs + b, h_wl, h_rl, d_cscore + b, st, d_cend + b, false);
+            }
+            if (rc) return rc;
+            tsum.fill_ms += c.timing.fill_ms; tsum.traceback_ms += c.timing.traceback_ms; tsum.total_ms += c.timing.total_ms; tsum.cells += c.timing.cells;
+            tsum.n_launches += c.timing.n_launches; tsum.trace_bytes += c.timing.trace_bytes; tsum.dominant_ms += c.timing.dominant_ms;
+            tsum.dominant_launches += c.timing.dominant_launches; tsum.fast_path = std::max(tsum.fast_path, c.timing.fast_path);
+        }
+        hipLaunchKernelGGL(first_max_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, st, (const int64_t *)d_cscore, (const int64_t *)d_cend, (const int64_t *)bo[BO_COFF].p,
+                           n_reads, (int32_t *)bo[BO_BEST].p, (int64_t *)bo[BO_BSCORE].p, (int64_t *)bo[BO_BEND].p);
+        HIPCHK(hipGetLastError());
+    }
+
+    // ---- CIGAR stage: the winners only ----
+    std::vector<int32_t> h_best((size_t)n_reads, -1);
+    int64_t total = 0;
+    if (n_win > 0) {
+        if ((rc = bo[BO_WREAD].ensure((size_t)n_win * 8)) || (rc = bo[BO_WR].ensure((size_t)n_win * 8)) || (rc = bo[BO_WW].ensure((size_t)n_win * 8)) ||
+            (rc = c.res_score.ensure((size_t)n_win * 8)) || (rc = c.res_off.ensure((size_t)(n_win + 1) * 8))) return rc;
+        int64_t *d_wr = (int64_t *)bo[BO_WR].p, *d_ww = (int64_t *)bo[BO_WW].p;
+        HIPCHK(hipMemcpyAsync(bo[BO_WREAD].p, win_read.data(), (size_t)n_win * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(winner_tables_kernel, dim3((unsigned)((n_win + 255) / 256)), dim3(256), 0, st, (const int32_t *)bo[BO_BEST].p, (const int64_t *)bo[BO_COFF].p,
+                           (const int64_t *)bo[BO_WREAD].p, (const int64_t *)d_rs, (const int64_t *)d_ws, n_win, d_wr, d_ww);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h_best.data(), bo[BO_BEST].p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, st)); // all that crosses between the stages
+        HIPCHK(hipStreamSynchronize(st));
+        std::vector<int64_t> w_rlen((size_t)n_win), w_wlen((size_t)n_win);
+        int64_t worst = 0;
+        for (int64_t w = 0; w < n_win; w++) {
+            const int64_t r = win_read[(size_t)w];
+            w_rlen[(size_t)w] = read_off[r + 1] - read_off[r]; w_wlen[(size_t)w] = cand_len[cand_off[r] + h_best[(size_t)r]];
+            worst += w_rlen[(size_t)w] + w_wlen[(size_t)w] + 1;
+        }
+        const int64_t size = cut(n_win);
+        if ((rc = grow_ops(c, 0, std::max<int64_t>(std::min<int64_t>(worst, std::max<int64_t>((int64_t)1 << 20, 64 * std::min(n_win, size))), 1), st))) return rc;
+        gnx_timing tal = {};
+        for (int64_t b = 0; b < n_win; b += size) {
+            const int64_t cnt = std::min(size, n_win - b);
+            const int64_t *h_rl = w_rlen.data() + b, *h_wl = w_wlen.data() + b;
+            if (local && resident && (rc = unpack(d_ww + b, h_wl, cnt))) return rc; // only the winners' windows
+            int64_t tot = 0;
+            for (int attempt = 0;; attempt++) {
+                const int64_t cap = (int64_t)(c.res_ops.cap / sizeof(gnx_cigar)) - total;
+                int64_t *d_sc = (int64_t *)c.res_score.p + b, *d_off = (int64_t *)c.res_off.p + b;
+                gnx_cigar *d_ops = (gnx_cigar *)c.res_ops.p + total;
+                if (!local) {
+                    c.beta_packed = resident;
+                    rc = run_device(prm, cnt, d_reads, d_wr + b, d_tbuf, d_ww + b, h_rl, h_wl, d_sc, d_ops, cap, d_off, &tot, st);
+                    c.beta_packed = false;
+                } else if (resident) rc = run_device(prm, cnt, (const uint8_t *)c.in_b.p, (const int64_t *)c.in_bl.p, d_reads, d_wr + b, h_wl, h_rl, d_sc, d_ops, cap, d_off, &tot, st);
+                else rc = run_device(prm, cnt, d_tbuf, d_ww + b, d_reads, d_wr + b, h_wl, h_rl, d_sc, d_ops, cap, d_off, &tot, st);
+                if (rc != GNX_ECAPACITY || attempt >= 8) break;
+                const int64_t left = (n_win - b + cnt - 1) / cnt;
+                if ((rc = grow_ops(c, total, total + tot * std::min<int64_t>(left, 4) + 1024, st))) break;
+            }
+            if (rc) return rc;
+            tal.total_ms += c.timing.total_ms;
+            if (total > 0) { // offsets of a sub-batch start at 0
+                hipLaunchKernelGGL(add_offset_kernel, dim3((unsigned)((cnt + 1 + 255) / 256)), dim3(256), 0, st, (int64_t *)c.res_off.p + b, cnt + 1, total);
+                HIPCHK(hipGetLastError());
+            }
+            total += tot;
+        }
+        tsum.total_ms += tal.total_ms;
+    }
+
+    // ---- results: pinned CIGAR arrays (gnx_free), the rest into the caller's arrays ----
+    const auto t_fetch = std::chrono::steady_clock::now();
+    gnx_cigar *ops = nullptr;
+    int64_t *off = nullptr;
+    if (cigars) {
+        ops = (gnx_cigar *)g_pool.get((size_t)std::max<int64_t>(total, 1) * sizeof(gnx_cigar));
+        off = (int64_t *)g_pool.get((size_t)(n_reads + 1) * 8);
+        if (!ops || !off) { if (ops) g_pool.put(ops); if (off) g_pool.put(off); set_err("pinned host allocation failed%s", ""); return GNX_ENOMEM; }
+    }
+    std::vector<int64_t> w_score((size_t)n_win), w_off((size_t)n_win + 1, 0), h_bscore((size_t)n_reads, 0), h_bend((size_t)n_reads, 0), h_cscore(out_cand_score ? (size_t)n_cand : 0);
+    auto fetch = [&]() -> int {
+        if (n_cand > 0 && n_reads > 0) {
+            if (!n_win) HIPCHK(hipMemcpyAsync(h_best.data(), bo[BO_BEST].p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(h_bscore.data(), bo[BO_BSCORE].p, (size_t)n_reads * 8, hipMemcpyDeviceToHost, st));
+            if (out_end) HIPCHK(hipMemcpyAsync(h_bend.data(), bo[BO_BEND].p, (size_t)n_reads * 8, hipMemcpyDeviceToHost, st));
+            if (out_cand_score) HIPCHK(hipMemcpyAsync(h_cscore.data(), d_cscore, (size_t)n_cand * 8, hipMemcpyDeviceToHost, st));
+        }
+        if (n_win) {
+            HIPCHK(hipMemcpyAsync(w_score.data(), c.res_score.p, (size_t)n_win * 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(w_off.data(), c.res_off.p, (size_t)(n_win + 1) * 8, hipMemcpyDeviceToHost, st));
+            if (total) HIPCHK(hipMemcpyAsync(ops, c.res_ops.p, (size_t)total * sizeof(gnx_cigar), hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(hipStreamSynchronize(st));
+        return GNX_OK;
+    };
+    if ((rc = fetch())) { if (ops) g_pool.put(ops); if (off) g_pool.put(off); return rc; }
+    for (int64_t r = 0; r < n_reads; r++) { out_best[r] = h_best[(size_t)r]; out_score[r] = h_bscore[(size_t)r]; if (out_end) out_end[r] = h_bend[(size_t)r]; }
+    if (out_cand_score && n_cand > 0) memcpy(out_cand_score, h_cscore.data(), (size_t)n_cand * 8);
+    if (cigars) { // a read without candidates: an empty CIGAR
+        int64_t w = 0;
+        for (int64_t r = 0; r < n_reads; r++) {
+            off[r] = w_off[(size_t)w];
+            if (w < n_win && win_read[(size_t)w] == r) { out_score[r] = w_score[(size_t)w]; w++; }
+        }
+        off[n_reads] = total;
+        *out_ops = ops; *out_ops_off = off;
+    }
+    tsum.fetch_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_fetch).count();
+    tsum.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count();
+    tsum.n_contexts = 1;
+    c.timing = tsum;
+    return GNX_OK;
+}
+
 } // namespace

@@ -41,3 +41,15 @@ def AllToUpper(bases):
     """In-place like the Go version; also returns the array for convenience."""
     bases[:] = _TO_UPPER[bases]
     return bases
+
+
+_COMPLEMENT = np.arange(256, dtype=np.uint8)
+_COMPLEMENT[[A, C, G, T, LowerA, LowerC, LowerG, LowerT]] = (T, G, C, A, LowerT, LowerG, LowerC, LowerA)  # complementArray, dna/modify.go:72
+
+
+def ReverseComplement(bases):
+    """dna.ReverseComplement (dna/modify.go:111), in place like the Go version (the array is also returned): the sequence reversed with
+    A <-> T and C <-> G (upper and lower case); N, n, Gap, Dot and Nil stay what they are.  The device's reverse complement
+    (gnx_best_of_*) is this on the bases an alignment accepts, 0 .. 4."""
+    bases[:] = _COMPLEMENT[bases[::-1]]
+    return bases

@@ -251,6 +251,50 @@ int gnx_locate_batch_windows(const gnx_params *p, int64_t n_pairs,
 int gnx_locate_batch_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *query_cat, const int64_t *query_off,
                                const int64_t *ref_start, const int64_t *ref_len, int64_t *out_score, int64_t *out_target_end);
 
+/* ---- best of K on both strands: what mapping a read needs (an extension, no Go signature) ----------------------------------------- */
+/* Score a read against a handful of candidate windows on either strand, keep the best, produce a CIGAR for that one only and report
+ * every candidate's score.  Reads: read_cat / read_off[n_reads + 1].  Candidates of read r: cand_off[r] .. cand_off[r + 1]
+ * (cand_off[0] = 0, cand_off[n_reads] = n_cand); candidate c = the window (cand_start[c], cand_len[c]) and cand_strand[c] (0: the read
+ * as given, 1: its reverse complement).  _by_offset takes its windows from the resident reference (gnx_set_reference, read packed),
+ * _windows from target_buf.  The reads are uploaded once; reverse complements, the selection and the winners' tables are made on the
+ * device, and between the two stages only out_best (4 bytes per read) comes back -- the host plans the CIGAR stage from it.
+ * Roles, by meaning and the same in both entries (p->scores is indexed [alpha * 5 + beta] as everywhere):
+ *   the four global modes:   alpha = the read or its reverse complement, beta = the window;
+ *   GNX_AFFINE_GAP_LOCAL:    target (alpha) = the window, query (beta) = the read or its reverse complement -- the mapping mode; mind
+ *                            that gnx_align_batch_by_offset has these two the other way round.
+ * Reverse complement: the read reversed with A <-> T and C <-> G; N stays N; a byte >= 5 stays a byte >= 5 and still yields GNX_EBASE
+ * (dna.ReverseComplement, /root/reference/dna/modify.go:111, on upper-case bases).
+ * Contract: every output equals what an existing entry returns on the flattened pair list.
+ *   out_cand_score[c] (may be NULL)  global modes: what gnx_score_batch_windows / _by_offset returns for candidate c's pair; local mode:
+ *                        the score gnx_locate_batch_windows / _by_offset returns for it.
+ *   out_best[r]          index within read r's candidates of the FIRST maximum in candidate order (ties go to the lowest index).  A read
+ *                        without candidates gets out_best = -1, score 0, target end 0 and an empty CIGAR: not an error.
+ *   out_score[r], CIGAR  what gnx_align_batch_windows returns for the winning pair under the roles above (local mode on the resident
+ *                        reference: alpha = the window's bases), reference quirks included, checkersize_* honoured.  *out_ops /
+ *                        (*out_ops_off)[n_reads + 1] as in gnx_align_batch (gnx_free).  out_ops = out_ops_off = NULL: no CIGAR stage,
+ *                        out_score[r] is the winner's candidate score (the same number).
+ *   out_target_end[r] (may be NULL)  GNX_AFFINE_GAP_LOCAL only: what the locate twin returns for the winner; non-NULL in another mode:
+ *                        GNX_EINVAL.
+ * Return codes are those of the twins on the flattened list; GNX_EBASE or GNX_EEMPTY in ANY candidate pair, winner or not, fails the call
+ * before any output is written.  GNX_EINVAL also for: cand_off not starting at 0 or decreasing (read_off decreasing), a strand byte > 1,
+ * a window outside the buffer or the reference, exactly one of out_ops / out_ops_off NULL.  Never GNX_ERANGE.  Without a device:
+ * GNX_EDEVICE, after the argument checks (no CPU fallback).  n_reads == 0 or n_cand == 0: GNX_OK.
+ * Routes: the score stage takes the twins' routes under the twins' conditions (the score sweep, gnx_timing.fast_path 7 / 8;
+ * GNX_SCORE_SWEEP=0 and everything the sweep does not take: the align route with its CIGAR left on the device); the CIGAR stage is the
+ * align driver on the winners (local mode on the resident reference unpacks the winners' windows only).  Both stages are cut into
+ * sub-batches of GNX_HOST_SUB pairs; a read's candidates may straddle a cut.  The call runs on context 0 alone, also after
+ * gnx_init_devices (same results; the other contexts idle).  gnx_get_timing afterwards describes the score stage (fast_path,
+ * fill_ms, dominant_ms, cells = candidate cells); total_ms (device) and host_ms (wall clock) cover both stages. */
+int gnx_best_of_by_offset(const gnx_params *p, int64_t n_reads, const uint8_t *read_cat, const int64_t *read_off,
+                          const int64_t *cand_off, const int64_t *cand_start, const int64_t *cand_len, const uint8_t *cand_strand,
+                          int32_t *out_best, int64_t *out_score, int64_t *out_target_end, int64_t *out_cand_score,
+                          gnx_cigar **out_ops, int64_t **out_ops_off);
+int gnx_best_of_windows(const gnx_params *p, int64_t n_reads, const uint8_t *read_cat, const int64_t *read_off,
+                        const uint8_t *target_buf, int64_t target_buf_len,
+                        const int64_t *cand_off, const int64_t *cand_start, const int64_t *cand_len, const uint8_t *cand_strand,
+                        int32_t *out_best, int64_t *out_score, int64_t *out_target_end, int64_t *out_cand_score,
+                        gnx_cigar **out_ops, int64_t **out_ops_off);
+
 int gnx_get_timing(gnx_timing *out);
 /* Diagnostics (tests only; nothing in the reference corresponds to it): launch n_workgroups workgroups that each hold one CU's whole
  * LDS and spin for `milliseconds` on a stream of their own, and return at once -- the pipelined launches of the library must make

@@ -52,6 +52,11 @@ inline std::string BasesToString(const std::vector<Base> &b) { // dna/convert.go
 inline void AllToUpper(std::vector<Base> &b) { // dna/modify.go:60
     for (auto &x : b) if (x >= LowerA && x <= LowerN) x = (Base)(x - 5);
 }
+inline void ReverseComplement(std::vector<Base> &b) { // dna/modify.go:111 (in place; a byte beyond Nil stays what it is instead of panicking)
+    static const Base comp[13] = {T, G, C, A, N, LowerT, LowerG, LowerC, LowerA, LowerN, Gap, Dot, Nil};
+    std::reverse(b.begin(), b.end());
+    for (auto &x : b) if (x <= Nil) x = comp[x];
+}
 } // namespace dna
 
 namespace align {
@@ -191,6 +196,69 @@ inline std::pair<std::vector<int64_t>, std::vector<int64_t>> LocateBatch(const S
 inline std::pair<int64_t, int64_t> AffineGapLocalEnd(const std::vector<dna::Base> &target, const std::vector<dna::Base> &query, const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend) {
     const auto r = LocateBatch(scores, gapOpen, gapExtend, {target}, {query});
     return {r.first[0], r.second[0]};
+}
+
+// ---- best of K on both strands (gnx_best_of_*; an extension) ----
+// A read against candidate windows on either strand: per read the FIRST best candidate, its score and route, every candidate's score
+// and, for GNX_AFFINE_GAP_LOCAL, the target end.  Global modes: alpha = the read (strand 1: its reverse complement), beta = the
+// window; GNX_AFFINE_GAP_LOCAL: target = the window, query = the read.  A read without candidates gets Best = -1 and nothing else.
+struct RefCandidate { int64_t Start, Len; uint8_t Strand; };                  // a window of the resident reference (gnx_set_reference)
+struct SeqCandidate { std::vector<dna::Base> Target; uint8_t Strand; };       // a window given as bases
+struct BestOf { int32_t Best = -1; int64_t Score = 0, TargetEnd = 0; std::vector<Cigar> Route; std::vector<int64_t> CandScores; };
+namespace detail {
+inline std::vector<BestOf> best_of(const gnx_params &p, const std::vector<std::vector<dna::Base>> &reads, const std::vector<dna::Base> *tcat,
+                                   const std::vector<int64_t> &coff, const std::vector<int64_t> &cstart, const std::vector<int64_t> &clen, const std::vector<uint8_t> &cstrand, bool cigar) {
+    const int64_t n = (int64_t)reads.size();
+    std::vector<int64_t> roff((size_t)n + 1, 0);
+    for (int64_t k = 0; k < n; k++) roff[(size_t)k + 1] = roff[(size_t)k] + (int64_t)reads[(size_t)k].size();
+    std::vector<dna::Base> rcat((size_t)roff[(size_t)n] + 1);
+    for (int64_t k = 0; k < n; k++) std::copy(reads[(size_t)k].begin(), reads[(size_t)k].end(), rcat.begin() + roff[(size_t)k]);
+    const size_t nn = (size_t)std::max<int64_t>(n, 1), nc = std::max<size_t>(cstart.size(), 1);
+    std::vector<int32_t> best(nn, -1);
+    std::vector<int64_t> sc(nn, 0), end(nn, 0), cand(nc, 0);
+    const bool local = p.mode == GNX_AFFINE_GAP_LOCAL;
+    gnx_cigar *ops = nullptr; int64_t *off = nullptr;
+    const int rc = tcat ? gnx_best_of_windows(&p, n, rcat.data(), roff.data(), tcat->data(), (int64_t)tcat->size(), coff.data(), cstart.data(), clen.data(), cstrand.data(), best.data(), sc.data(),
+                                              local ? end.data() : nullptr, cand.data(), cigar ? &ops : nullptr, cigar ? &off : nullptr)
+                        : gnx_best_of_by_offset(&p, n, rcat.data(), roff.data(), coff.data(), cstart.data(), clen.data(), cstrand.data(), best.data(), sc.data(), local ? end.data() : nullptr, cand.data(),
+                                                cigar ? &ops : nullptr, cigar ? &off : nullptr);
+    if (rc) raise(rc);
+    std::vector<BestOf> out((size_t)n);
+    for (int64_t k = 0; k < n; k++) {
+        BestOf &b = out[(size_t)k];
+        b.Best = best[(size_t)k]; b.Score = sc[(size_t)k]; b.TargetEnd = end[(size_t)k];
+        b.CandScores.assign(cand.begin() + coff[(size_t)k], cand.begin() + coff[(size_t)k + 1]);
+        for (int64_t x = cigar ? off[k] : 0; cigar && x < off[k + 1]; x++) b.Route.push_back(Cigar{ops[x].run_length, ops[x].op});
+    }
+    if (cigar) { gnx_free(ops); gnx_free(off); }
+    return out;
+}
+} // namespace detail
+inline std::vector<BestOf> MapBestOf(int mode, const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, const std::vector<std::vector<dna::Base>> &reads,
+                                     const std::vector<std::vector<SeqCandidate>> &candidates, bool cigar = true) {
+    std::vector<int64_t> coff(reads.size() + 1, 0), cstart, clen;
+    std::vector<uint8_t> cstrand;
+    std::vector<dna::Base> tcat;
+    for (size_t r = 0; r < reads.size(); r++) {
+        for (const auto &cd : candidates[r]) {
+            cstart.push_back((int64_t)tcat.size()); clen.push_back((int64_t)cd.Target.size()); cstrand.push_back(cd.Strand);
+            tcat.insert(tcat.end(), cd.Target.begin(), cd.Target.end());
+        }
+        coff[r + 1] = (int64_t)cstart.size();
+    }
+    cstart.push_back(0); clen.push_back(0); cstrand.push_back(0); // (data() of an empty vector may be null)
+    return detail::best_of(detail::params(mode, scores, gapOpen, gapExtend, 10000, 10000), reads, &tcat, coff, cstart, clen, cstrand, cigar);
+}
+inline std::vector<BestOf> MapBestOf(int mode, const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, const std::vector<std::vector<dna::Base>> &reads,
+                                     const std::vector<std::vector<RefCandidate>> &candidates, bool cigar = true) {
+    std::vector<int64_t> coff(reads.size() + 1, 0), cstart, clen;
+    std::vector<uint8_t> cstrand;
+    for (size_t r = 0; r < reads.size(); r++) {
+        for (const auto &cd : candidates[r]) { cstart.push_back(cd.Start); clen.push_back(cd.Len); cstrand.push_back(cd.Strand); }
+        coff[r + 1] = (int64_t)cstart.size();
+    }
+    cstart.push_back(0); clen.push_back(0); cstrand.push_back(0);
+    return detail::best_of(detail::params(mode, scores, gapOpen, gapExtend, 10000, 10000), reads, nullptr, coff, cstart, clen, cstrand, cigar);
 }
 
 inline void AffineGapLocalEngine(const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, std::vector<TargetQueryPair> &pairs) {
