@@ -21,6 +21,7 @@ EXPORTS = ["gnx_device_count", "gnx_init", "gnx_shutdown", "gnx_last_error", "gn
            "gnx_seed_index_build", "gnx_seed_index_set", "gnx_seed_find_batch", "gnx_seed_index_set_gen", "gnx_seed_find_batch_gen", "gnx_gsw_graph_create", "gnx_gsw_graph_free", "gnx_gsw_map_reads", "gnx_debug_occupy", "gnx_debug_counter", "gnx_reference_info",
            "gnx_score_batch", "gnx_score_batch_windows", "gnx_score_batch_by_offset", "gnx_score_batch_device",
            "gnx_locate_batch", "gnx_locate_batch_windows", "gnx_locate_batch_by_offset",
+           "gnx_locate_span_batch", "gnx_locate_span_batch_windows", "gnx_locate_span_batch_by_offset",
            "gnx_affine_gap_chunk_score_batch", "gnx_multiple_affine_gap_score_batch",
            "gnx_best_of_by_offset", "gnx_best_of_windows"]
 
@@ -121,6 +122,12 @@ def lib():
         L.gnx_locate_batch_windows.restype = ctypes.c_int
         L.gnx_locate_batch_by_offset.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, c_p, c_p, c_p, c_p, c_p]
         L.gnx_locate_batch_by_offset.restype = ctypes.c_int
+        L.gnx_locate_span_batch.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p]
+        L.gnx_locate_span_batch.restype = ctypes.c_int
+        L.gnx_locate_span_batch_windows.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, i64, c_p, c_p, c_p, i64, c_p, c_p, c_p, c_p, c_p]
+        L.gnx_locate_span_batch_windows.restype = ctypes.c_int
+        L.gnx_locate_span_batch_by_offset.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p]
+        L.gnx_locate_span_batch_by_offset.restype = ctypes.c_int
         L.gnx_best_of_by_offset.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_p)]
         L.gnx_best_of_by_offset.restype = ctypes.c_int
         L.gnx_best_of_windows.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, c_p, c_p, i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_p)]
@@ -416,6 +423,55 @@ def locate_batch(params, targets, queries):
     ends = np.zeros(max(n, 1), dtype=np.int64)
     check(L.gnx_locate_batch(ctypes.byref(params), n, t_cat.ctypes.data, t_off.ctypes.data, q_cat.ctypes.data, q_off.ctypes.data, scores.ctypes.data, ends.ctypes.data))
     return scores[:n], ends[:n]
+
+
+# ---- span calls (gnx_locate_span_*): the locate calls plus the target start of the alignment ----
+def locate_span_batch_windows(params, t_buf, t_start, t_len, q_buf, q_start, q_len):
+    """gnx_locate_span_batch_windows.  Returns (scores[int64], target_starts[int64], target_ends[int64])."""
+    L = lib()
+    t_buf, q_buf = _u8(t_buf), _u8(q_buf)
+    t_start, t_len, q_start, q_len = _i64(t_start), _i64(t_len), _i64(q_start), _i64(q_len)
+    n = int(t_start.shape[0])
+    scores = np.zeros(max(n, 1), dtype=np.int64)
+    starts = np.zeros(max(n, 1), dtype=np.int64)
+    ends = np.zeros(max(n, 1), dtype=np.int64)
+    check(L.gnx_locate_span_batch_windows(ctypes.byref(params), n, t_buf.ctypes.data, t_buf.shape[0], t_start.ctypes.data, t_len.ctypes.data,
+                                          q_buf.ctypes.data, q_buf.shape[0], q_start.ctypes.data, q_len.ctypes.data,
+                                          scores.ctypes.data, starts.ctypes.data, ends.ctypes.data))
+    return scores[:n], starts[:n], ends[:n]
+
+
+def locate_span_batch_by_offset(params, q_cat, q_off, ref_start, ref_len):
+    """gnx_locate_span_batch_by_offset: reads (the queries) against windows of the resident reference (the targets); positions are
+    relative to each window."""
+    L = lib()
+    q_cat, q_off, ref_start, ref_len = _u8(q_cat), _i64(q_off), _i64(ref_start), _i64(ref_len)
+    n = int(ref_start.shape[0])
+    scores = np.zeros(max(n, 1), dtype=np.int64)
+    starts = np.zeros(max(n, 1), dtype=np.int64)
+    ends = np.zeros(max(n, 1), dtype=np.int64)
+    check(L.gnx_locate_span_batch_by_offset(ctypes.byref(params), n, q_cat.ctypes.data, q_off.ctypes.data, ref_start.ctypes.data, ref_len.ctypes.data,
+                                            scores.ctypes.data, starts.ctypes.data, ends.ctypes.data))
+    return scores[:n], starts[:n], ends[:n]
+
+
+def locate_span_batch(params, targets, queries):
+    """gnx_locate_span_batch on lists of uint8 arrays.  Returns (scores[int64], target_starts[int64], target_ends[int64])."""
+    L = lib()
+    n = len(targets)
+    t_off = np.zeros(n + 1, dtype=np.int64)
+    q_off = np.zeros(n + 1, dtype=np.int64)
+    if n:
+        t_off[1:] = np.cumsum([len(t) for t in targets])
+        q_off[1:] = np.cumsum([len(q) for q in queries])
+    t_cat = _u8(np.concatenate([_u8(t) for t in targets])) if n and t_off[-1] else np.zeros(1, dtype=np.uint8)
+    q_cat = _u8(np.concatenate([_u8(q) for q in queries])) if n and q_off[-1] else np.zeros(1, dtype=np.uint8)
+    scores = np.zeros(max(n, 1), dtype=np.int64)
+    starts = np.zeros(max(n, 1), dtype=np.int64)
+    ends = np.zeros(max(n, 1), dtype=np.int64)
+    check(L.gnx_locate_span_batch(ctypes.byref(params), n, t_cat.ctypes.data, t_off.ctypes.data, q_cat.ctypes.data, q_off.ctypes.data,
+                                  scores.ctypes.data, starts.ctypes.data, ends.ctypes.data))
+    return scores[:n], starts[:n], ends[:n]
 
 
 # ---- best of K on both strands (gnx_best_of_*): score every candidate, keep the first maximum, align the winners ----

@@ -152,6 +152,23 @@ def AffineGapLocalEnd(target, query, scores, gapOpen, gapExtend):
     return sc[0], ends[0]
 
 
+def LocateSpanBatch(params, targets, queries):
+    """AffineGapLocal's score, target start and target end for every (target, query) pair: ([score, ...], [targetStart, ...],
+    [targetEnd, ...]) in input order.  targetStart = the leading ColD run of the route AffineGapLocal returns (0 if it does not begin
+    with one): the leftmost aligned target position; targetEnd as in LocateBatch.  params.mode must be GNX_AFFINE_GAP_LOCAL."""
+    try:
+        scores, starts, ends = _lib.locate_span_batch(params, targets, queries)
+    except _lib.GnxError as e:
+        _raise(e)
+    return [int(x) for x in scores], [int(x) for x in starts], [int(x) for x in ends]
+
+
+def AffineGapLocalSpan(target, query, scores, gapOpen, gapExtend):
+    """(score, targetStart, targetEnd) of AffineGapLocal(target, query, ...) without its route."""
+    sc, starts, ends = LocateSpanBatch(_lib.make_params(_lib.GNX_AFFINE_GAP_LOCAL, scores, gapOpen, gapExtend), [target], [query])
+    return sc[0], starts[0], ends[0]
+
+
 def ScoreAllPairs(seqs, params):
     """Scores of all x < y pairs of `seqs` from one device call: {(x, y): score} (what a distance matrix or the choice of the
     nearest pair of a progressive-alignment round needs)."""

@@ -326,6 +326,21 @@ __global__ __launch_bounds__(256) void cigar_target_end_kernel(const gnx_cigar *
     if (off[p + 1] > off[p]) { const gnx_cigar last = ops[off[p + 1] - 1]; if (last.op == GNX_COL_D) e -= last.run_length; }
     end[p] = e;
 }
+// gnx_locate_span_* on the same routes: also start[p] = the leading GNX_COL_D run of pair p's CIGAR (0 if it does not begin with one);
+// a CIGAR that is ONE GNX_COL_D run (an empty query) gives start = end = 0
+__global__ __launch_bounds__(256) void cigar_target_span_kernel(const gnx_cigar *__restrict__ ops, const int64_t *__restrict__ off, const int64_t *__restrict__ target_len,
+                                                                int64_t n, int64_t *__restrict__ start, int64_t *__restrict__ end) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    int64_t s = 0, e = target_len[p];
+    if (off[p + 1] > off[p]) {
+        const gnx_cigar first = ops[off[p]], last = ops[off[p + 1] - 1];
+        if (last.op == GNX_COL_D) e -= last.run_length;
+        if (first.op == GNX_COL_D && off[p + 1] - off[p] > 1) s = first.run_length;
+    }
+    start[p] = s;
+    end[p] = e;
+}
 
 // ---- gnx_best_of_*: reverse complements, per read the first maximum of its candidates, the winners' window tables ---------------
 // rc[read_off[r] + k] = complement of reads[read_off[r + 1] - 1 - k]: A <-> T, C <-> G, N stays N, a byte >= 5 stays what it is (and

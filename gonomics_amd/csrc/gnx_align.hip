@@ -52,6 +52,7 @@
 #include "seed_kernels.hip.h"
 #include "score_sweep.hip.h"
 #include "n1_sweep.hip.h"
+#include "span_origin.hip.h"
 
 namespace {
 
@@ -134,6 +135,7 @@ struct Ctx {
     // pipelined host entry (gnx_host.hip.h): double-buffered inputs, results accumulated on the device, the resident reference
     DevBuf pin_a[2], pin_as[2], pin_b[2], pin_bs[2], res_score, res_off, res_ops, ref, gat_score, gat_off, gat_ops;
     // resident seed index of the graph aligner (gnx_seed_index_set)
+    DevBuf sp_hand, res_start, gat_start; // gnx_locate_span_*: stage 2's hand-over rows (span_origin.hip.h), the starts of a host job, their gather on device 0
     DevBuf ss_len, res_end, gat_end; // gnx_locate_*: target lengths for the end read off a CIGAR, the ends of a host job, their gather on device 0
     DevBuf ss_plans, ss_rowbuf, ss_prog, ss_err, ss_off; // the score-only sweep (score_sweep.hip.h): plans, hand-over rows, progress / claim words, error flags; offsets of a dropped CIGAR
     DevBuf sd_keys, sd_locs, sd_nodes, sd_node_off, sd_word_off, sd_words, sd_tmp[8];
@@ -2137,8 +2139,12 @@ bool n1_sweep_fits(const gnx_params *prm2, int64_t n_pairs, const std::vector<Sc
 // piped launch of all levels, or one launch per level (GNX_NO_PIPE, and again after a level timed out waiting: err bit 16).  The
 // launchers find the error word, the hand-over rows and the progress / claim words in ss_err, ss_rowbuf and ss_prog.
 // Leaves the error word of the sweep that counts in `ef` and fills gnx_timing.
-template <class Plan, class OneBlock, class Levels>
-int run_sweep_plans(std::vector<Plan> &plans, hipStream_t stream, int fast_path, int64_t cells, int &ef, OneBlock one_block, Levels levels) {
+// after(device plans, their number): a second stage enqueued behind the sweep, before the error word is fetched (gnx_locate_span_*: no host
+// round trip between the stages); fill_ms and total_ms then cover both stages, dominant_ms stays the sweep's.
+struct NoAfter { int operator()(const void *, int64_t) const { return GNX_OK; } };
+template <class Plan, class OneBlock, class Levels, class After = NoAfter>
+int run_sweep_plans(std::vector<Plan> &plans, hipStream_t stream, int fast_path, int64_t cells, int &ef, OneBlock one_block, Levels levels, After after = After()) {
+    constexpr bool two_stages = !std::is_same<After, NoAfter>::value;
     Ctx &c = g_ctx;
     int rc;
     const int64_t n_pairs = (int64_t)plans.size();
@@ -2193,6 +2199,10 @@ int run_sweep_plans(std::vector<Plan> &plans, hipStream_t stream, int fast_path,
             HIPCHK(hipGetLastError());
         }
         HIPCHK(hipEventRecord(c.ev[1], stream));
+        if (two_stages) {
+            if ((rc = after(dpl, (int64_t)plans.size()))) return rc;
+            HIPCHK(hipEventRecord(c.ev[2], stream));
+        }
         HIPCHK(hipMemcpyAsync(&ef, d_err, 4, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
         return GNX_OK;
@@ -2211,6 +2221,11 @@ int run_sweep_plans(std::vector<Plan> &plans, hipStream_t stream, int fast_path,
     c.timing = gnx_timing{};
     c.timing.fill_ms = ms; c.timing.total_ms = ms; c.timing.cells = cells; c.timing.n_launches = 1; c.timing.trace_bytes = 0;
     c.timing.dominant_ms = ms; c.timing.dominant_launches = launches; c.timing.fast_path = fast_path;
+    if (two_stages) {
+        float ms2 = 0;
+        HIPCHK(hipEventElapsedTime(&ms2, c.ev[0], c.ev[2]));
+        c.timing.fill_ms = ms2; c.timing.total_ms = ms2;
+    }
     return GNX_OK;
 }
 
@@ -2576,7 +2591,8 @@ int run_host_windows(const gnx_params *prm, int64_t n_pairs,
 // scores[target * 5 + query] either way) -- at most SS_MAX_LEVELS * 160 bases, with gapExtend <= 0 and -2 * gapExtend inside int16
 // as well; d_end != nullptr also receives the target end of every pair.
 int run_score_sweep(const gnx_params *prm, int64_t n_pairs, const uint8_t *d_a, const int64_t *d_as, const uint8_t *d_b, const int64_t *d_bs,
-                    const int64_t *h_alen, const int64_t *h_blen, int64_t *d_score, hipStream_t stream, int64_t *d_end = nullptr, bool query_is_alpha = false) {
+                    const int64_t *h_alen, const int64_t *h_blen, int64_t *d_score, hipStream_t stream, int64_t *d_end = nullptr, bool query_is_alpha = false,
+                    int64_t *d_start = nullptr) {
     Ctx &c = g_ctx;
     KParams kp; TbParams tp; bool affine, local, lowmem;
     int rc = check_params(prm, kp, tp, affine, local, lowmem);
@@ -2613,13 +2629,12 @@ int run_score_sweep(const gnx_params *prm, int64_t n_pairs, const uint8_t *d_a, 
         kp.brank = reinterpret_cast<const unsigned *>(c.ref_rank.p); kp.bexc = reinterpret_cast<const unsigned long long *>(c.ref_exc.p);
     }
     int ef = 0;
-    rc = run_sweep_plans(plans, stream, local ? 8 : 7, cells, ef,
-        [&](const ScorePlan *gp, int W) {
+    auto one_block = [&](const ScorePlan *gp, int W) {
             int *d_err = (int *)c.ss_err.p;
             if (local) hipLaunchKernelGGL(score_local_kernel, dim3((unsigned)W), dim3(64), 0, stream, gp, d_a, d_as, d_b, d_bs, kp, sp, d_score, d_end, d_err);
             else hipLaunchKernelGGL(affine ? score_sweep_kernel<true> : score_sweep_kernel<false>, dim3((unsigned)W), dim3(64), 0, stream, gp, d_a, d_as, d_b, d_bs, kp, sp, d_score, d_err);
-        },
-        [&](const ScorePlan *gp, int S, int W, int level0, int piped, unsigned grid) {
+        };
+    auto levels = [&](const ScorePlan *gp, int S, int W, int level0, int piped, unsigned grid) {
             int *d_err = (int *)c.ss_err.p, *prog = (int *)c.ss_prog.p;
             int2 *rb = (int2 *)c.ss_rowbuf.p;
             if (local) {
@@ -2629,9 +2644,48 @@ int run_score_sweep(const gnx_params *prm, int64_t n_pairs, const uint8_t *d_a, 
                 ScoreLevelsArgs la{gp, d_a, d_as, d_b, d_bs, kp, sp, d_score, d_err, rb, S, W, level0, piped, prog};
                 hipLaunchKernelGGL(affine ? score_sweep_levels_kernel<true> : score_sweep_levels_kernel<false>, dim3(grid), dim3(64), 0, stream, la);
             }
+        };
+    if (local && d_start && d_end) {
+        // gnx_locate_span_* (fast_path 10): stage 2 behind the sweep on the same stream, one wave per pair at a
+        // time.  Its hand-over rows (queries of more than one 192-column strip) are sized from the host's own bound on the window,
+        // rows <= min(n, m + dmax) with S >= gapOpen + m * gapExtend, i.e. dmax <= m * (smax+ - gapExtend) / -gapExtend -- per WAVE of the
+        // grid, not per pair; gapExtend == 0 leaves only rows <= n, and the grid shrinks until the rows fit 256 MB.
+        SpanArgs sa;
+        memset(&sa, 0, sizeof(sa));
+        int64_t smaxp = 0, wcap = 0;
+        for (int x = 0; x < 25; x++) { sa.sp.sc[x] = (int)prm->scores[x]; smaxp = std::max<int64_t>(smaxp, prm->scores[x]); }
+        sa.sp.o = (int)prm->gap_open; sa.sp.e = (int)prm->gap_extend; sa.sp.smaxp = (int)smaxp;
+        for (int64_t p = 0; p < n_pairs; p++) {
+            const int64_t n = query_is_alpha ? h_blen[p] : h_alen[p], m = query_is_alpha ? h_alen[p] : h_blen[p];
+            if (m <= SPAN_STRIP) continue;
+            const int64_t rows = prm->gap_extend < 0 ? std::min(n, m + m * (smaxp - prm->gap_extend) / -prm->gap_extend) : n;
+            wcap = std::max(wcap, rows + 1);
+        }
+        static std::atomic<int> per_cu_cache{0}; // one-wave workgroups of the kernel a CU holds (its registers decide): the grid is what is resident at once
+        int per_cu = per_cu_cache.load();
+        if (per_cu <= 0) {
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, span_origin_kernel, 64, 0) != hipSuccess || per_cu <= 0) per_cu = 16;
+            per_cu_cache.store(per_cu);
+        }
+        int64_t waves = std::min<int64_t>(n_pairs, (int64_t)std::max(c.n_cu, 1) * per_cu);
+        while (waves > 64 && waves * wcap * 24 > ((int64_t)256 << 20)) waves /= 2;
+        if (waves * wcap * 24 > ((int64_t)256 << 20)) return -1;
+        if (wcap && (rc = c.sp_hand.ensure((size_t)(waves * wcap * 24)))) return rc;
+        sa.t_buf = query_is_alpha ? d_b : d_a; sa.t_start = query_is_alpha ? d_bs : d_as;
+        sa.q_buf = query_is_alpha ? d_a : d_b; sa.q_start = query_is_alpha ? d_as : d_bs;
+        sa.kp = kp;
+        if (!query_is_alpha) { sa.kp.b2 = nullptr; sa.kp.bflag = nullptr; sa.kp.brank = nullptr; sa.kp.bexc = nullptr; } // (the target is alpha: plain bytes)
+        sa.score = d_score; sa.end = d_end; sa.start = d_start; sa.hand = (int *)c.sp_hand.p; sa.wcap = (int)wcap;
+        rc = run_sweep_plans(plans, stream, 10, cells, ef, one_block, levels, [&](const void *dpl, int64_t n_plans) -> int {
+            sa.plans = (const ScorePlan *)dpl; sa.n_plans = (int)n_plans; sa.err = (int *)c.ss_err.p;
+            hipLaunchKernelGGL(span_origin_kernel, dim3((unsigned)waves), dim3(64), 0, stream, sa);
+            HIPCHK(hipGetLastError());
+            return GNX_OK;
         });
+    } else rc = run_sweep_plans(plans, stream, local ? 8 : 7, cells, ef, one_block, levels);
     if (rc) return rc;
     if (ef & 1) { set_err("a base >= 5 was found: the reference would panic (index out of range)%s", ""); return GNX_EBASE; }
+    if (ef & SPAN_ERR) { set_err("gnx_locate_span_*: the window DP did not reproduce the sweep's score%s", ""); return GNX_ETRACE; }
     return GNX_OK;
 }
 
@@ -2727,7 +2781,7 @@ void gnx_shutdown(void) {
                           &c.fp_wplans[0], &c.fp_wplans[1], &c.fp_active[0], &c.fp_active[1], &c.trace, &c.hcol, &c.rowbuf, &c.dcol, &c.plans, &c.nops, &c.misc, &c.in_a, &c.in_b,
                           &c.in_as, &c.in_al, &c.in_bs, &c.in_bl, &c.out_score, &c.out_off, &c.out_ops, &c.out_end, &c.sc_pairs, &c.sc_mat, &c.sc_err,
                           &c.pin_a[0], &c.pin_a[1], &c.pin_as[0], &c.pin_as[1], &c.pin_b[0], &c.pin_b[1], &c.pin_bs[0], &c.pin_bs[1], &c.res_score, &c.res_off, &c.res_ops,
-                          &c.ref, &c.ref_flag, &c.ref_rank, &c.ref_exc, &c.unpk_b, &c.unpk_off, &c.cl_bases, &c.sc_prof_a, &c.sc_prof_b, &c.mega_rows, &c.mega_state, &c.farm, &c.mega_arena, &c.gat_score, &c.gat_off, &c.gat_ops, &c.ss_plans, &c.ss_rowbuf, &c.ss_prog, &c.ss_err, &c.ss_off, &c.ss_len, &c.res_end, &c.gat_end, &c.sd_keys, &c.sd_locs, &c.sd_nodes, &c.sd_node_off, &c.sd_word_off, &c.sd_words,
+                          &c.ref, &c.ref_flag, &c.ref_rank, &c.ref_exc, &c.unpk_b, &c.unpk_off, &c.cl_bases, &c.sc_prof_a, &c.sc_prof_b, &c.mega_rows, &c.mega_state, &c.farm, &c.mega_arena, &c.gat_score, &c.gat_off, &c.gat_ops, &c.ss_plans, &c.ss_rowbuf, &c.ss_prog, &c.ss_err, &c.ss_off, &c.ss_len, &c.res_end, &c.gat_end, &c.sp_hand, &c.res_start, &c.gat_start, &c.sd_keys, &c.sd_locs, &c.sd_nodes, &c.sd_node_off, &c.sd_word_off, &c.sd_words,
                           &c.sd_tmp[0], &c.sd_tmp[1], &c.sd_tmp[2], &c.sd_tmp[3], &c.sd_tmp[4], &c.sd_tmp[5], &c.sd_tmp[6], &c.sd_tmp[7]};
         for (DevBuf *b : bufs) b->release();
         for (DevBuf &b : c.bo) b.release();
@@ -2875,6 +2929,39 @@ int gnx_locate_batch_by_offset(const gnx_params *p, int64_t n_pairs, const uint8
     std::vector<int64_t> ql((size_t)n_pairs);
     for (int64_t q = 0; q < n_pairs; q++) ql[(size_t)q] = query_off[q + 1] - query_off[q];
     return run_host_sharded(p, n_pairs, query_cat, query_off[n_pairs], query_off, ql.data(), nullptr, 0, ref_start, ref_len, out_score, nullptr, nullptr, true, out_target_end, 2);
+}
+
+/* ---- span entries: the locate entries plus the target START of the alignment (gnx_align.h) ---- */
+int gnx_locate_span_batch_windows(const gnx_params *p, int64_t n_pairs,
+                                  const uint8_t *target_buf, int64_t target_buf_len, const int64_t *target_start, const int64_t *target_len,
+                                  const uint8_t *query_buf, int64_t query_buf_len, const int64_t *query_start, const int64_t *query_len,
+                                  int64_t *out_score, int64_t *out_target_start, int64_t *out_target_end) {
+    std::lock_guard<std::mutex> api(g_api_mu);
+    g_err[0] = 0;
+    static const uint8_t none = 0;
+    if (!out_target_end || !out_target_start) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    return run_host_sharded(p, n_pairs, target_buf ? target_buf : &none, target_buf_len, target_start, target_len, query_buf ? query_buf : &none, query_buf_len, query_start, query_len,
+                            out_score, nullptr, nullptr, true, out_target_end, 3, out_target_start);
+}
+
+int gnx_locate_span_batch(const gnx_params *p, int64_t n_pairs, const uint8_t *target_cat, const int64_t *target_off,
+                          const uint8_t *query_cat, const int64_t *query_off, int64_t *out_score, int64_t *out_target_start, int64_t *out_target_end) {
+    if (n_pairs < 0 || !target_off || !query_off) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    std::vector<int64_t> tl((size_t)n_pairs), ql((size_t)n_pairs);
+    for (int64_t q = 0; q < n_pairs; q++) { tl[(size_t)q] = target_off[q + 1] - target_off[q]; ql[(size_t)q] = query_off[q + 1] - query_off[q]; }
+    return gnx_locate_span_batch_windows(p, n_pairs, target_cat, target_off[n_pairs], target_off, tl.data(), query_cat, query_off[n_pairs], query_off, ql.data(),
+                                         out_score, out_target_start, out_target_end);
+}
+
+int gnx_locate_span_batch_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *query_cat, const int64_t *query_off,
+                                    const int64_t *ref_start, const int64_t *ref_len, int64_t *out_score, int64_t *out_target_start, int64_t *out_target_end) {
+    std::lock_guard<std::mutex> api(g_api_mu);
+    g_err[0] = 0;
+    if (n_pairs < 0 || !query_off || !out_target_end || !out_target_start || (n_pairs > 0 && (!ref_start || !ref_len))) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    std::vector<int64_t> ql((size_t)n_pairs);
+    for (int64_t q = 0; q < n_pairs; q++) ql[(size_t)q] = query_off[q + 1] - query_off[q];
+    return run_host_sharded(p, n_pairs, query_cat, query_off[n_pairs], query_off, ql.data(), nullptr, 0, ref_start, ref_len, out_score, nullptr, nullptr, true, out_target_end, 4,
+                            out_target_start);
 }
 
 /* ---- best of K on both strands: score every candidate, keep the first maximum, align the winners (gnx_align.h) ---- */

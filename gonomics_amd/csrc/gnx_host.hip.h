@@ -283,6 +283,7 @@ struct HostJob {
     const uint8_t *b_dev = nullptr; // != nullptr: the whole beta buffer / the resident reference is on this context's device
     bool packed = false;            // b_dev is the PACKED resident reference (beta windows = base positions in it)
     bool score_only = false;        // gnx_score_*: scores only (the score sweep, or the ordinary route with its CIGAR left on the device)
+    bool span = false;              // gnx_locate_span_*: the target start as well (res_start)
     int locate = 0;                 // gnx_locate_* (score_only as well): 1: alpha = target, beta = query; 2: alpha = query, beta = target (windows of the resident reference)
     int64_t total_ops = 0;
     int rc = GNX_OK;
@@ -307,10 +308,12 @@ int grow_ops(Ctx &c, int64_t keep_elems, int64_t want_elems, hipStream_t st) {
 // A batch of a score-only call on the current context: the score sweep where it applies (run_score_sweep), else the ordinary
 // route, whose CIGAR goes into the context's result buffer and simply stays there.  Sets c.timing like run_device.
 // d_end != nullptr (gnx_locate_*, alpha = target): also the target end of every pair, from the sweep or read off the CIGAR on the
-// device.  try_sweep = false: the caller has tried the sweep already.
+// device.  d_start != nullptr (gnx_locate_span_*, with d_end): the target start as well, from stage 2 behind the sweep (fast_path 10) or off the
+// CIGAR.  try_sweep = false: the caller has tried the sweep already.
 int score_or_fallback(Ctx &c, const gnx_params *prm, int64_t cnt, const uint8_t *d_a, const int64_t *d_as, const uint8_t *d_b, const int64_t *d_bs,
-                      const int64_t *h_alen, const int64_t *h_blen, int64_t *d_score, hipStream_t stream, int64_t *d_end = nullptr, bool try_sweep = true) {
-    int rc = try_sweep ? run_score_sweep(prm, cnt, d_a, d_as, d_b, d_bs, h_alen, h_blen, d_score, stream, d_end) : -1;
+                      const int64_t *h_alen, const int64_t *h_blen, int64_t *d_score, hipStream_t stream, int64_t *d_end = nullptr, bool try_sweep = true,
+                      int64_t *d_start = nullptr) {
+    int rc = try_sweep ? run_score_sweep(prm, cnt, d_a, d_as, d_b, d_bs, h_alen, h_blen, d_score, stream, d_end, false, d_start) : -1;
     if (rc != -1) return rc;
     if ((rc = c.ss_off.ensure((size_t)(std::max<int64_t>(cnt, 0) + 1) * 8))) return rc;
     if ((rc = grow_ops(c, 0, std::max<int64_t>((int64_t)1 << 20, 64 * cnt), stream))) return rc;
@@ -323,8 +326,10 @@ int score_or_fallback(Ctx &c, const gnx_params *prm, int64_t cnt, const uint8_t 
     if (rc == GNX_OK && d_end && cnt > 0) {
         if ((rc = c.ss_len.ensure((size_t)cnt * 8))) return rc;
         HIPCHK(hipMemcpyAsync(c.ss_len.p, h_alen, (size_t)cnt * 8, hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(cigar_target_end_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, (const gnx_cigar *)c.res_ops.p, (const int64_t *)c.ss_off.p,
-                           (const int64_t *)c.ss_len.p, cnt, d_end);
+        if (d_start) hipLaunchKernelGGL(cigar_target_span_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, (const gnx_cigar *)c.res_ops.p, (const int64_t *)c.ss_off.p,
+                                        (const int64_t *)c.ss_len.p, cnt, d_start, d_end);
+        else hipLaunchKernelGGL(cigar_target_end_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, (const gnx_cigar *)c.res_ops.p, (const int64_t *)c.ss_off.p,
+                                (const int64_t *)c.ss_len.p, cnt, d_end);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(stream)); // h_alen is the caller's
     }
@@ -339,6 +344,7 @@ int run_host_job(HostJob &j) {
     if ((rc = c.res_score.ensure((size_t)std::max<int64_t>(n, 1) * 8))) return rc;
     if ((rc = c.res_off.ensure((size_t)(n + 1) * 8))) return rc;
     if (j.locate && (rc = c.res_end.ensure((size_t)std::max<int64_t>(n, 1) * 8))) return rc;
+    if (j.span && (rc = c.res_start.ensure((size_t)std::max<int64_t>(n, 1) * 8))) return rc;
     if (n == 0) { HIPCHK(hipMemsetAsync(c.res_off.p, 0, 8, c.own_stream)); HIPCHK(hipStreamSynchronize(c.own_stream)); return GNX_OK; }
     int64_t sub = 131072;
     if (const char *e = getenv("GNX_HOST_SUB")) sub = (std::max<int64_t>(atoll(e), 8) + 7) & ~(int64_t)7;
@@ -437,16 +443,16 @@ int run_host_job(HostJob &j) {
         // (gnx_locate_batch_by_offset: the local sweep reads its target packed; only its fallback needs bytes)
         if (packed && rc == GNX_OK && j.locate != 2 && (j.prm->mode == GNX_AFFINE_GAP_LOCAL || getenv("GNX_REF_UNPACK"))) rc = unpack_windows();
         if (j.score_only && j.locate == 2 && rc == GNX_OK) { // alpha = queries, beta = targets: the sweep as it is, the ordinary route with the two swapped
-            int64_t *d_sc = (int64_t *)c.res_score.p + done, *d_en = (int64_t *)c.res_end.p + done;
+            int64_t *d_sc = (int64_t *)c.res_score.p + done, *d_en = (int64_t *)c.res_end.p + done, *d_st = j.span ? (int64_t *)c.res_start.p + done : nullptr;
             c.beta_packed = packed;
-            rc = run_score_sweep(j.prm, cnt, (const uint8_t *)c.pin_a[slot].p, (const int64_t *)c.pin_as[slot].p, db, dbs, al + b, bl + b, d_sc, c.own_stream, d_en, true);
+            rc = run_score_sweep(j.prm, cnt, (const uint8_t *)c.pin_a[slot].p, (const int64_t *)c.pin_as[slot].p, db, dbs, al + b, bl + b, d_sc, c.own_stream, d_en, true, d_st);
             c.beta_packed = false;
             if (rc == -1 && (!packed || (rc = unpack_windows()) == GNX_OK))
-                rc = score_or_fallback(c, j.prm, cnt, db, dbs, (const uint8_t *)c.pin_a[slot].p, (const int64_t *)c.pin_as[slot].p, bl + b, al + b, d_sc, c.own_stream, d_en, false);
+                rc = score_or_fallback(c, j.prm, cnt, db, dbs, (const uint8_t *)c.pin_a[slot].p, (const int64_t *)c.pin_as[slot].p, bl + b, al + b, d_sc, c.own_stream, d_en, false, d_st);
         } else if (j.score_only && rc == GNX_OK) {
             c.beta_packed = packed;
             rc = score_or_fallback(c, j.prm, cnt, (const uint8_t *)c.pin_a[slot].p, (const int64_t *)c.pin_as[slot].p, db, dbs, al + b, bl + b, (int64_t *)c.res_score.p + done, c.own_stream,
-                                   j.locate ? (int64_t *)c.res_end.p + done : nullptr);
+                                   j.locate ? (int64_t *)c.res_end.p + done : nullptr, true, j.span ? (int64_t *)c.res_start.p + done : nullptr);
             c.beta_packed = false;
         }
         for (int attempt = 0; rc == GNX_OK && !j.score_only; attempt++) {
@@ -587,11 +593,15 @@ int ensure_reference(int nc) {
 int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
                      const uint8_t *a_buf, int64_t a_len_total, const int64_t *a_start, const int64_t *a_lens,
                      const uint8_t *b_buf, int64_t b_len_total, const int64_t *b_start, const int64_t *b_lens,
-                     int64_t *out_score, gnx_cigar **out_ops, int64_t **out_ops_off, bool score_only = false, int64_t *out_end = nullptr, int locate = 0) {
+                     int64_t *out_score, gnx_cigar **out_ops, int64_t **out_ops_off, bool score_only = false, int64_t *out_end = nullptr, int locate_arg = 0,
+                     int64_t *out_start = nullptr) {
+    // locate_arg: 0 none; 1 / 2 gnx_locate_* (alpha = target / alpha = query); 3 / 4 gnx_locate_span_* with the same two roles
+    const bool span = locate_arg >= 3;
+    const int locate = span ? locate_arg - 2 : locate_arg;
     const auto t_entry = std::chrono::steady_clock::now();
     if (!prm || n_pairs < 0 || !out_score || (!score_only && (!out_ops || !out_ops_off)) || a_len_total < 0 || b_len_total < 0) { set_err("bad argument%s", ""); return GNX_EINVAL; }
     if (n_pairs > 0 && (!a_start || !a_lens || !b_start || !b_lens)) { set_err("null window table%s", ""); return GNX_EINVAL; }
-    if (locate && (!score_only || !out_end)) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (locate && (!score_only || !out_end || (span && !out_start))) { set_err("bad argument%s", ""); return GNX_EINVAL; }
     if (locate && prm->mode != GNX_AFFINE_GAP_LOCAL) { set_err("gnx_locate_*: the mode must be GNX_AFFINE_GAP_LOCAL%s", ""); return GNX_EINVAL; }
     const bool resident = (b_buf == nullptr);
     Ctx &c0 = ctx_at(0);
@@ -641,6 +651,7 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
         j.packed = resident;
         j.score_only = score_only;
         j.locate = locate;
+        j.span = span;
     }
     auto work = [](HostJob *j) {
         CtxScope sc(*j->c);
@@ -672,6 +683,7 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
         if ((rc = c0.gat_off.ensure((size_t)(n_pairs + nc) * 8))) return fail(rc);
         if ((rc = c0.gat_ops.ensure((size_t)std::max<int64_t>(total, 1) * sizeof(gnx_cigar)))) return fail(rc);
         if (locate && (rc = c0.gat_end.ensure((size_t)std::max<int64_t>(n_pairs, 1) * 8))) return fail(rc);
+        if (span && (rc = c0.gat_start.ensure((size_t)std::max<int64_t>(n_pairs, 1) * 8))) return fail(rc);
         // context 0's own share never goes through RCCL (no send-to-self): a device-to-device copy on its stream
         auto gather_local = [&]() -> int {
             HostJob &j = jobs[0];
@@ -681,6 +693,7 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
                 HIPCHK(hipMemcpyAsync((int64_t *)c0.gat_score.p + j.p0, c0.res_score.p, (size_t)nd * 8, hipMemcpyDeviceToDevice, c0.own_stream));
                 HIPCHK(hipMemcpyAsync((int64_t *)c0.gat_off.p + j.p0, c0.res_off.p, (size_t)(nd + 1) * 8, hipMemcpyDeviceToDevice, c0.own_stream));
                 if (locate) HIPCHK(hipMemcpyAsync((int64_t *)c0.gat_end.p + j.p0, c0.res_end.p, (size_t)nd * 8, hipMemcpyDeviceToDevice, c0.own_stream));
+                if (span) HIPCHK(hipMemcpyAsync((int64_t *)c0.gat_start.p + j.p0, c0.res_start.p, (size_t)nd * 8, hipMemcpyDeviceToDevice, c0.own_stream));
             }
             if (j.total_ops > 0) HIPCHK(hipMemcpyAsync(c0.gat_ops.p, c0.res_ops.p, (size_t)j.total_ops * sizeof(gnx_cigar), hipMemcpyDeviceToDevice, c0.own_stream));
             return GNX_OK;
@@ -697,6 +710,7 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
                         RCCLCHK(g_rccl.Send(c.res_score.p, (size_t)nd, ncclInt64, 0, g_rccl.comms[(size_t)d], c.own_stream));
                         RCCLCHK(g_rccl.Send(c.res_off.p, (size_t)nd + 1, ncclInt64, 0, g_rccl.comms[(size_t)d], c.own_stream));
                         if (locate) RCCLCHK(g_rccl.Send(c.res_end.p, (size_t)nd, ncclInt64, 0, g_rccl.comms[(size_t)d], c.own_stream));
+                        if (span) RCCLCHK(g_rccl.Send(c.res_start.p, (size_t)nd, ncclInt64, 0, g_rccl.comms[(size_t)d], c.own_stream));
                     }
                     if (d == 1 && rccl_injected_failure(2)) return GNX_EDEVICE; // (a send is enqueued, its receive is not)
                     if (j.total_ops > 0) RCCLCHK(g_rccl.Send(c.res_ops.p, (size_t)j.total_ops * 2, ncclInt64, 0, g_rccl.comms[(size_t)d], c.own_stream));
@@ -705,6 +719,7 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
                         RCCLCHK(g_rccl.Recv((int64_t *)c0.gat_score.p + j.p0, (size_t)nd, ncclInt64, d, g_rccl.comms[0], c0.own_stream));
                         RCCLCHK(g_rccl.Recv((int64_t *)c0.gat_off.p + j.p0 + d, (size_t)nd + 1, ncclInt64, d, g_rccl.comms[0], c0.own_stream));
                         if (locate) RCCLCHK(g_rccl.Recv((int64_t *)c0.gat_end.p + j.p0, (size_t)nd, ncclInt64, d, g_rccl.comms[0], c0.own_stream));
+                        if (span) RCCLCHK(g_rccl.Recv((int64_t *)c0.gat_start.p + j.p0, (size_t)nd, ncclInt64, d, g_rccl.comms[0], c0.own_stream));
                     }
                     if (j.total_ops > 0) RCCLCHK(g_rccl.Recv((gnx_cigar *)c0.gat_ops.p + obase, (size_t)j.total_ops * 2, ncclInt64, d, g_rccl.comms[0], c0.own_stream));
                     obase += j.total_ops;
@@ -726,6 +741,7 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
                     HIPCHK(hipMemcpyPeer((int64_t *)c0.gat_score.p + j.p0, c0.device, c.res_score.p, c.device, (size_t)nd * 8));
                     HIPCHK(hipMemcpyPeer((int64_t *)c0.gat_off.p + j.p0 + d, c0.device, c.res_off.p, c.device, (size_t)(nd + 1) * 8));
                     if (locate) HIPCHK(hipMemcpyPeer((int64_t *)c0.gat_end.p + j.p0, c0.device, c.res_end.p, c.device, (size_t)nd * 8));
+                    if (span) HIPCHK(hipMemcpyPeer((int64_t *)c0.gat_start.p + j.p0, c0.device, c.res_start.p, c.device, (size_t)nd * 8));
                 }
                 if (j.total_ops > 0) HIPCHK(hipMemcpyPeer((gnx_cigar *)c0.gat_ops.p + obase, c0.device, c.res_ops.p, c.device, (size_t)j.total_ops * sizeof(gnx_cigar)));
                 obase += j.total_ops;
@@ -753,6 +769,7 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
         hipStream_t st = c0.own_stream;
         if (n_pairs) HIPCHK(hipMemcpyAsync(out_score, d_score, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
         if (n_pairs && locate) HIPCHK(hipMemcpyAsync(out_end, nc > 1 ? c0.gat_end.p : c0.res_end.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
+        if (n_pairs && span) HIPCHK(hipMemcpyAsync(out_start, nc > 1 ? c0.gat_start.p : c0.res_start.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
         if (total) HIPCHK(hipMemcpyAsync(ops, d_ops, (size_t)total * sizeof(gnx_cigar), hipMemcpyDeviceToHost, st));
         if (score_only) { /* only the score vector comes back */ }
         else if (nc == 1) HIPCHK(hipMemcpyAsync(off, d_off, (size_t)(n_pairs + 1) * 8, hipMemcpyDeviceToHost, st));

@@ -100,7 +100,9 @@ typedef struct gnx_timing {
                             6: the constant-gap snapshot path in its 64-lane form; 7: the score-only sweep ran (gnx_score_* entries,
                             score_sweep.hip.h); 8: its AffineGapLocal variant ran (gnx_score_* with GNX_AFFINE_GAP_LOCAL, gnx_locate_*);
                             9: the score-only sweep with explicit cell scores ran (gnx_affine_gap_chunk_score_batch,
-                            gnx_multiple_affine_gap_score_batch; n1_sweep.hip.h).
+                            gnx_multiple_affine_gap_score_batch; n1_sweep.hip.h);
+                            10: the local sweep (8) followed by the origin-carrying window DP ran (gnx_locate_span_*;
+                            span_origin.hip.h): fill_ms and total_ms cover both stages, dominant_ms is the sweep's.
                             Multi-context score calls report the maximum over contexts. */
     int32_t _pad;
     /* host-buffer entry points only (wall clock inside the library): */
@@ -250,6 +252,34 @@ int gnx_locate_batch_windows(const gnx_params *p, int64_t n_pairs,
  * the other way round (its alpha, the reads, is the target there). */
 int gnx_locate_batch_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *query_cat, const int64_t *query_off,
                                const int64_t *ref_start, const int64_t *ref_len, int64_t *out_score, int64_t *out_target_end);
+
+/* ---- span entries: score, target START and target end of AffineGapLocal's alignment, without a CIGAR (an extension, no Go signature) -- */
+/* The arguments of the gnx_locate_* twins plus out_target_start[n_pairs]; all three output vectors are required (a null one:
+ * GNX_EINVAL).  p->mode must be GNX_AFFINE_GAP_LOCAL (else GNX_EINVAL).
+ * Contract: out_score and out_target_end are exactly what the locate twin returns.  out_target_start[p] is the run length of the leading
+ * GNX_COL_D run of the CIGAR gnx_align_batch returns for AffineGapLocal(target, query), or 0 when the CIGAR does not begin with one:
+ * the leftmost target position of the alignment (SAM POS - 1, BED chromStart), relative to the pair's own target -- also for
+ * _by_offset: the caller adds ref_start[p].  A CIGAR that is a single GNX_COL_D run (an empty query) gives start = end = 0; an empty
+ * target gives 0 / 0; otherwise start <= end.  Validation and return codes are the locate twins': GNX_EBASE and GNX_EINVAL are
+ * reported before any output is written, GNX_EDEVICE without a device comes after the argument checks, never GNX_ERANGE.
+ * Routes: under the local sweep's conditions (the list at gnx_locate_batch; GNX_SCORE_SWEEP=0 switches it off) the sweep runs
+ * unchanged and a second kernel behind it, with no host round trip in between, repeats the three-state recurrence over the short
+ * stretch target[lo : end] that must hold the route, carrying per state the target row where its path left column 0
+ * (gnx_timing.fast_path == 10).  It compares its own score with the sweep's; a difference -- the impossible case -- returns
+ * GNX_ETRACE, never a wrong start.  Route 10 serves every query the sweep serves: up to 10 240 bases.  Queries of more than 192 bases
+ * hand rows over in device memory sized by the window bound, per resident wave; with gapExtend == 0 (no bound but the target itself)
+ * a sub-batch whose rows would exceed 256 MB takes the fallback.  Everything else -- gapOpen > 0, gapExtend > 0, an empty sequence,
+ * bounds exceeded, GNX_SCORE_SWEEP=0 -- runs the route gnx_align_batch takes and a small kernel reads both positions off the CIGAR on
+ * the device: start and end are defined identically on every route.  Multi-context calls shard and gather all three vectors. */
+int gnx_locate_span_batch(const gnx_params *p, int64_t n_pairs, const uint8_t *target_cat, const int64_t *target_off,
+                          const uint8_t *query_cat, const int64_t *query_off, int64_t *out_score, int64_t *out_target_start, int64_t *out_target_end);
+int gnx_locate_span_batch_windows(const gnx_params *p, int64_t n_pairs,
+                                  const uint8_t *target_buf, int64_t target_buf_len, const int64_t *target_start, const int64_t *target_len,
+                                  const uint8_t *query_buf, int64_t query_buf_len, const int64_t *query_start, const int64_t *query_len,
+                                  int64_t *out_score, int64_t *out_target_start, int64_t *out_target_end);
+/* target = the window (ref_start[p], ref_len[p]) of the resident reference, queries = the reads (as gnx_locate_batch_by_offset) */
+int gnx_locate_span_batch_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *query_cat, const int64_t *query_off,
+                                    const int64_t *ref_start, const int64_t *ref_len, int64_t *out_score, int64_t *out_target_start, int64_t *out_target_end);
 
 /* ---- best of K on both strands: what mapping a read needs (an extension, no Go signature) ----------------------------------------- */
 /* Score a read against a handful of candidate windows on either strand, keep the best, produce a CIGAR for that one only and report

@@ -198,6 +198,33 @@ inline std::pair<int64_t, int64_t> AffineGapLocalEnd(const std::vector<dna::Base
     return {r.first[0], r.second[0]};
 }
 
+// ---- span calls (gnx_locate_span_*; an extension) ----
+// AffineGapLocal's score, target start and target end for every (target, query) pair; targetStart = the leading ColD run of the route
+// AffineGapLocal returns (0 if it does not begin with one): the leftmost aligned target position.
+struct Span { int64_t Score = 0, TargetStart = 0, TargetEnd = 0; };
+inline std::vector<Span> LocateSpanBatch(const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend,
+                                         const std::vector<std::vector<dna::Base>> &targets, const std::vector<std::vector<dna::Base>> &queries) {
+    const int64_t n = (int64_t)targets.size();
+    std::vector<int64_t> toff((size_t)n + 1, 0), qoff((size_t)n + 1, 0);
+    for (int64_t k = 0; k < n; k++) { toff[(size_t)k + 1] = toff[(size_t)k] + (int64_t)targets[(size_t)k].size(); qoff[(size_t)k + 1] = qoff[(size_t)k] + (int64_t)queries[(size_t)k].size(); }
+    std::vector<dna::Base> tcat((size_t)toff[(size_t)n] + 1), qcat((size_t)qoff[(size_t)n] + 1);
+    for (int64_t k = 0; k < n; k++) {
+        std::copy(targets[(size_t)k].begin(), targets[(size_t)k].end(), tcat.begin() + toff[(size_t)k]);
+        std::copy(queries[(size_t)k].begin(), queries[(size_t)k].end(), qcat.begin() + qoff[(size_t)k]);
+    }
+    const gnx_params p = detail::params(GNX_AFFINE_GAP_LOCAL, scores, gapOpen, gapExtend, 10000, 10000);
+    std::vector<int64_t> sc((size_t)std::max<int64_t>(n, 1), 0), start((size_t)std::max<int64_t>(n, 1), 0), end((size_t)std::max<int64_t>(n, 1), 0);
+    const int rc = gnx_locate_span_batch(&p, n, tcat.data(), toff.data(), qcat.data(), qoff.data(), sc.data(), start.data(), end.data());
+    if (rc) detail::raise(rc);
+    std::vector<Span> out((size_t)n);
+    for (int64_t k = 0; k < n; k++) { out[(size_t)k].Score = sc[(size_t)k]; out[(size_t)k].TargetStart = start[(size_t)k]; out[(size_t)k].TargetEnd = end[(size_t)k]; }
+    return out;
+}
+// {score, targetStart, targetEnd} of AffineGapLocal(target, query, ...) without its route
+inline Span AffineGapLocalSpan(const std::vector<dna::Base> &target, const std::vector<dna::Base> &query, const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend) {
+    return LocateSpanBatch(scores, gapOpen, gapExtend, {target}, {query})[0];
+}
+
 // ---- best of K on both strands (gnx_best_of_*; an extension) ----
 // A read against candidate windows on either strand: per read the FIRST best candidate, its score and route, every candidate's score
 // and, for GNX_AFFINE_GAP_LOCAL, the target end.  Global modes: alpha = the read (strand 1: its reverse complement), beta = the
