@@ -23,7 +23,8 @@ EXPORTS = ["gnx_device_count", "gnx_init", "gnx_shutdown", "gnx_last_error", "gn
            "gnx_locate_batch", "gnx_locate_batch_windows", "gnx_locate_batch_by_offset",
            "gnx_locate_span_batch", "gnx_locate_span_batch_windows", "gnx_locate_span_batch_by_offset",
            "gnx_affine_gap_chunk_score_batch", "gnx_multiple_affine_gap_score_batch",
-           "gnx_best_of_by_offset", "gnx_best_of_windows"]
+           "gnx_best_of_by_offset", "gnx_best_of_windows",
+           "gnx_reference_index_build", "gnx_reference_index_info", "gnx_reference_index_get", "gnx_seed_candidates"]
 
 
 class GnxCigar(ctypes.Structure):
@@ -45,6 +46,11 @@ class GnxTiming(ctypes.Structure):
                 ("dominant_ms", ctypes.c_double), ("dominant_launches", ctypes.c_int64), ("fast_path", ctypes.c_int32),
                 ("_pad", ctypes.c_int32), ("host_ms", ctypes.c_double), ("stage0_ms", ctypes.c_double), ("fetch_ms", ctypes.c_double),
                 ("transport", ctypes.c_int32), ("n_contexts", ctypes.c_int32), ("gather_ms", ctypes.c_double), ("bcast_ms", ctypes.c_double)]
+
+
+class GnxSeedVoteOpts(ctypes.Structure):
+    _fields_ = [("max_occ", ctypes.c_int32), ("bin", ctypes.c_int32), ("pad", ctypes.c_int32), ("max_cand", ctypes.c_int32),
+                ("min_votes", ctypes.c_int32), ("_reserved", ctypes.c_int32 * 3)]
 
 
 class GnxError(RuntimeError):
@@ -132,6 +138,14 @@ def lib():
         L.gnx_best_of_by_offset.restype = ctypes.c_int
         L.gnx_best_of_windows.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, c_p, c_p, i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_p)]
         L.gnx_best_of_windows.restype = ctypes.c_int
+        L.gnx_reference_index_build.argtypes = [ctypes.c_int, ctypes.c_int]
+        L.gnx_reference_index_build.restype = ctypes.c_int
+        L.gnx_reference_index_info.argtypes = [ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+        L.gnx_reference_index_info.restype = ctypes.c_int
+        L.gnx_reference_index_get.argtypes = [ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(i64)]
+        L.gnx_reference_index_get.restype = ctypes.c_int
+        L.gnx_seed_candidates.argtypes = [ctypes.POINTER(GnxSeedVoteOpts), i64, c_p, c_p] + [ctypes.POINTER(c_p)] * 5
+        L.gnx_seed_candidates.restype = ctypes.c_int
         L.gnx_seed_index_build.argtypes = [c_p, c_p, i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(i64)]
         L.gnx_seed_index_build.restype = ctypes.c_int
         L.gnx_seed_index_set.argtypes = [c_p, c_p, i64, c_p, c_p, i64, ctypes.c_int]
@@ -506,6 +520,51 @@ def best_of_by_offset(params, read_cat, read_off, cand_off, cand_start, cand_len
 def best_of_windows(params, read_cat, read_off, target_buf, cand_off, cand_start, cand_len, cand_strand, cigar=True, target_end=None):
     """gnx_best_of_windows: the same with the windows taken from target_buf."""
     return _best_of(params, read_cat, read_off, target_buf, cand_off, cand_start, cand_len, cand_strand, cigar, target_end)
+
+
+# ---- candidates by seed votes (gnx_reference_index_*, gnx_seed_candidates): an index of the resident reference, reads -> candidate tables ----
+def reference_index_build(seed_len, seed_step=1):
+    check(lib().gnx_reference_index_build(int(seed_len), int(seed_step)))
+
+
+def reference_index_info():
+    """{"n_kmers", "device_bytes", "seed_len", "seed_step"} of the index of the resident reference"""
+    n, b, k, s = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int(), ctypes.c_int()
+    check(lib().gnx_reference_index_info(ctypes.byref(n), ctypes.byref(b), ctypes.byref(k), ctypes.byref(s)))
+    return {"n_kmers": n.value, "device_bytes": b.value, "seed_len": k.value, "seed_step": s.value}
+
+
+def _take_array(ptr, n, ctype, dtype):
+    out = np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctype)), shape=(n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype)
+    lib().gnx_free(ptr)
+    return out
+
+
+def reference_index_get():
+    """(keys, positions) of the index as uint64 arrays, sorted by key, equal keys in ascending position"""
+    kp, pp, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+    check(lib().gnx_reference_index_get(ctypes.byref(kp), ctypes.byref(pp), ctypes.byref(n)))
+    return _take_array(kp, n.value, ctypes.c_uint64, np.uint64), _take_array(pp, n.value, ctypes.c_uint64, np.uint64)
+
+
+def seed_vote_opts(max_occ, bin, pad, max_cand, min_votes):
+    o = GnxSeedVoteOpts()
+    o.max_occ, o.bin, o.pad, o.max_cand, o.min_votes = int(max_occ), int(bin), int(pad), int(max_cand), int(min_votes)
+    return o
+
+
+def seed_candidates(read_cat, read_off, max_occ, bin, pad, max_cand, min_votes):
+    """gnx_seed_candidates: (cand_off[n + 1], cand_start, cand_len, cand_strand, cand_votes) -- the first four are the candidate
+    tables best_of_by_offset takes."""
+    read_cat, read_off = _u8(read_cat), _i64(read_off)
+    n = int(read_off.shape[0]) - 1
+    o = seed_vote_opts(max_occ, bin, pad, max_cand, min_votes)
+    ptrs = [ctypes.c_void_p() for _ in range(5)]
+    check(lib().gnx_seed_candidates(ctypes.byref(o), n, read_cat.ctypes.data, read_off.ctypes.data, *[ctypes.byref(p) for p in ptrs]))
+    off = _take_array(ptrs[0], n + 1, ctypes.c_int64, np.int64)
+    nc = int(off[-1])
+    return (off, _take_array(ptrs[1], nc, ctypes.c_int64, np.int64), _take_array(ptrs[2], nc, ctypes.c_int64, np.int64),
+            _take_array(ptrs[3], nc, ctypes.c_uint8, np.uint8), _take_array(ptrs[4], nc, ctypes.c_int32, np.int32))
 
 
 def _chunk_pairs(alphas, betas):

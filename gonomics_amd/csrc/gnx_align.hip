@@ -53,6 +53,7 @@
 #include "score_sweep.hip.h"
 #include "n1_sweep.hip.h"
 #include "span_origin.hip.h"
+#include "ref_seeds.hip.h"
 
 namespace {
 
@@ -141,6 +142,10 @@ struct Ctx {
     DevBuf sd_keys, sd_locs, sd_nodes, sd_node_off, sd_word_off, sd_words, sd_tmp[8];
     DevBuf bo[13]; // gnx_best_of_* (gnx_host.hip.h, BO_*): reads + reverse complements, candidate tables and scores, per-read winners, the winners' tables
     int64_t sd_n = -1, sd_nodes_n = 0; int sd_seed_len = 0;
+    // k-mer index of the resident reference (gnx_reference_index_build; context 0 only) and the scratch of gnx_seed_candidates (RS_*)
+    DevBuf ri_keys, ri_pos, ri_dir, rs[15];
+    int ri_dir_bits = 0; // ri_dir: 2^bits + 1 first entries by key prefix (ref_index_dir_kernel)
+    int64_t ri_n = -1, ri_epoch = 0; int ri_seed_len = 0, ri_seed_step = 0; // ri_n >= 0: an index of that many k-mers of the reference of epoch ri_epoch is built
     PinBuf h_plans; // host-side plans of the general path
     PinBuf st_a[2], st_as[2], st_b[2], st_bs[2];
     // the resident reference, PACKED (gnx_host.hip.h: pack_reference): `ref` = 2 bits per base, ref_flag / ref_rank / ref_exc = the
@@ -2689,6 +2694,14 @@ int run_score_sweep(const gnx_params *prm, int64_t n_pairs, const uint8_t *d_a, 
     return GNX_OK;
 }
 
+// the k-mer index belongs to the resident reference: whatever replaces or releases the reference drops it (with its scratch)
+void drop_reference_index(Ctx &c) {
+    c.ri_n = -1;
+    c.ri_keys.release(); c.ri_pos.release(); c.ri_dir.release();
+    for (DevBuf &b : c.rs) b.release();
+}
+std::atomic<int64_t> g_sv_lds{0}, g_sv_slab{0}; // reads voted with the table in LDS / in a slab (gnx_debug_counter(7 / 8))
+
 } // namespace
 
 #include "gnx_host.hip.h"
@@ -2785,6 +2798,7 @@ void gnx_shutdown(void) {
                           &c.sd_tmp[0], &c.sd_tmp[1], &c.sd_tmp[2], &c.sd_tmp[3], &c.sd_tmp[4], &c.sd_tmp[5], &c.sd_tmp[6], &c.sd_tmp[7]};
         for (DevBuf *b : bufs) b->release();
         for (DevBuf &b : c.bo) b.release();
+        drop_reference_index(c);
         PinBuf *pins[] = {&c.h_plans, &c.st_a[0], &c.st_a[1], &c.st_as[0], &c.st_as[1], &c.st_b[0], &c.st_b[1], &c.st_bs[0], &c.st_bs[1]};
         for (PinBuf *b : pins) b->release();
         c.fpc_ptr = nullptr; c.ref_len = -1; c.sd_n = -1;
@@ -3484,6 +3498,271 @@ static int seed_find_locked(const uint8_t *read_cat, const int64_t *read_off, in
     return GNX_OK;
 }
 
+/* ---- k-mer index of the resident reference, candidate windows by seed votes (ref_seeds.hip.h) ---- */
+namespace {
+KParams ref_kparams(const Ctx &c) {
+    KParams k;
+    memset(&k, 0, sizeof(k));
+    k.b2 = (const unsigned *)c.ref.p; k.bflag = (const unsigned long long *)c.ref_flag.p; k.brank = (const unsigned *)c.ref_rank.p; k.bexc = (const unsigned long long *)c.ref_exc.p;
+    return k;
+}
+bool reference_index_live(const Ctx &c) { return c.inited && c.ref_len >= 0 && c.ri_n >= 0 && c.ri_epoch == c.ref_epoch; }
+struct TmpBufs { DevBuf b[5]; ~TmpBufs() { for (DevBuf &x : b) x.release(); } };
+struct IndexGuard { Ctx &c; bool keep = false; ~IndexGuard() { if (!keep) drop_reference_index(c); } }; // a failed build leaves nothing half-built
+enum { RS_READS, RS_ROFF, RS_SOFF, RS_FIRST, RS_OCC, RS_HITS, RS_STAGE, RS_CNT, RS_COFF, RS_ITEMS, RS_SLAB, RS_CSTART, RS_CLEN, RS_CSTRAND, RS_CVOTES, RS_COUNT };
+static_assert(RS_COUNT == sizeof(Ctx::rs) / sizeof(DevBuf), "Ctx::rs holds one buffer per RS_* index");
+} // namespace
+
+int gnx_reference_index_build(int seed_len, int seed_step) {
+    std::lock_guard<std::mutex> api(g_api_mu);
+    CtxScope sc(ctx_at(0));
+    g_err[0] = 0;
+    if (seed_len < 8 || seed_len > 32 || seed_step < 1) { set_err("gnx_reference_index_build: seed_len must be 8 .. 32 and seed_step >= 1%s", ""); return GNX_EINVAL; }
+    Ctx &c = g_ctx;
+    if (!c.inited || c.ref_len < 0) { set_err("no resident reference: call gnx_set_reference first%s", ""); return GNX_EINVAL; }
+    int rc = ensure_init();
+    if (rc) return rc;
+    hipStream_t st = c.own_stream;
+    drop_reference_index(c); // a second build replaces the first
+    IndexGuard guard{c};
+    TmpBufs tmp;
+    DevBuf &flag = tmp.b[0], &off = tmp.b[1], &ck = tmp.b[2], &cp = tmp.b[3], &sort_tmp = tmp.b[4];
+    const int64_t L = c.ref_len, n_slots = L >= seed_len ? (L - seed_len) / seed_step + 1 : 0;
+    int64_t chunk = (int64_t)1 << 24; // positions flagged, scanned and compacted per pass: 256 MB of scratch whatever the reference
+    if (const char *e = getenv("GNX_REF_INDEX_SUB")) chunk = std::min<int64_t>(std::max<int64_t>(atoll(e), 1), 0x7ffffff0);
+    chunk = std::min(chunk, std::max<int64_t>(n_slots, 1));
+    int64_t n_kmers = 0;
+    if (n_slots > 0) {
+        if ((rc = flag.ensure((size_t)(chunk + 1) * 8)) || (rc = off.ensure((size_t)(chunk + 1) * 8)) || (rc = ck.ensure((size_t)n_slots * 8)) || (rc = cp.ensure((size_t)n_slots * 8)) ||
+            (rc = c.misc.ensure(64))) return rc;
+        HIPCHK(hipMemsetAsync(c.misc.p, 0, 64, st));
+        int64_t *d_carry = reinterpret_cast<int64_t *>(reinterpret_cast<char *>(c.misc.p) + 16);
+        const KParams kp = ref_kparams(c);
+        for (int64_t s0 = 0; s0 < n_slots; s0 += chunk) {
+            const int64_t n = std::min(chunk, n_slots - s0);
+            const unsigned gb = (unsigned)((n + 255) / 256);
+            hipLaunchKernelGGL(ref_index_flag_kernel, dim3(gb), dim3(256), 0, st, kp, s0, n, seed_len, seed_step, (int64_t *)flag.p);
+            HIPCHK(hipGetLastError());
+            if ((rc = launch_scan((const int64_t *)flag.p, (int)n, (int64_t *)off.p, d_carry, st))) return rc; // (the carry runs on from chunk to chunk)
+            hipLaunchKernelGGL(ref_index_emit_kernel, dim3(gb), dim3(256), 0, st, kp, s0, n, seed_len, seed_step, (const int64_t *)flag.p, (const int64_t *)off.p, (uint64_t *)ck.p, (uint64_t *)cp.p);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(&n_kmers, d_carry, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    if (n_kmers > 0) {
+        if ((rc = c.ri_keys.ensure((size_t)n_kmers * 8)) || (rc = c.ri_pos.ensure((size_t)n_kmers * 8))) return rc;
+        size_t tmp_bytes = 0;
+        HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, (uint64_t *)ck.p, (uint64_t *)c.ri_keys.p, (uint64_t *)cp.p, (uint64_t *)c.ri_pos.p, (size_t)n_kmers, 0u, (unsigned)(2 * seed_len), st));
+        if ((rc = sort_tmp.ensure(tmp_bytes + 16))) return rc;
+        // stable LSD radix sort: equal keys keep the compaction's order, ascending position
+        HIPCHK(rocprim::radix_sort_pairs(sort_tmp.p, tmp_bytes, (uint64_t *)ck.p, (uint64_t *)c.ri_keys.p, (uint64_t *)cp.p, (uint64_t *)c.ri_pos.p, (size_t)n_kmers, 0u, (unsigned)(2 * seed_len), st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    // the directory: one entry per prefix of about log2(k-mers) bits, 24 at the most (128 MB), so that a lookup bisects a handful of entries
+    int bits = 8;
+    while (bits < 24 && ((int64_t)1 << bits) < n_kmers) bits++;
+    bits = std::min(bits, 2 * seed_len);
+    const int64_t n_dir = (int64_t)1 << bits;
+    if ((rc = c.ri_dir.ensure((size_t)(n_dir + 1) * 8)) || (rc = c.ri_keys.ensure(8))) return rc;
+    hipLaunchKernelGGL(ref_index_dir_kernel, dim3((unsigned)((n_dir + 1 + 255) / 256)), dim3(256), 0, st, (const uint64_t *)c.ri_keys.p, n_kmers, 2 * seed_len - bits, n_dir, (int64_t *)c.ri_dir.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    c.ri_n = n_kmers; c.ri_epoch = c.ref_epoch; c.ri_seed_len = seed_len; c.ri_seed_step = seed_step; c.ri_dir_bits = bits;
+    guard.keep = true;
+    return GNX_OK;
+}
+
+int gnx_reference_index_info(int64_t *out_n_kmers, int64_t *out_device_bytes, int *out_seed_len, int *out_seed_step) {
+    std::lock_guard<std::mutex> api(g_api_mu);
+    Ctx &c = ctx_at(0);
+    CtxScope sc(c);
+    g_err[0] = 0;
+    if (!reference_index_live(c)) { set_err("no reference index: call gnx_reference_index_build first%s", ""); return GNX_EINVAL; }
+    if (out_n_kmers) *out_n_kmers = c.ri_n;
+    if (out_device_bytes) *out_device_bytes = c.ri_n * 16 + (((int64_t)1 << c.ri_dir_bits) + 1) * 8; // keys, positions, the prefix directory
+    if (out_seed_len) *out_seed_len = c.ri_seed_len;
+    if (out_seed_step) *out_seed_step = c.ri_seed_step;
+    return GNX_OK;
+}
+
+int gnx_reference_index_get(uint64_t **out_keys, uint64_t **out_pos, int64_t *out_n) {
+    std::lock_guard<std::mutex> api(g_api_mu);
+    Ctx &c = ctx_at(0);
+    CtxScope sc(c);
+    g_err[0] = 0;
+    if (!out_keys || !out_pos || !out_n) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (!reference_index_live(c)) { set_err("no reference index: call gnx_reference_index_build first%s", ""); return GNX_EINVAL; }
+    int rc = ensure_init();
+    if (rc) return rc;
+    const size_t bytes = (size_t)c.ri_n * 8;
+    uint64_t *hk = (uint64_t *)malloc(std::max<size_t>(bytes, 8)), *hp = (uint64_t *)malloc(std::max<size_t>(bytes, 8));
+    if (!hk || !hp) { free(hk); free(hp); set_err("host allocation failed%s", ""); return GNX_ENOMEM; }
+    if (bytes && (hipMemcpy(hk, c.ri_keys.p, bytes, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hp, c.ri_pos.p, bytes, hipMemcpyDeviceToHost) != hipSuccess)) {
+        free(hk); free(hp); set_err("D2H of the index failed%s", ""); return GNX_EDEVICE;
+    }
+    *out_keys = hk; *out_pos = hp; *out_n = c.ri_n;
+    return GNX_OK;
+}
+
+int gnx_seed_candidates(const gnx_seed_vote_opts *o, int64_t n_reads, const uint8_t *read_cat, const int64_t *read_off,
+                        int64_t **out_cand_off, int64_t **out_cand_start, int64_t **out_cand_len, uint8_t **out_cand_strand, int32_t **out_cand_votes) {
+    std::lock_guard<std::mutex> api(g_api_mu);
+    const auto t_entry = std::chrono::steady_clock::now();
+    CtxScope sc(ctx_at(0));
+    g_err[0] = 0;
+    // ---- argument checks: everything that needs no device ----
+    if (!o || n_reads < 0 || n_reads > 0x7ffffff0 || !read_off || !out_cand_off || !out_cand_start || !out_cand_len || !out_cand_strand || !out_cand_votes) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (o->max_occ < 1 || o->bin < 8 || o->pad < 0 || o->max_cand < 1 || o->max_cand > 64 || o->min_votes < 1) { set_err("gnx_seed_candidates: an option is out of range (max_occ >= 1, bin >= 8, pad >= 0, max_cand 1 .. 64, min_votes >= 1)%s", ""); return GNX_EINVAL; }
+    if (read_off[0] < 0) { set_err("read_off must start at >= 0%s", ""); return GNX_EINVAL; }
+    int64_t maxlen = 0;
+    for (int64_t r = 0; r < n_reads; r++) {
+        if (read_off[r + 1] < read_off[r]) { set_err("decreasing offsets at read %s%lld", "", (long long)r); return GNX_EINVAL; }
+        maxlen = std::max(maxlen, read_off[r + 1] - read_off[r]);
+    }
+    if (read_off[n_reads] > read_off[0] && !read_cat) { set_err("null read buffer%s", ""); return GNX_EINVAL; }
+    for (int64_t x = read_off[0]; x < read_off[n_reads]; x++)
+        if (read_cat[x] >= 5) { set_err("a base >= 5 was found: the reference would panic (index out of range)%s", ""); return GNX_EBASE; }
+    int rc = ensure_init();
+    if (rc) return rc;
+    Ctx &c = g_ctx;
+    if (!reference_index_live(c)) { set_err("no reference index: call gnx_reference_index_build after gnx_set_reference%s", ""); return GNX_EINVAL; }
+    const int k = c.ri_seed_len, max_cand = o->max_cand;
+    const int64_t L = c.ref_len;
+    if ((L + maxlen) / o->bin + 4 >= ((int64_t)1 << 30)) { set_err("gnx_seed_candidates: more than 2^30 diagonal bins: use a wider bin%s", ""); return GNX_EINVAL; }
+    hipStream_t st = c.own_stream;
+    DevBuf *rs = c.rs;
+    const char *e_lds = getenv("GNX_SEED_VOTE_LDS");
+    const bool use_lds = !(e_lds && e_lds[0] == '0');
+    int64_t sub = std::min<int64_t>(std::max<int64_t>(c.ws_limit / 64, (int64_t)1 << 20), (int64_t)1 << 28); // hits per vote launch: a slab takes at most 32 bytes per hit
+    if (const char *e = getenv("GNX_SEED_SUB")) sub = std::max<int64_t>(atoll(e), 1);
+    const int64_t slot_cap = (int64_t)1 << 25, read_cap = std::max<int64_t>(((int64_t)1 << 25) / max_cand, 1); // slot tables of 400 MB, staged candidates of 256 MB at the most
+
+    std::vector<int64_t> h_coff((size_t)n_reads + 1, 0), v_start, v_len;
+    std::vector<uint8_t> v_strand;
+    std::vector<int32_t> v_votes;
+    gnx_timing tsum = {};
+    int64_t n_lds_reads = 0, n_slab_reads = 0;
+    auto npos_of = [&](int64_t r) { return std::max<int64_t>(read_off[r + 1] - read_off[r] - k + 1, 0); };
+    for (int64_t p0 = 0; p0 < n_reads;) {
+        // ---- a piece of the batch: reads [p0, p1) ----
+        int64_t p1 = p0, n_slots = 0;
+        while (p1 < n_reads && (p1 == p0 || (n_slots + 2 * npos_of(p1) <= slot_cap && p1 - p0 < read_cap))) { n_slots += 2 * npos_of(p1); p1++; }
+        const int64_t np = p1 - p0, b_lo = read_off[p0], b_len = read_off[p1] - b_lo;
+        if (n_slots > 0x7ffffff0) { set_err("read %s%lld is too long for gnx_seed_candidates", "", (long long)p0); return GNX_EINVAL; }
+        if (n_slots == 0) { for (int64_t r = p0; r < p1; r++) h_coff[(size_t)r + 1] = h_coff[(size_t)r]; p0 = p1; continue; }
+        std::vector<int64_t> h_roff((size_t)np + 1), h_soff((size_t)np + 1, 0);
+        for (int64_t r = 0; r <= np; r++) h_roff[(size_t)r] = read_off[p0 + r] - b_lo;
+        for (int64_t r = 0; r < np; r++) h_soff[(size_t)r + 1] = h_soff[(size_t)r] + 2 * npos_of(p0 + r);
+        if ((rc = rs[RS_READS].ensure((size_t)b_len + 16)) || (rc = rs[RS_ROFF].ensure((size_t)(np + 1) * 8)) || (rc = rs[RS_SOFF].ensure((size_t)(np + 1) * 8)) ||
+            (rc = rs[RS_FIRST].ensure((size_t)n_slots * 8)) || (rc = rs[RS_OCC].ensure((size_t)n_slots * 4)) || (rc = rs[RS_HITS].ensure((size_t)np * 8)) ||
+            (rc = rs[RS_STAGE].ensure((size_t)np * max_cand * 8)) || (rc = rs[RS_CNT].ensure((size_t)(np + 1) * 8)) || (rc = rs[RS_COFF].ensure((size_t)(np + 1) * 8)) || (rc = c.misc.ensure(64))) return rc;
+        HIPCHK(hipMemcpyAsync(rs[RS_READS].p, read_cat + b_lo, (size_t)b_len, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(rs[RS_ROFF].p, h_roff.data(), (size_t)(np + 1) * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(rs[RS_SOFF].p, h_soff.data(), (size_t)(np + 1) * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(rs[RS_HITS].p, 0, (size_t)np * 8, st));
+        HIPCHK(hipMemsetAsync(rs[RS_CNT].p, 0, (size_t)(np + 1) * 8, st));
+        HIPCHK(hipMemsetAsync(c.misc.p, 0, 64, st));
+        SeedVoteArgs a;
+        a.keys = (const uint64_t *)c.ri_keys.p; a.pos = (const uint64_t *)c.ri_pos.p; a.n_index = c.ri_n;
+        a.dir = (const int64_t *)c.ri_dir.p; a.dir_shift = 2 * k - c.ri_dir_bits;
+        a.reads = (const uint8_t *)rs[RS_READS].p; a.read_off = (const int64_t *)rs[RS_ROFF].p; a.slot_off = (const int64_t *)rs[RS_SOFF].p;
+        a.first = (int64_t *)rs[RS_FIRST].p; a.occ = (int *)rs[RS_OCC].p; a.hits = (unsigned long long *)rs[RS_HITS].p;
+        a.stage = (unsigned long long *)rs[RS_STAGE].p; a.cnt = (int64_t *)rs[RS_CNT].p;
+        a.ref_len = L; a.seed_len = k; a.max_occ = o->max_occ; a.bin = o->bin; a.pad = o->pad; a.max_cand = max_cand; a.min_votes = o->min_votes;
+        a.bin_shift = (o->bin & (o->bin - 1)) == 0 ? __builtin_ctz((unsigned)o->bin) : -1;
+        // ---- stage 1: lookup and count ----
+        HIPCHK(hipEventRecord(c.ev[0], st));
+        hipLaunchKernelGGL(ref_seed_lookup_kernel, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, st, a, (int)np, n_slots);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c.ev[1], st));
+        std::vector<int64_t> h_hits((size_t)np);
+        HIPCHK(hipMemcpyAsync(h_hits.data(), rs[RS_HITS].p, (size_t)np * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st)); // (h_roff / h_soff are locals, too)
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+        tsum.fill_ms += ms; tsum.total_ms += ms;
+        // ---- stage 2: vote and select, in sub-batches of `sub` hits (a read with more runs alone) ----
+        for (int64_t q0 = 0; q0 < np;) {
+            int64_t q1 = q0, acc = 0;
+            while (q1 < np && (q1 == q0 || acc + h_hits[(size_t)q1] <= sub)) { acc += h_hits[(size_t)q1]; q1++; }
+            std::vector<VoteItem> items_lds, items_slab;
+            int64_t slab_slots = 0;
+            for (int64_t r = q0; r < q1; r++) {
+                const int64_t h = h_hits[(size_t)r];
+                if (h == 0) continue; // (its count stays 0)
+                VoteItem it;
+                it.read = (int32_t)r; it.lg = 10; it.slab_off = 0;
+                if (use_lds && 2 * h <= VOTE_LDS_SLOTS) { items_lds.push_back(it); continue; }
+                int lg = 6;
+                while (lg <= 30 && ((int64_t)1 << lg) < 2 * h) lg++;
+                if (lg > 30) { set_err("read %s%lld has too many seed hits for one vote table: lower max_occ", "", (long long)(p0 + r)); return GNX_ENOMEM; }
+                it.lg = lg; it.slab_off = slab_slots; slab_slots += (int64_t)1 << lg;
+                items_slab.push_back(it);
+            }
+            const int64_t n_l = (int64_t)items_lds.size(), n_s = (int64_t)items_slab.size();
+            q0 = q1;
+            if (n_l + n_s == 0) continue;
+            if ((rc = rs[RS_ITEMS].ensure((size_t)(n_l + n_s) * sizeof(VoteItem))) || (rc = rs[RS_SLAB].ensure((size_t)std::max<int64_t>(slab_slots, 1) * 8))) return rc;
+            VoteItem *d_items = (VoteItem *)rs[RS_ITEMS].p;
+            if (n_l) HIPCHK(hipMemcpyAsync(d_items, items_lds.data(), (size_t)n_l * sizeof(VoteItem), hipMemcpyHostToDevice, st));
+            if (n_s) HIPCHK(hipMemcpyAsync(d_items + n_l, items_slab.data(), (size_t)n_s * sizeof(VoteItem), hipMemcpyHostToDevice, st));
+            if (n_s) HIPCHK(hipMemsetAsync(rs[RS_SLAB].p, 0, (size_t)slab_slots * 8, st));
+            HIPCHK(hipEventRecord(c.ev[2], st));
+            if (n_l) hipLaunchKernelGGL(ref_seed_vote_kernel<true>, dim3((unsigned)n_l), dim3(64), 0, st, a, (const VoteItem *)d_items, (unsigned *)nullptr);
+            if (n_s) hipLaunchKernelGGL(ref_seed_vote_kernel<false>, dim3((unsigned)n_s), dim3(64), 0, st, a, (const VoteItem *)(d_items + n_l), (unsigned *)rs[RS_SLAB].p);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(c.ev[3], st));
+            HIPCHK(hipStreamSynchronize(st)); // (the item lists are locals)
+            HIPCHK(hipEventElapsedTime(&ms, c.ev[2], c.ev[3]));
+            tsum.fill_ms += ms; tsum.dominant_ms += ms; tsum.total_ms += ms; tsum.cells += acc;
+            tsum.n_launches++; tsum.dominant_launches += (n_l ? 1 : 0) + (n_s ? 1 : 0);
+            n_lds_reads += n_l; n_slab_reads += n_s;
+        }
+        // ---- stage 3: the windows, compacted behind a scan of the counts ----
+        int64_t *d_carry = reinterpret_cast<int64_t *>(reinterpret_cast<char *>(c.misc.p) + 16);
+        HIPCHK(hipEventRecord(c.ev[4], st));
+        if ((rc = launch_scan((const int64_t *)rs[RS_CNT].p, (int)np, (int64_t *)rs[RS_COFF].p, d_carry, st))) return rc;
+        int64_t n_cand = 0;
+        HIPCHK(hipMemcpyAsync(&n_cand, d_carry, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const int64_t base = h_coff[(size_t)p0];
+        std::vector<int64_t> p_coff((size_t)np + 1, 0);
+        if (n_cand > 0) {
+            if ((rc = rs[RS_CSTART].ensure((size_t)n_cand * 8)) || (rc = rs[RS_CLEN].ensure((size_t)n_cand * 8)) || (rc = rs[RS_CSTRAND].ensure((size_t)n_cand)) || (rc = rs[RS_CVOTES].ensure((size_t)n_cand * 4))) return rc;
+            hipLaunchKernelGGL(ref_seed_windows_kernel, dim3((unsigned)((np * max_cand + 255) / 256)), dim3(256), 0, st, a, np, (const int64_t *)rs[RS_COFF].p,
+                               (int64_t *)rs[RS_CSTART].p, (int64_t *)rs[RS_CLEN].p, (uint8_t *)rs[RS_CSTRAND].p, (int32_t *)rs[RS_CVOTES].p);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(c.ev[5], st));
+            v_start.resize((size_t)(base + n_cand)); v_len.resize((size_t)(base + n_cand)); v_strand.resize((size_t)(base + n_cand)); v_votes.resize((size_t)(base + n_cand));
+            HIPCHK(hipMemcpyAsync(p_coff.data(), rs[RS_COFF].p, (size_t)(np + 1) * 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(v_start.data() + base, rs[RS_CSTART].p, (size_t)n_cand * 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(v_len.data() + base, rs[RS_CLEN].p, (size_t)n_cand * 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(v_strand.data() + base, rs[RS_CSTRAND].p, (size_t)n_cand, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(v_votes.data() + base, rs[RS_CVOTES].p, (size_t)n_cand * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            HIPCHK(hipEventElapsedTime(&ms, c.ev[4], c.ev[5]));
+            tsum.total_ms += ms;
+        }
+        for (int64_t r = 0; r < np; r++) h_coff[(size_t)(p0 + r) + 1] = base + (n_cand > 0 ? p_coff[(size_t)r + 1] : 0);
+        p0 = p1;
+    }
+    // ---- results: malloc'd arrays (gnx_free); nothing was written before this point ----
+    const int64_t total = h_coff[(size_t)n_reads];
+    int64_t *r_off = (int64_t *)malloc((size_t)(n_reads + 1) * 8), *r_start = (int64_t *)malloc((size_t)std::max<int64_t>(total, 1) * 8), *r_len = (int64_t *)malloc((size_t)std::max<int64_t>(total, 1) * 8);
+    uint8_t *r_strand = (uint8_t *)malloc((size_t)std::max<int64_t>(total, 1));
+    int32_t *r_votes = (int32_t *)malloc((size_t)std::max<int64_t>(total, 1) * 4);
+    if (!r_off || !r_start || !r_len || !r_strand || !r_votes) { free(r_off); free(r_start); free(r_len); free(r_strand); free(r_votes); set_err("host allocation failed%s", ""); return GNX_ENOMEM; }
+    memcpy(r_off, h_coff.data(), (size_t)(n_reads + 1) * 8);
+    if (total) { memcpy(r_start, v_start.data(), (size_t)total * 8); memcpy(r_len, v_len.data(), (size_t)total * 8); memcpy(r_strand, v_strand.data(), (size_t)total); memcpy(r_votes, v_votes.data(), (size_t)total * 4); }
+    *out_cand_off = r_off; *out_cand_start = r_start; *out_cand_len = r_len; *out_cand_strand = r_strand; *out_cand_votes = r_votes;
+    g_sv_lds += n_lds_reads; g_sv_slab += n_slab_reads;
+    tsum.fast_path = 11; tsum.n_contexts = 1;
+    tsum.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count();
+    c.timing = tsum;
+    return GNX_OK;
+}
+
 /* diagnostics (refused unless the process runs with GNX_DEBUG_ENTRY=1: a production caller cannot park the GPU by accident):
  * n_workgroups workgroups that each hold a whole CU's LDS and spin for `milliseconds`, on a stream of their own; returns
  * at once.  The stress leg of the claim protocol (tests/test_ticket.py): piped launches must finish with half the CUs taken away. */
@@ -3508,7 +3787,13 @@ int gnx_debug_counter(int which, int reset, int64_t *out) {
     std::lock_guard<std::mutex> api(g_api_mu);
     CtxScope sc(ctx_at(0));
     g_err[0] = 0;
-    if (which < 0 || which > 6 || !out) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (which < 0 || which > 8 || !out) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (which >= 7) { // gnx_seed_candidates: reads voted with the table in LDS / in a slab
+        std::atomic<int64_t> &v = which == 7 ? g_sv_lds : g_sv_slab;
+        *out = v.load();
+        if (reset) v = 0;
+        return GNX_OK;
+    }
     if (which == 1 || which == 2) { // combined gnx_align_pair batches run / pairs served by them
         *out = which == 1 ? g_pq_batches.load() : g_pq_pairs.load();
         if (reset) { if (which == 1) g_pq_batches = 0; else g_pq_pairs = 0; }

@@ -199,6 +199,7 @@ int set_reference_packed(const uint8_t *ref, int64_t len, uint64_t seed) {
         HIPCHK(hipSetDevice(c0.device));
         hipStream_t st = c0.own_stream;
         c0.ref_len = -1;
+        drop_reference_index(c0); // (before anything can fail: an index never outlives the reference it was built from)
         if (len == 0) { // release: every context gives the reference (and the unpacked-window scratch) back; nothing is re-allocated
             int n_all0; { std::lock_guard<std::mutex> lk(g_ctxs_mu); n_all0 = (int)g_ctxs.size(); }
             for (int d = 0; d < n_all0; d++) {

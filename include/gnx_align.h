@@ -103,6 +103,8 @@ typedef struct gnx_timing {
                             gnx_multiple_affine_gap_score_batch; n1_sweep.hip.h);
                             10: the local sweep (8) followed by the origin-carrying window DP ran (gnx_locate_span_*;
                             span_origin.hip.h): fill_ms and total_ms cover both stages, dominant_ms is the sweep's.
+                            11: gnx_seed_candidates ran (ref_seeds.hip.h): fill_ms = lookup + vote kernels, dominant_ms = the vote kernels, cells = seed
+                            hits that voted, n_launches = vote sub-batches.
                             Multi-context score calls report the maximum over contexts. */
     int32_t _pad;
     /* host-buffer entry points only (wall clock inside the library): */
@@ -325,6 +327,48 @@ int gnx_best_of_windows(const gnx_params *p, int64_t n_reads, const uint8_t *rea
                         int32_t *out_best, int64_t *out_score, int64_t *out_target_end, int64_t *out_cand_score,
                         gnx_cigar **out_ops, int64_t **out_ops_off);
 
+/* ---- candidate windows for gnx_best_of_by_offset: a k-mer index of the resident reference and seed votes (an extension, no Go signature) -- */
+/* Index of the resident reference (gnx_set_reference / _synthetic), built on the device from the packed words and kept there, on context 0.
+ * 8 <= seed_len <= 32 and seed_step >= 1, else GNX_EINVAL; no resident reference: GNX_EINVAL (a reference of 0 bases is none).  Positions
+ * p = 0, seed_step, 2 * seed_step, ... with p + seed_len <= len; key = the 2-bit code of ref[p .. p + seed_len), first base most significant
+ * (dnaToNumber, /root/reference/genomeGraph/align.go:170); a k-mer that touches a base that is not A C G T (N, a byte >= 5) is skipped.  Two
+ * device arrays sorted by key, equal keys in ascending position, positions 64-bit (16 bytes per k-mer), and a directory of first entries by
+ * key prefix beside them (about one entry per k-mer, 128 MB at the most).  The index belongs to the reference: gnx_set_reference (also
+ * with len = 0), gnx_set_reference_synthetic and gnx_shutdown drop it, a second build replaces the first; a failed build (GNX_ENOMEM) leaves
+ * none.  It shares nothing with the graph aligner's seed index (gnx_seed_index_*) or its generation.  GNX_REF_INDEX_SUB=<positions> (read per
+ * call) sets how many positions one compaction pass takes (default 2^24). */
+int gnx_reference_index_build(int seed_len, int seed_step);
+/* What is built (every pointer may be NULL): k-mers, bytes of device memory, the build's arguments.  No index: GNX_EINVAL. */
+int gnx_reference_index_info(int64_t *out_n_kmers, int64_t *out_device_bytes, int *out_seed_len, int *out_seed_step);
+/* A host copy of the index (tests, debugging): malloc'd, gnx_free.  No index: GNX_EINVAL. */
+int gnx_reference_index_get(uint64_t **out_keys, uint64_t **out_pos, int64_t *out_n);
+
+typedef struct gnx_seed_vote_opts {
+    int32_t max_occ;    /* a k-mer with more index entries than this is ignored (repeats); >= 1 */
+    int32_t bin;        /* width of a diagonal bin in bases; >= 8 */
+    int32_t pad;        /* bases added on either side of a bin's window; >= 0 */
+    int32_t max_cand;   /* candidates kept per read, 1 .. 64 */
+    int32_t min_votes;  /* a bin with fewer votes is no candidate; >= 1 */
+    int32_t _reserved[3];
+} gnx_seed_vote_opts;
+/* Reads in, the candidate tables of gnx_best_of_by_offset out.  k = the index's seed length, L = the length of the resident reference.
+ * Contract, per read r of n bases and strand s (0: x = the read; 1: x = its reverse complement as gnx_best_of_* defines it):
+ *   for every q in 0 .. n - k with x[q .. q + k) all A C G T: occ = the number of index entries of its code; occ == 0 or occ > max_occ: nothing;
+ *   else every entry's position t casts one vote for (s, b), b = floor((t - q) / bin) -- floor, not truncation: t - q goes down to -(n - k).
+ *   Candidates = the (s, b) with votes >= min_votes, ordered by votes descending, then strand ascending, then b ascending; the first max_cand
+ *   are kept.  Candidate (s, b): start = clamp(b * bin - pad, 0, L), end = clamp((b + 1) * bin + n + pad, 0, L), len = end - start (>= k),
+ *   strand = s.  A read shorter than k, or without a surviving bin, has no candidates.
+ * Outputs (malloc'd, gnx_free): (*out_cand_off)[n_reads + 1] starting at 0, and per candidate start, len, strand -- the layout of
+ * gnx_best_of_by_offset's inputs -- and votes.  The result does not depend on launch geometry, sub-batch cuts or execution order.
+ * Return codes, all before any output is written: GNX_EINVAL for a null pointer, a negative count, a decreasing read_off, an option outside
+ * its range, more than 2^30 diagonal bins ((L + n) / bin), or no index built; GNX_EBASE for a byte >= 5 in any read; GNX_EDEVICE without a
+ * device, after the argument checks; GNX_ENOMEM when a vote table does not fit; n_reads == 0: GNX_OK with cand_off = {0}.  Never GNX_ERANGE.
+ * Runs on context 0.  The vote table of a read lives in LDS (up to 512 hits) or in a slab of device memory; launches are cut by total hits
+ * so that the slabs stay inside the workspace limit of gnx_init.  Switches, read per call: GNX_SEED_VOTE_LDS=0 sends every read to the slab
+ * form; GNX_SEED_SUB=<hits> sets the hits per vote launch.  gnx_get_timing afterwards: fast_path 11. */
+int gnx_seed_candidates(const gnx_seed_vote_opts *o, int64_t n_reads, const uint8_t *read_cat, const int64_t *read_off,
+                        int64_t **out_cand_off, int64_t **out_cand_start, int64_t **out_cand_len, uint8_t **out_cand_strand, int32_t **out_cand_votes);
+
 int gnx_get_timing(gnx_timing *out);
 /* Diagnostics (tests only; nothing in the reference corresponds to it): launch n_workgroups workgroups that each hold one CU's whole
  * LDS and spin for `milliseconds` on a stream of their own, and return at once -- the pipelined launches of the library must make
@@ -337,6 +381,7 @@ int gnx_debug_occupy(int n_workgroups, int milliseconds); /* refused with GNX_EI
  * /root/reference/align/affineGap.go:305 (quirk Q1) changed the state / all such crossings -- each of the former can cost the CIGAR
  * at most one gap open against the score, which is what the tests of megabase pairs (no oracle finishes them) check.
  * which = 5 / 6: rows per lane / snapshot spacing of the last 64-lane affine sweep (bench.py prices its design bytes with them).
+ * which = 7 / 8: reads gnx_seed_candidates voted with the table in LDS / in a slab of device memory.
  * reset != 0 zeroes the counter after reading (3 and 4 together). */
 int gnx_debug_counter(int which, int reset, int64_t *out);
 

@@ -288,6 +288,41 @@ inline std::vector<BestOf> MapBestOf(int mode, const ScoreMatrix &scores, int64_
     return detail::best_of(detail::params(mode, scores, gapOpen, gapExtend, 10000, 10000), reads, nullptr, coff, cstart, clen, cstrand, cigar);
 }
 
+// ---- candidates by seed votes on the resident reference, and reads in / placements out (gnx_reference_index_build, gnx_seed_candidates) ----
+struct SeedVoteOpts { int32_t MaxOcc = 64, Bin = 32, Pad = 16, MaxCand = 4, MinVotes = 2; };
+struct VotedCandidate { int64_t Start, Len; uint8_t Strand; int32_t Votes; };
+struct Mapped { BestOf Hit; int64_t WindowStart = 0; uint8_t Strand = 0; }; // the winner's window start: add Hit.TargetEnd (or the route's leading D run) to it
+inline void ReferenceIndexBuild(int seedLen, int seedStep = 1) { const int rc = gnx_reference_index_build(seedLen, seedStep); if (rc) detail::raise(rc); }
+inline std::vector<std::vector<VotedCandidate>> SeedCandidates(const std::vector<std::vector<dna::Base>> &reads, const SeedVoteOpts &o = SeedVoteOpts()) {
+    const int64_t n = (int64_t)reads.size();
+    std::vector<int64_t> roff((size_t)n + 1, 0);
+    for (int64_t k = 0; k < n; k++) roff[(size_t)k + 1] = roff[(size_t)k] + (int64_t)reads[(size_t)k].size();
+    std::vector<dna::Base> rcat((size_t)roff[(size_t)n] + 1);
+    for (int64_t k = 0; k < n; k++) std::copy(reads[(size_t)k].begin(), reads[(size_t)k].end(), rcat.begin() + roff[(size_t)k]);
+    gnx_seed_vote_opts vo = {o.MaxOcc, o.Bin, o.Pad, o.MaxCand, o.MinVotes, {0, 0, 0}};
+    int64_t *coff = nullptr, *cstart = nullptr, *clen = nullptr; uint8_t *cstrand = nullptr; int32_t *cvotes = nullptr;
+    const int rc = gnx_seed_candidates(&vo, n, rcat.data(), roff.data(), &coff, &cstart, &clen, &cstrand, &cvotes);
+    if (rc) detail::raise(rc);
+    std::vector<std::vector<VotedCandidate>> out((size_t)n);
+    for (int64_t k = 0; k < n; k++)
+        for (int64_t x = coff[k]; x < coff[k + 1]; x++) out[(size_t)k].push_back(VotedCandidate{cstart[x], clen[x], cstrand[x], cvotes[x]});
+    gnx_free(coff); gnx_free(cstart); gnx_free(clen); gnx_free(cstrand); gnx_free(cvotes);
+    return out;
+}
+inline std::vector<Mapped> MapReads(int mode, const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, const std::vector<std::vector<dna::Base>> &reads,
+                                    const SeedVoteOpts &o = SeedVoteOpts(), bool cigar = true) {
+    const std::vector<std::vector<VotedCandidate>> voted = SeedCandidates(reads, o);
+    std::vector<std::vector<RefCandidate>> cands(reads.size());
+    for (size_t r = 0; r < reads.size(); r++) for (const auto &v : voted[r]) cands[r].push_back(RefCandidate{v.Start, v.Len, v.Strand});
+    std::vector<BestOf> best = MapBestOf(mode, scores, gapOpen, gapExtend, reads, cands, cigar);
+    std::vector<Mapped> out(reads.size());
+    for (size_t r = 0; r < reads.size(); r++) {
+        out[r].Hit = std::move(best[r]);
+        if (out[r].Hit.Best >= 0) { out[r].WindowStart = cands[r][(size_t)out[r].Hit.Best].Start; out[r].Strand = cands[r][(size_t)out[r].Hit.Best].Strand; }
+    }
+    return out;
+}
+
 inline void AffineGapLocalEngine(const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, std::vector<TargetQueryPair> &pairs) {
     std::vector<std::vector<dna::Base>> t, q;
     for (auto &p : pairs) { t.push_back(p.Target); q.push_back(p.Query); }
