@@ -23,7 +23,7 @@ EXPORTS = ["gnx_device_count", "gnx_init", "gnx_shutdown", "gnx_last_error", "gn
            "gnx_locate_batch", "gnx_locate_batch_windows", "gnx_locate_batch_by_offset",
            "gnx_locate_span_batch", "gnx_locate_span_batch_windows", "gnx_locate_span_batch_by_offset",
            "gnx_affine_gap_chunk_score_batch", "gnx_multiple_affine_gap_score_batch",
-           "gnx_best_of_by_offset", "gnx_best_of_windows",
+           "gnx_best_of_by_offset", "gnx_best_of_windows", "gnx_best_pair_by_offset", "gnx_best_pair_windows",
            "gnx_reference_index_build", "gnx_reference_index_info", "gnx_reference_index_get", "gnx_seed_candidates"]
 
 
@@ -51,6 +51,10 @@ class GnxTiming(ctypes.Structure):
 class GnxSeedVoteOpts(ctypes.Structure):
     _fields_ = [("max_occ", ctypes.c_int32), ("bin", ctypes.c_int32), ("pad", ctypes.c_int32), ("max_cand", ctypes.c_int32),
                 ("min_votes", ctypes.c_int32), ("_reserved", ctypes.c_int32 * 3)]
+
+
+class GnxPairOpts(ctypes.Structure):
+    _fields_ = [("min_insert", ctypes.c_int64), ("max_insert", ctypes.c_int64), ("unpaired_penalty", ctypes.c_int64), ("_reserved", ctypes.c_int64)]
 
 
 class GnxError(RuntimeError):
@@ -138,6 +142,10 @@ def lib():
         L.gnx_best_of_by_offset.restype = ctypes.c_int
         L.gnx_best_of_windows.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, c_p, c_p, i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_p)]
         L.gnx_best_of_windows.restype = ctypes.c_int
+        L.gnx_best_pair_by_offset.argtypes = [ctypes.POINTER(GnxParams), ctypes.POINTER(GnxPairOpts), i64, c_p, c_p] + [c_p] * 14 + [ctypes.POINTER(c_p), ctypes.POINTER(c_p)]
+        L.gnx_best_pair_by_offset.restype = ctypes.c_int
+        L.gnx_best_pair_windows.argtypes = [ctypes.POINTER(GnxParams), ctypes.POINTER(GnxPairOpts), i64, c_p, c_p, c_p, i64] + [c_p] * 14 + [ctypes.POINTER(c_p), ctypes.POINTER(c_p)]
+        L.gnx_best_pair_windows.restype = ctypes.c_int
         L.gnx_reference_index_build.argtypes = [ctypes.c_int, ctypes.c_int]
         L.gnx_reference_index_build.restype = ctypes.c_int
         L.gnx_reference_index_info.argtypes = [ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
@@ -520,6 +528,48 @@ def best_of_by_offset(params, read_cat, read_off, cand_off, cand_start, cand_len
 def best_of_windows(params, read_cat, read_off, target_buf, cand_off, cand_start, cand_len, cand_strand, cigar=True, target_end=None):
     """gnx_best_of_windows: the same with the windows taken from target_buf."""
     return _best_of(params, read_cat, read_off, target_buf, cand_off, cand_start, cand_len, cand_strand, cigar, target_end)
+
+
+# ---- best proper pair (gnx_best_pair_*): best-of for mate pairs, reads 2k and 2k + 1 placed together ----
+def pair_opts(min_insert, max_insert, unpaired_penalty=0):
+    o = GnxPairOpts()
+    o.min_insert, o.max_insert, o.unpaired_penalty = int(min_insert), int(max_insert), int(unpaired_penalty)
+    return o
+
+
+def _best_pair(params, opts, read_cat, read_off, target, cand_off, cand_start, cand_len, cand_strand, cigar):
+    L = lib()
+    read_cat, read_off, cand_off = _u8(read_cat), _i64(read_off), _i64(cand_off)
+    cand_start, cand_len, cand_strand = _i64(cand_start), _i64(cand_len), _u8(cand_strand)
+    n, nc = int(read_off.shape[0]) - 1, int(cand_start.shape[0])
+    best = np.zeros(max(n, 1), dtype=np.int32)
+    per_read = [np.zeros(max(n, 1), dtype=np.int64) for _ in range(4)]  # score, start, end, second
+    proper, tlen = np.zeros(max(n // 2, 1), dtype=np.uint8), np.zeros(max(n // 2, 1), dtype=np.int64)
+    per_cand = [np.zeros(max(nc, 1), dtype=np.int64) for _ in range(3)]  # score, start, end
+    ops_p, off_p = ctypes.c_void_p(), ctypes.c_void_p()
+    tail = [cand_off.ctypes.data, cand_start.ctypes.data, cand_len.ctypes.data, cand_strand.ctypes.data, best.ctypes.data] + [a.ctypes.data for a in per_read] + \
+           [proper.ctypes.data, tlen.ctypes.data] + [a.ctypes.data for a in per_cand] + [ctypes.byref(ops_p) if cigar else None, ctypes.byref(off_p) if cigar else None]
+    if target is None:
+        check(L.gnx_best_pair_by_offset(ctypes.byref(params), ctypes.byref(opts), n, read_cat.ctypes.data, read_off.ctypes.data, *tail))
+    else:
+        target = _u8(target)
+        check(L.gnx_best_pair_windows(ctypes.byref(params), ctypes.byref(opts), n, read_cat.ctypes.data, read_off.ctypes.data, target.ctypes.data, target.shape[0], *tail))
+    ops, off = _take(ops_p, off_p, n) if cigar else (None, None)
+    return {"best": best[:n], "score": per_read[0][:n], "target_start": per_read[1][:n], "target_end": per_read[2][:n], "second_score": per_read[3][:n],
+            "proper": proper[:n // 2], "tlen": tlen[:n // 2], "cand_score": per_cand[0][:nc], "cand_start": per_cand[1][:nc], "cand_end": per_cand[2][:nc],
+            "ops": ops, "off": off}
+
+
+def best_pair_by_offset(params, opts, read_cat, read_off, cand_off, cand_start, cand_len, cand_strand, cigar=True):
+    """gnx_best_pair_by_offset: mates 2k / 2k + 1 against candidate windows of the resident reference (tables as best_of_by_offset), opts from
+    pair_opts().  Returns a dict: per read best[int32], score, target_start, target_end (relative to the chosen window), second_score; per
+    pair proper[uint8], tlen; per candidate cand_score, cand_start, cand_end; ops / off (None with cigar=False)."""
+    return _best_pair(params, opts, read_cat, read_off, None, cand_off, cand_start, cand_len, cand_strand, cigar)
+
+
+def best_pair_windows(params, opts, read_cat, read_off, target_buf, cand_off, cand_start, cand_len, cand_strand, cigar=True):
+    """gnx_best_pair_windows: the same with the windows taken from target_buf."""
+    return _best_pair(params, opts, read_cat, read_off, target_buf, cand_off, cand_start, cand_len, cand_strand, cigar)
 
 
 # ---- candidates by seed votes (gnx_reference_index_*, gnx_seed_candidates): an index of the resident reference, reads -> candidate tables ----

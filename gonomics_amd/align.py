@@ -299,6 +299,63 @@ def MapReads(params, reads, cigar=True, **vote_opts):
              [int(x) for x in cand[c_off[r]:c_off[r + 1]]], int(start[c_off[r] + best[r]]) if best[r] >= 0 else None) for r in range(len(reads))]
 
 
+def _pair_result(out, n, c_off, w_start, cigar):
+    """(per read, per pair) of MapBestPair / MapReadPairs from _lib.best_pair_*'s dict; w_start = every candidate's window start"""
+    per_read = []
+    for r in range(n):
+        b = int(out["best"][r])
+        at = int(w_start[c_off[r] + b]) if b >= 0 else None
+        per_read.append((b, int(out["score"][r]), _to_route(out["ops"][out["off"][r]:out["off"][r + 1]]) if cigar else None, int(out["target_end"][r]),
+                         [int(x) for x in out["cand_score"][c_off[r]:c_off[r + 1]]],
+                         at + int(out["target_start"][r]) if b >= 0 else None, at + int(out["target_end"][r]) if b >= 0 else None,
+                         int(out["second_score"][r]) if out["second_score"][r] != np.iinfo(np.int64).min else None))
+    return per_read, [(bool(out["proper"][k]), int(out["tlen"][k])) for k in range(n // 2)]
+
+
+def MapBestPair(params, reads, candidates, min_insert, max_insert, unpaired_penalty=0, cigar=True, target=None):
+    """Best proper pair in ONE device call (gnx_best_pair_*): reads[2k] and reads[2k + 1] are mates, candidates[r] a list of (start, len,
+    strand) windows of the resident reference (_lib.set_reference) or, with target given, of that sequence; strand 1 = the read's reverse
+    complement; the mode GNX_AFFINE_GAP_LOCAL.  The two mates are chosen together: opposite strands, the forward one first, min_insert <=
+    outer distance <= max_insert; the best such combination wins unless the two separate first maxima beat it by more than
+    unpaired_penalty (include/gnx_align.h states the rule).  Returns (per_read, per_pair): per read MapBestOf's tuple plus (abs_start,
+    abs_end, second_score) -- the alignment's span in the coordinates of the window starts (None without a candidate) and the best score
+    among the read's other candidates (None without one); per pair (proper, tlen)."""
+    if len(reads) % 2:
+        raise ValueError("MapBestPair: reads come in mate pairs (an even number)")
+    if not reads:
+        return [], []
+    flat = [c for cs in candidates for c in cs]
+    r_cat, r_off = _lib._cat(list(reads))
+    c_off = np.concatenate([[0], np.cumsum([len(c) for c in candidates])]).astype(np.int64)
+    opts = _lib.pair_opts(min_insert, max_insert, unpaired_penalty)
+    w_start = np.array([w[0] for w in flat], dtype=np.int64)
+    args = (c_off, w_start, [w[1] for w in flat], [w[2] for w in flat])
+    try:
+        if target is None and flat:
+            out = _lib.best_pair_by_offset(params, opts, r_cat, r_off, *args, cigar=cigar)
+        else:
+            out = _lib.best_pair_windows(params, opts, r_cat, r_off, np.zeros(1, np.uint8) if target is None else target, *args, cigar=cigar)
+    except _lib.GnxError as e:
+        _raise(e)
+    return _pair_result(out, len(reads), c_off, w_start, cigar)
+
+
+def MapReadPairs(params, reads, min_insert, max_insert, unpaired_penalty=0, cigar=True, **vote_opts):
+    """Mate pairs in, placements out: gnx_seed_candidates over all mates, then gnx_best_pair_by_offset on its tables unchanged.  Returns
+    what MapBestPair returns; abs_start / abs_end are positions of the resident reference."""
+    if len(reads) % 2:
+        raise ValueError("MapReadPairs: reads come in mate pairs (an even number)")
+    if not reads:
+        return [], []
+    r_cat, r_off = _lib._cat(list(reads))
+    try:
+        c_off, start, ln, strand, _ = _lib.seed_candidates(r_cat, r_off, **_vote_opts(vote_opts))
+        out = _lib.best_pair_by_offset(params, _lib.pair_opts(min_insert, max_insert, unpaired_penalty), r_cat, r_off, c_off, start, ln, strand, cigar=cigar)
+    except _lib.GnxError as e:
+        _raise(e)
+    return _pair_result(out, len(reads), c_off, start, cigar)
+
+
 def AffineGapChunk(alpha, beta, scores, gapOpen, gapExtend, chunkSize):
     """align.AffineGapChunk (/root/reference/align/affineGap_highMem.go:227-268)."""
     try:

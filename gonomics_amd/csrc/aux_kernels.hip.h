@@ -1,4 +1,4 @@
-// aux_kernels.hip.h -- N1 score matrices, run scaling, exclusive scan of the run counts, window unpacking, the best-of-K helpers
+// aux_kernels.hip.h -- N1 score matrices, run scaling, exclusive scan of the run counts, window unpacking, the best-of-K helpers, the pair selection
 // Part of libgonomics_align_hip.so; included by gnx_align.hip (one translation unit).  See DESIGN.md section 4.
 #pragma once
 #include "gnx_common.hip.h"
@@ -382,6 +382,91 @@ __global__ __launch_bounds__(256) void winner_tables_kernel(const int32_t *__res
     const int64_t r = win_read[w], c = cand_off[r] + best[r];
     win_rstart[w] = cand_rstart[c];
     win_wstart[w] = cand_wstart[c];
+}
+
+// ---- gnx_best_pair_*: the two mates of a read pair placed together (gnx_align.h states the rule) ----------------------------------
+// The wave-wide maximum of (score, then the LOWEST index): at < 0 means "none".  at is unique per item, so the order is total and every
+// lane ends with the same winner whatever the lanes held.  64-bit values cross lanes as two 32-bit halves.
+struct PairPick { int64_t score, at; };
+__device__ __forceinline__ int64_t shfl_xor_i64(int64_t v, int d) {
+    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)(unsigned long long)v, d, 64), hi = (unsigned)__shfl_xor((int)(unsigned)((unsigned long long)v >> 32), d, 64);
+    return (int64_t)(((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ void pick_better(PairPick &k, int64_t score, int64_t at) {
+    if (at >= 0 && (k.at < 0 || score > k.score || (score == k.score && at < k.at))) { k.score = score; k.at = at; }
+}
+__device__ __forceinline__ PairPick wave_pick(PairPick k) {
+    for (int d = 32; d >= 1; d >>= 1) {
+        const int64_t os = shfl_xor_i64(k.score, d), oa = shfl_xor_i64(k.at, d);
+        pick_better(k, os, oa);
+    }
+    return k;
+}
+// the maximum over the candidates [c0, c1) other than `skip` (an absolute index, or -1), indices relative to c0
+__device__ __forceinline__ PairPick wave_first_max(const int64_t *__restrict__ score, int64_t c0, int64_t c1, int64_t skip, int lane) {
+    PairPick k{0, -1};
+    for (int64_t c = c0 + lane; c < c1; c += 64) if (c != skip) pick_better(k, score[c], c - c0);
+    return wave_pick(k);
+}
+struct PairSelectArgs {
+    const int64_t *score, *start, *end, *wstart, *cand_off; // per candidate: the span entry's three values and the window's start
+    const uint8_t *strand;
+    int64_t n_pairs, min_insert, max_insert, penalty;
+    int32_t *best;                                           // per read
+    int64_t *best_score, *best_start, *best_end, *second;
+    uint8_t *proper;                                         // per pair
+    int64_t *tlen;
+};
+// candidates x of mate 1 and y of mate 2 (absolute indices): E(v) - A(f) if the combination is proper, else -1
+__device__ __forceinline__ int64_t proper_insert(const PairSelectArgs &a, int64_t x, int64_t y) {
+    if (a.strand[x] == a.strand[y] || a.end[x] <= a.start[x] || a.end[y] <= a.start[y]) return -1;
+    const int64_t f = a.strand[x] ? y : x, v = a.strand[x] ? x : y; // f on strand 0, v on strand 1
+    const int64_t Af = a.wstart[f] + a.start[f], Ef = a.wstart[f] + a.end[f], Av = a.wstart[v] + a.start[v], Ev = a.wstart[v] + a.end[v];
+    if (Af > Av || Ef > Ev || Ev - Af < a.min_insert || Ev - Af > a.max_insert) return -1;
+    return Ev - Af;
+}
+// One wave per read pair (reads 2k, 2k + 1) and per workgroup, so that what is the same for the whole wave (the pair, its offsets, K1, K2)
+// is uniform by construction.  The K1 * K2 combinations c = c1 * K2 + c2 are strided over the lanes; each lane keeps its best proper one,
+// wave_pick reduces them (ties: the lowest c, i.e. the lowest c1, then the lowest c2).  The same wave finds both mates' first maxima,
+// decides, and looks up the runner-up of what it chose.  Lane 0 writes.
+__global__ __launch_bounds__(64) void pair_select_kernel(PairSelectArgs a) {
+    const int lane = threadIdx.x;
+    for (int64_t k = blockIdx.x; k < a.n_pairs; k += gridDim.x) {
+        const int64_t b1 = a.cand_off[2 * k], b2 = a.cand_off[2 * k + 1], e2 = a.cand_off[2 * k + 2];
+        const int K1 = (int)(b2 - b1), K2 = (int)(e2 - b2); // (out_best is 32 bits wide: K1, K2 < 2^31)
+        const PairPick f1 = wave_first_max(a.score, b1, b2, -1, lane), f2 = wave_first_max(a.score, b2, e2, -1, lane);
+        // the lane's combinations c = lane, lane + 64, ... as (c1, c2) = (c / K2, c % K2), advanced without a 64-bit division; the key of
+        // the reduction is c1 << 32 | c2, which orders the combinations exactly as c does
+        int c1 = 0, c2 = lane, step1 = 0, step2 = 64;
+        if (K2 > 0 && K2 <= 64) { c1 = lane / K2; c2 = lane % K2; step1 = 64 / K2; step2 = 64 % K2; }
+        PairPick p{0, -1};
+        while (K2 > 0 && c1 < K1) {
+            if (proper_insert(a, b1 + c1, b2 + c2) >= 0) pick_better(p, a.score[b1 + c1] + a.score[b2 + c2], ((int64_t)c1 << 32) | c2);
+            c1 += step1;
+            unsigned next = (unsigned)c2 + (unsigned)step2; // (below 2^32: c2 < K2 < 2^31 and step2 <= 64)
+            if (next >= (unsigned)K2) { next -= (unsigned)K2; c1++; }
+            c2 = (int)next;
+        }
+        const PairPick w = wave_pick(p);
+        const bool proper = w.at >= 0 && w.score >= f1.score + f2.score - a.penalty;
+        const int at1 = proper ? (int)(w.at >> 32) : (int)f1.at, at2 = proper ? (int)(w.at & 0x7fffffff) : (int)f2.at;
+        const PairPick s1 = wave_first_max(a.score, b1, b2, at1 < 0 ? -1 : b1 + at1, lane), s2 = wave_first_max(a.score, b2, e2, at2 < 0 ? -1 : b2 + at2, lane);
+        if (lane == 0) {
+            const int at[2] = {at1, at2};
+            const int64_t base[2] = {b1, b2};
+            const PairPick sec[2] = {s1, s2};
+            for (int m = 0; m < 2; m++) {
+                const int64_t r = 2 * k + m, c = base[m] + at[m];
+                a.best[r] = at[m];
+                a.best_score[r] = at[m] < 0 ? 0 : a.score[c];
+                a.best_start[r] = at[m] < 0 ? 0 : a.start[c];
+                a.best_end[r] = at[m] < 0 ? 0 : a.end[c];
+                a.second[r] = sec[m].at < 0 ? INT64_MIN : sec[m].score;
+            }
+            a.proper[k] = proper ? 1 : 0;
+            a.tlen[k] = proper ? proper_insert(a, b1 + at1, b2 + at2) : 0;
+        }
+    }
 }
 
 } // namespace

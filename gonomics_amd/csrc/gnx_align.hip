@@ -140,7 +140,7 @@ struct Ctx {
     DevBuf ss_len, res_end, gat_end; // gnx_locate_*: target lengths for the end read off a CIGAR, the ends of a host job, their gather on device 0
     DevBuf ss_plans, ss_rowbuf, ss_prog, ss_err, ss_off; // the score-only sweep (score_sweep.hip.h): plans, hand-over rows, progress / claim words, error flags; offsets of a dropped CIGAR
     DevBuf sd_keys, sd_locs, sd_nodes, sd_node_off, sd_word_off, sd_words, sd_tmp[8];
-    DevBuf bo[13]; // gnx_best_of_* (gnx_host.hip.h, BO_*): reads + reverse complements, candidate tables and scores, per-read winners, the winners' tables
+    DevBuf bo[19]; // gnx_best_of_* / gnx_best_pair_* (gnx_host.hip.h, BO_*): reads + reverse complements, candidate tables and scores, per-read winners, the winners' tables
     int64_t sd_n = -1, sd_nodes_n = 0; int sd_seed_len = 0;
     // k-mer index of the resident reference (gnx_reference_index_build; context 0 only) and the scratch of gnx_seed_candidates (RS_*)
     DevBuf ri_keys, ri_pos, ri_dir, rs[15];
@@ -2994,6 +2994,31 @@ int gnx_best_of_windows(const gnx_params *p, int64_t n_reads, const uint8_t *rea
     g_err[0] = 0;
     return run_best_of(p, n_reads, read_cat, read_off, false, target_buf, target_buf_len, cand_off, cand_start, cand_len, cand_strand, out_best, out_score, out_target_end, out_cand_score,
                        out_ops, out_ops_off);
+}
+
+/* ---- best proper pair: best-of's body with the joint selection of the two mates (gnx_align.h) ---- */
+int gnx_best_pair_by_offset(const gnx_params *p, const gnx_pair_opts *o, int64_t n_reads, const uint8_t *read_cat, const int64_t *read_off,
+                            const int64_t *cand_off, const int64_t *cand_start, const int64_t *cand_len, const uint8_t *cand_strand,
+                            int32_t *out_best, int64_t *out_score, int64_t *out_target_start, int64_t *out_target_end,
+                            int64_t *out_second_score, uint8_t *out_proper, int64_t *out_tlen,
+                            int64_t *out_cand_score, int64_t *out_cand_start, int64_t *out_cand_end, gnx_cigar **out_ops, int64_t **out_ops_off) {
+    std::lock_guard<std::mutex> api(g_api_mu);
+    g_err[0] = 0;
+    const PairOut pr{o, out_target_start, out_second_score, out_proper, out_tlen, out_cand_start, out_cand_end};
+    return run_best_of(p, n_reads, read_cat, read_off, true, nullptr, 0, cand_off, cand_start, cand_len, cand_strand, out_best, out_score, out_target_end, out_cand_score, out_ops, out_ops_off, &pr);
+}
+
+int gnx_best_pair_windows(const gnx_params *p, const gnx_pair_opts *o, int64_t n_reads, const uint8_t *read_cat, const int64_t *read_off,
+                          const uint8_t *target_buf, int64_t target_buf_len,
+                          const int64_t *cand_off, const int64_t *cand_start, const int64_t *cand_len, const uint8_t *cand_strand,
+                          int32_t *out_best, int64_t *out_score, int64_t *out_target_start, int64_t *out_target_end,
+                          int64_t *out_second_score, uint8_t *out_proper, int64_t *out_tlen,
+                          int64_t *out_cand_score, int64_t *out_cand_start, int64_t *out_cand_end, gnx_cigar **out_ops, int64_t **out_ops_off) {
+    std::lock_guard<std::mutex> api(g_api_mu);
+    g_err[0] = 0;
+    const PairOut pr{o, out_target_start, out_second_score, out_proper, out_tlen, out_cand_start, out_cand_end};
+    return run_best_of(p, n_reads, read_cat, read_off, false, target_buf, target_buf_len, cand_off, cand_start, cand_len, cand_strand, out_best, out_score, out_target_end, out_cand_score,
+                       out_ops, out_ops_off, &pr);
 }
 
 int gnx_score_batch_device(const gnx_params *p, int64_t n_pairs,

@@ -817,11 +817,22 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
 //   selection     first_max_kernel; only best[] (4 bytes per read) comes back: the host plans the CIGAR stage from the winners' lengths
 //   CIGAR stage   winner_tables_kernel builds the winners' start tables from what is resident, run_device aligns them in sub-batches
 // Nothing is written to the caller's outputs before both stages have succeeded.
-enum { BO_READS, BO_ROFF, BO_COFF, BO_WREAD, BO_RS, BO_WS, BO_CSCORE, BO_CEND, BO_BEST, BO_BSCORE, BO_BEND, BO_WR, BO_WW, BO_COUNT };
+// gnx_best_pair_* (pr != nullptr) is the same body: its score stage also asks for every candidate's target start, pair_select_kernel
+// stands where first_max_kernel stands, and a few more vectors come back.
+enum { BO_READS, BO_ROFF, BO_COFF, BO_WREAD, BO_RS, BO_WS, BO_CSCORE, BO_CEND, BO_BEST, BO_BSCORE, BO_BEND, BO_WR, BO_WW,
+       BO_CSTART, BO_STRAND, BO_BSTART, BO_SECOND, BO_PROPER, BO_TLEN, BO_COUNT };
+struct PairOut { // what gnx_best_pair_* has beyond gnx_best_of_*
+    const gnx_pair_opts *o;
+    int64_t *start, *second; // per read
+    uint8_t *proper;         // per pair
+    int64_t *tlen;
+    int64_t *cand_start, *cand_end; // per candidate (may be null)
+};
 static_assert(BO_COUNT == sizeof(Ctx::bo) / sizeof(DevBuf), "Ctx::bo holds one buffer per BO_* index");
 int run_best_of(const gnx_params *prm, int64_t n_reads, const uint8_t *read_cat, const int64_t *read_off, bool resident, const uint8_t *t_buf, int64_t t_len,
                 const int64_t *cand_off, const int64_t *cand_start, const int64_t *cand_len, const uint8_t *cand_strand,
-                int32_t *out_best, int64_t *out_score, int64_t *out_end, int64_t *out_cand_score, gnx_cigar **out_ops, int64_t **out_ops_off) {
+                int32_t *out_best, int64_t *out_score, int64_t *out_end, int64_t *out_cand_score, gnx_cigar **out_ops, int64_t **out_ops_off,
+                const PairOut *pr = nullptr) {
     const auto t_entry = std::chrono::steady_clock::now();
     // ---- argument checks: everything that needs no device ----
     if (!prm || n_reads < 0 || !read_off || !cand_off || !out_best || !out_score || t_len < 0) { set_err("bad argument%s", ""); return GNX_EINVAL; }
@@ -829,6 +840,12 @@ int run_best_of(const gnx_params *prm, int64_t n_reads, const uint8_t *read_cat,
     if (prm->mode < GNX_AFFINE_GAP || prm->mode > GNX_CONST_GAP_HIGHMEM) { set_err("unknown mode %s%lld", "", (long long)prm->mode); return GNX_EINVAL; }
     const bool local = prm->mode == GNX_AFFINE_GAP_LOCAL, cigars = out_ops != nullptr;
     if (out_end && !local) { set_err("out_target_end is defined for GNX_AFFINE_GAP_LOCAL only%s", ""); return GNX_EINVAL; }
+    if (pr) {
+        if (!pr->o || !out_end || !pr->start || !pr->proper || !pr->tlen) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+        if (!local) { set_err("gnx_best_pair_*: the mode must be GNX_AFFINE_GAP_LOCAL%s", ""); return GNX_EINVAL; }
+        if (n_reads & 1) { set_err("gnx_best_pair_*: n_reads must be even (reads 2k and 2k + 1 are mates)%s", ""); return GNX_EINVAL; }
+        if (pr->o->min_insert < 0 || pr->o->max_insert < pr->o->min_insert || pr->o->unpaired_penalty < 0) { set_err("gnx_best_pair_*: 0 <= min_insert <= max_insert and unpaired_penalty >= 0%s", ""); return GNX_EINVAL; }
+    }
     if (read_off[0] < 0 || cand_off[0] != 0) { set_err("read_off must start at >= 0 and cand_off at 0%s", ""); return GNX_EINVAL; }
     for (int64_t r = 0; r < n_reads; r++)
         if (read_off[r + 1] < read_off[r] || cand_off[r + 1] < cand_off[r]) { set_err("decreasing offsets at read %s%lld", "", (long long)r); return GNX_EINVAL; }
@@ -869,16 +886,20 @@ int run_best_of(const gnx_params *prm, int64_t n_reads, const uint8_t *read_cat,
     if ((rc = bo[BO_READS].ensure((size_t)r_total * 2 + 16)) || (rc = bo[BO_ROFF].ensure((nr + 1) * 8)) || (rc = bo[BO_COFF].ensure((nr + 1) * 8)) ||
         (rc = bo[BO_RS].ensure(ncd * 8)) || (rc = bo[BO_WS].ensure(ncd * 8)) || (rc = bo[BO_CSCORE].ensure(ncd * 8)) || (local && (rc = bo[BO_CEND].ensure(ncd * 8))) ||
         (rc = bo[BO_BEST].ensure(nr * 4)) || (rc = bo[BO_BSCORE].ensure(nr * 8)) || (rc = bo[BO_BEND].ensure(nr * 8))) return rc;
+    if (pr && ((rc = bo[BO_CSTART].ensure(ncd * 8)) || (rc = bo[BO_STRAND].ensure(ncd)) || (rc = bo[BO_BSTART].ensure(nr * 8)) || (rc = bo[BO_SECOND].ensure(nr * 8)) ||
+               (rc = bo[BO_PROPER].ensure(nr)) || (rc = bo[BO_TLEN].ensure(nr * 8)))) return rc;
     if (!resident && (rc = c.in_b.ensure((size_t)t_len + 16))) return rc;
     uint8_t *d_reads = (uint8_t *)bo[BO_READS].p;
     const uint8_t *d_tbuf = resident ? (const uint8_t *)c.ref.p : (const uint8_t *)c.in_b.p;
     int64_t *d_rs = (int64_t *)bo[BO_RS].p, *d_ws = (int64_t *)bo[BO_WS].p, *d_cscore = (int64_t *)bo[BO_CSCORE].p, *d_cend = local ? (int64_t *)bo[BO_CEND].p : nullptr;
+    int64_t *d_cstart = pr ? (int64_t *)bo[BO_CSTART].p : nullptr;
     if (n_reads > 0 && n_cand > 0) {
         if (r_total) HIPCHK(hipMemcpyAsync(d_reads, read_cat + r_lo, (size_t)r_total, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(bo[BO_ROFF].p, r_lo ? h_roff.data() : read_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(bo[BO_COFF].p, cand_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_rs, h_rs.data(), (size_t)n_cand * 8, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_ws, cand_start, (size_t)n_cand * 8, hipMemcpyHostToDevice, st));
+        if (pr) HIPCHK(hipMemcpyAsync(bo[BO_STRAND].p, cand_strand, (size_t)n_cand, hipMemcpyHostToDevice, st));
         if (!resident && t_len) HIPCHK(hipMemcpyAsync(c.in_b.p, t_buf, (size_t)t_len, hipMemcpyHostToDevice, st));
         if (r_total) {
             hipLaunchKernelGGL(revcomp_reads_kernel, dim3((unsigned)std::min<int64_t>((n_reads + 3) / 4, 1 << 20)), dim3(256), 0, st, (const uint8_t *)d_reads, (const int64_t *)bo[BO_ROFF].p, n_reads, d_reads + r_total);
@@ -909,26 +930,33 @@ int run_best_of(const gnx_params *prm, int64_t n_reads, const uint8_t *read_cat,
         for (int64_t b = 0; b < n_cand; b += size) {
             const int64_t cnt = std::min(size, n_cand - b);
             const int64_t *h_rl = h_rlen.data() + b, *h_wl = cand_len + b;
+            int64_t *d_st = d_cstart ? d_cstart + b : nullptr;
             if (!local) { // alpha = the read or its reverse complement, beta = the window
                 c.beta_packed = resident;
                 rc = score_or_fallback(c, prm, cnt, d_reads, d_rs + b, d_tbuf, d_ws + b, h_rl, h_wl, d_cscore + b, st);
                 c.beta_packed = false;
             } else if (!resident) { // target (alpha) = the window, query (beta) = the read
-                rc = score_or_fallback(c, prm, cnt, d_tbuf, d_ws + b, d_reads, d_rs + b, h_wl, h_rl, d_cscore + b, st, d_cend + b);
+                rc = score_or_fallback(c, prm, cnt, d_tbuf, d_ws + b, d_reads, d_rs + b, h_wl, h_rl, d_cscore + b, st, d_cend + b, true, d_st);
             } else { // the local sweep reads its target packed (the kernels' beta); only its fallback needs bytes
                 c.beta_packed = true;
-                rc = run_score_sweep(prm, cnt, d_reads, d_rs + b, d_tbuf, d_ws + b, h_rl, h_wl, d_cscore + b, st, d_cend + b, true);
+                rc = run_score_sweep(prm, cnt, d_reads, d_rs + b, d_tbuf, d_ws + b, h_rl, h_wl, d_cscore + b, st, d_cend + b, true, d_st);
                 c.beta_packed = false;
                 if (rc == -1 && (rc = unpack(d_ws + b, h_wl, cnt)) == GNX_OK)
-                    rc = score_or_fallback(c, prm, cnt, (const uint8_t *)c.in_b.p, (const int64_t *)c.in_bl.p, d_reads, d_rs + b, h_wl, h_rl, d_cscore + b, st, d_cend + b, false);
+                    rc = score_or_fallback(c, prm, cnt, (const uint8_t *)c.in_b.p, (const int64_t *)c.in_bl.p, d_reads, d_rs + b, h_wl, h_rl, d_cscore + b, st, d_cend + b, false, d_st);
             }
             if (rc) return rc;
             tsum.fill_ms += c.timing.fill_ms; tsum.traceback_ms += c.timing.traceback_ms; tsum.total_ms += c.timing.total_ms; tsum.cells += c.timing.cells;
             tsum.n_launches += c.timing.n_launches; tsum.trace_bytes += c.timing.trace_bytes; tsum.dominant_ms += c.timing.dominant_ms;
             tsum.dominant_launches += c.timing.dominant_launches; tsum.fast_path = std::max(tsum.fast_path, c.timing.fast_path);
         }
-        hipLaunchKernelGGL(first_max_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, st, (const int64_t *)d_cscore, (const int64_t *)d_cend, (const int64_t *)bo[BO_COFF].p,
-                           n_reads, (int32_t *)bo[BO_BEST].p, (int64_t *)bo[BO_BSCORE].p, (int64_t *)bo[BO_BEND].p);
+        if (pr) {
+            PairSelectArgs pa{d_cscore, d_cstart, d_cend, d_ws, (const int64_t *)bo[BO_COFF].p, (const uint8_t *)bo[BO_STRAND].p, n_reads / 2, pr->o->min_insert, pr->o->max_insert,
+                              pr->o->unpaired_penalty, (int32_t *)bo[BO_BEST].p, (int64_t *)bo[BO_BSCORE].p, (int64_t *)bo[BO_BSTART].p, (int64_t *)bo[BO_BEND].p,
+                              (int64_t *)bo[BO_SECOND].p, (uint8_t *)bo[BO_PROPER].p, (int64_t *)bo[BO_TLEN].p};
+            hipLaunchKernelGGL(pair_select_kernel, dim3((unsigned)std::min<int64_t>(n_reads / 2, 1 << 20)), dim3(64), 0, st, pa);
+        } else
+            hipLaunchKernelGGL(first_max_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, st, (const int64_t *)d_cscore, (const int64_t *)d_cend, (const int64_t *)bo[BO_COFF].p,
+                               n_reads, (int32_t *)bo[BO_BEST].p, (int64_t *)bo[BO_BSCORE].p, (int64_t *)bo[BO_BEND].p);
         HIPCHK(hipGetLastError());
     }
 
@@ -995,12 +1023,24 @@ int run_best_of(const gnx_params *prm, int64_t n_reads, const uint8_t *read_cat,
         if (!ops || !off) { if (ops) g_pool.put(ops); if (off) g_pool.put(off); set_err("pinned host allocation failed%s", ""); return GNX_ENOMEM; }
     }
     std::vector<int64_t> w_score((size_t)n_win), w_off((size_t)n_win + 1, 0), h_bscore((size_t)n_reads, 0), h_bend((size_t)n_reads, 0), h_cscore(out_cand_score ? (size_t)n_cand : 0);
+    const int64_t n_mates = n_reads / 2;
+    std::vector<int64_t> h_bstart(pr ? (size_t)n_reads : 0, 0), h_second(pr ? (size_t)n_reads : 0, INT64_MIN), h_tlen(pr ? (size_t)n_mates : 0, 0),
+        h_cstart(pr && pr->cand_start ? (size_t)n_cand : 0), h_cend(pr && pr->cand_end ? (size_t)n_cand : 0);
+    std::vector<uint8_t> h_proper(pr ? (size_t)n_mates : 0, 0);
     auto fetch = [&]() -> int {
         if (n_cand > 0 && n_reads > 0) {
             if (!n_win) HIPCHK(hipMemcpyAsync(h_best.data(), bo[BO_BEST].p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, st));
             HIPCHK(hipMemcpyAsync(h_bscore.data(), bo[BO_BSCORE].p, (size_t)n_reads * 8, hipMemcpyDeviceToHost, st));
             if (out_end) HIPCHK(hipMemcpyAsync(h_bend.data(), bo[BO_BEND].p, (size_t)n_reads * 8, hipMemcpyDeviceToHost, st));
             if (out_cand_score) HIPCHK(hipMemcpyAsync(h_cscore.data(), d_cscore, (size_t)n_cand * 8, hipMemcpyDeviceToHost, st));
+            if (pr) {
+                HIPCHK(hipMemcpyAsync(h_bstart.data(), bo[BO_BSTART].p, (size_t)n_reads * 8, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipMemcpyAsync(h_second.data(), bo[BO_SECOND].p, (size_t)n_reads * 8, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipMemcpyAsync(h_proper.data(), bo[BO_PROPER].p, (size_t)n_mates, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipMemcpyAsync(h_tlen.data(), bo[BO_TLEN].p, (size_t)n_mates * 8, hipMemcpyDeviceToHost, st));
+                if (pr->cand_start) HIPCHK(hipMemcpyAsync(h_cstart.data(), d_cstart, (size_t)n_cand * 8, hipMemcpyDeviceToHost, st));
+                if (pr->cand_end) HIPCHK(hipMemcpyAsync(h_cend.data(), d_cend, (size_t)n_cand * 8, hipMemcpyDeviceToHost, st));
+            }
         }
         if (n_win) {
             HIPCHK(hipMemcpyAsync(w_score.data(), c.res_score.p, (size_t)n_win * 8, hipMemcpyDeviceToHost, st));
@@ -1013,6 +1053,12 @@ int run_best_of(const gnx_params *prm, int64_t n_reads, const uint8_t *read_cat,
     if ((rc = fetch())) { if (ops) g_pool.put(ops); if (off) g_pool.put(off); return rc; }
     for (int64_t r = 0; r < n_reads; r++) { out_best[r] = h_best[(size_t)r]; out_score[r] = h_bscore[(size_t)r]; if (out_end) out_end[r] = h_bend[(size_t)r]; }
     if (out_cand_score && n_cand > 0) memcpy(out_cand_score, h_cscore.data(), (size_t)n_cand * 8);
+    if (pr) {
+        for (int64_t r = 0; r < n_reads; r++) { pr->start[r] = h_bstart[(size_t)r]; if (pr->second) pr->second[r] = h_second[(size_t)r]; }
+        for (int64_t k = 0; k < n_mates; k++) { pr->proper[k] = h_proper[(size_t)k]; pr->tlen[k] = h_tlen[(size_t)k]; }
+        if (pr->cand_start && n_cand > 0) memcpy(pr->cand_start, h_cstart.data(), (size_t)n_cand * 8);
+        if (pr->cand_end && n_cand > 0) memcpy(pr->cand_end, h_cend.data(), (size_t)n_cand * 8);
+    }
     if (cigars) { // a read without candidates: an empty CIGAR
         int64_t w = 0;
         for (int64_t r = 0; r < n_reads; r++) {

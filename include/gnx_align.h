@@ -101,7 +101,7 @@ typedef struct gnx_timing {
                             score_sweep.hip.h); 8: its AffineGapLocal variant ran (gnx_score_* with GNX_AFFINE_GAP_LOCAL, gnx_locate_*);
                             9: the score-only sweep with explicit cell scores ran (gnx_affine_gap_chunk_score_batch,
                             gnx_multiple_affine_gap_score_batch; n1_sweep.hip.h);
-                            10: the local sweep (8) followed by the origin-carrying window DP ran (gnx_locate_span_*;
+                            10: the local sweep (8) followed by the origin-carrying window DP ran (gnx_locate_span_*, gnx_best_pair_*;
                             span_origin.hip.h): fill_ms and total_ms cover both stages, dominant_ms is the sweep's.
                             11: gnx_seed_candidates ran (ref_seeds.hip.h): fill_ms = lookup + vote kernels, dominant_ms = the vote kernels, cells = seed
                             hits that voted, n_launches = vote sub-batches.
@@ -326,6 +326,57 @@ int gnx_best_of_windows(const gnx_params *p, int64_t n_reads, const uint8_t *rea
                         const int64_t *cand_off, const int64_t *cand_start, const int64_t *cand_len, const uint8_t *cand_strand,
                         int32_t *out_best, int64_t *out_score, int64_t *out_target_end, int64_t *out_cand_score,
                         gnx_cigar **out_ops, int64_t **out_ops_off);
+
+/* ---- best proper pair: the two mates of a read pair placed together (an extension; the graph path has it as gnx_gsw_map_reads(paired)) -- */
+typedef struct gnx_pair_opts {
+    int64_t min_insert, max_insert;   /* 0 <= min_insert <= max_insert */
+    int64_t unpaired_penalty;         /* >= 0 */
+    int64_t _reserved;
+} gnx_pair_opts;
+/* gnx_best_of_* for mate pairs: reads 2k and 2k + 1 are the mates of pair k (the convention of gnx_gsw_map_reads), so n_reads is even.
+ * Read and candidate tables, roles and the reverse complement are exactly those of gnx_best_of_*.  p->mode must be GNX_AFFINE_GAP_LOCAL:
+ * positions are defined nowhere else.
+ * Outputs: per read (n_reads) out_best, out_score, out_target_start, out_target_end (required) and out_second_score (may be NULL); per pair
+ * (n_reads / 2) out_proper and out_tlen (required); per candidate out_cand_score / _start / _end (each may be NULL); out_ops / out_ops_off
+ * together or both NULL, as in gnx_best_of_*.
+ * Contract: every value is defined by an existing entry plus the selection rule below.
+ *   out_cand_score / _start / _end[c]  what gnx_locate_span_batch_windows (_by_offset on the resident reference) returns for candidate c's
+ *                        pair: target = the window, query = the read or its reverse complement; positions relative to the window.
+ *   Absolute positions   A(c) = cand_start[c] + start(c), E(c) = cand_start[c] + end(c).
+ *   Proper               a combination (c1, c2) of a candidate of mate 1 and one of mate 2 is proper iff their strands differ, both
+ *                        alignments are non-empty (end > start) and, with f the strand-0 one and v the strand-1 one, A(f) <= A(v),
+ *                        E(f) <= E(v) and min_insert <= E(v) - A(f) <= max_insert.  Its pair score is score(c1) + score(c2).
+ *   Selection            P = the maximum pair score over the proper combinations, ties to the lowest c1, then the lowest c2;
+ *                        U = firstmax(mate 1) + firstmax(mate 2) - unpaired_penalty, firstmax being gnx_best_of_*'s rule.  A proper
+ *                        combination exists and P >= U: the mates get that combination, out_proper[k] = 1, out_tlen[k] = E(v) - A(f).
+ *                        Otherwise each mate gets its own first maximum, out_proper[k] = 0, out_tlen[k] = 0.  A mate without candidates
+ *                        gets -1 / 0 / 0 / 0 and an empty CIGAR, and its partner is placed alone: not an error.
+ *   out_second_score[r]  the highest score among read r's candidates other than the chosen one, INT64_MIN when there is none: the raw
+ *                        ingredient of a MAPQ (the library defines no MAPQ formula).
+ *   out_score[r], CIGAR  what gnx_align_batch_windows returns for the chosen pair under gnx_best_of_*'s local roles, quirks included,
+ *                        checkersize_* honoured; without a CIGAR stage out_score[r] is the chosen candidate's score.
+ *   out_target_start / _end[r]  the chosen candidate's span values, relative to its window: the CIGAR's leading GNX_COL_D run and the
+ *                        target length minus its trailing GNX_COL_D run.
+ * Return codes are those of gnx_best_of_*, all before any output is written: GNX_EBASE in ANY candidate pair fails the call; GNX_EINVAL
+ * also for an odd n_reads, an option outside its range, another mode, a null required output; GNX_EDEVICE without a device, after the
+ * argument checks; GNX_ETRACE is passed through from the span stage; never GNX_ERANGE; n_reads == 0: GNX_OK.
+ * Routes: gnx_best_of_*'s body.  The score stage asks for the target start as well (gnx_timing.fast_path 10 under the sweep's conditions,
+ * else the align route with both positions read off the CIGAR on the device); pair_select_kernel (one wave per pair, the K1 * K2
+ * combinations strided over its lanes, no limit on K1 or K2) stands where the first-maximum kernel stands; the CIGAR stage is the same.
+ * The result does not depend on launch geometry or sub-batch cuts.  The call runs on context 0; gnx_get_timing describes the score stage. */
+int gnx_best_pair_by_offset(const gnx_params *p, const gnx_pair_opts *o, int64_t n_reads, const uint8_t *read_cat, const int64_t *read_off,
+                            const int64_t *cand_off, const int64_t *cand_start, const int64_t *cand_len, const uint8_t *cand_strand,
+                            int32_t *out_best, int64_t *out_score, int64_t *out_target_start, int64_t *out_target_end,
+                            int64_t *out_second_score, uint8_t *out_proper, int64_t *out_tlen,
+                            int64_t *out_cand_score, int64_t *out_cand_start, int64_t *out_cand_end,
+                            gnx_cigar **out_ops, int64_t **out_ops_off);
+int gnx_best_pair_windows(const gnx_params *p, const gnx_pair_opts *o, int64_t n_reads, const uint8_t *read_cat, const int64_t *read_off,
+                          const uint8_t *target_buf, int64_t target_buf_len,
+                          const int64_t *cand_off, const int64_t *cand_start, const int64_t *cand_len, const uint8_t *cand_strand,
+                          int32_t *out_best, int64_t *out_score, int64_t *out_target_start, int64_t *out_target_end,
+                          int64_t *out_second_score, uint8_t *out_proper, int64_t *out_tlen,
+                          int64_t *out_cand_score, int64_t *out_cand_start, int64_t *out_cand_end,
+                          gnx_cigar **out_ops, int64_t **out_ops_off);
 
 /* ---- candidate windows for gnx_best_of_by_offset: a k-mer index of the resident reference and seed votes (an extension, no Go signature) -- */
 /* Index of the resident reference (gnx_set_reference / _synthetic), built on the device from the packed words and kept there, on context 0.

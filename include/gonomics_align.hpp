@@ -323,6 +323,73 @@ inline std::vector<Mapped> MapReads(int mode, const ScoreMatrix &scores, int64_t
     return out;
 }
 
+// ---- best proper pair (gnx_best_pair_*; an extension): reads[2k] and reads[2k + 1] are mates and are placed together ----
+// Mode GNX_AFFINE_GAP_LOCAL.  Per read a BestOf plus the alignment's span relative to the chosen window (TargetStart, Hit.TargetEnd), the
+// window's start in the caller's coordinates and the best score among the read's other candidates (HasSecond = false: none).  Per pair:
+// Proper and Tlen (0 when not proper).  gnx_align.h states the selection rule.
+struct PairOpts { int64_t MinInsert = 0, MaxInsert = 0, UnpairedPenalty = 0; };
+struct PairedRead { BestOf Hit; int64_t TargetStart = 0, WindowStart = 0, SecondScore = 0; bool HasSecond = false; std::vector<int64_t> CandStarts, CandEnds; };
+struct ReadPairs { std::vector<PairedRead> Reads; std::vector<uint8_t> Proper; std::vector<int64_t> Tlen; };
+namespace detail {
+inline ReadPairs best_pair(const gnx_params &p, const PairOpts &o, const std::vector<std::vector<dna::Base>> &reads, const std::vector<dna::Base> *tcat,
+                           const std::vector<int64_t> &coff, const std::vector<int64_t> &cstart, const std::vector<int64_t> &clen, const std::vector<uint8_t> &cstrand, bool cigar) {
+    const int64_t n = (int64_t)reads.size();
+    std::vector<int64_t> roff((size_t)n + 1, 0);
+    for (int64_t k = 0; k < n; k++) roff[(size_t)k + 1] = roff[(size_t)k] + (int64_t)reads[(size_t)k].size();
+    std::vector<dna::Base> rcat((size_t)roff[(size_t)n] + 1);
+    for (int64_t k = 0; k < n; k++) std::copy(reads[(size_t)k].begin(), reads[(size_t)k].end(), rcat.begin() + roff[(size_t)k]);
+    const size_t nn = (size_t)std::max<int64_t>(n, 1), nc = std::max<size_t>(cstart.size(), 1);
+    std::vector<int32_t> best(nn, -1);
+    std::vector<int64_t> sc(nn, 0), start(nn, 0), end(nn, 0), second(nn, 0), tlen(nn, 0), cs(nc, 0), cb(nc, 0), ce(nc, 0);
+    std::vector<uint8_t> proper(nn, 0);
+    const gnx_pair_opts po = {o.MinInsert, o.MaxInsert, o.UnpairedPenalty, 0};
+    gnx_cigar *ops = nullptr; int64_t *off = nullptr;
+    const int rc = tcat ? gnx_best_pair_windows(&p, &po, n, rcat.data(), roff.data(), tcat->data(), (int64_t)tcat->size(), coff.data(), cstart.data(), clen.data(), cstrand.data(), best.data(),
+                                                sc.data(), start.data(), end.data(), second.data(), proper.data(), tlen.data(), cs.data(), cb.data(), ce.data(), cigar ? &ops : nullptr, cigar ? &off : nullptr)
+                        : gnx_best_pair_by_offset(&p, &po, n, rcat.data(), roff.data(), coff.data(), cstart.data(), clen.data(), cstrand.data(), best.data(),
+                                                  sc.data(), start.data(), end.data(), second.data(), proper.data(), tlen.data(), cs.data(), cb.data(), ce.data(), cigar ? &ops : nullptr, cigar ? &off : nullptr);
+    if (rc) raise(rc);
+    ReadPairs out;
+    out.Reads.resize((size_t)n);
+    for (int64_t k = 0; k < n; k++) {
+        PairedRead &r = out.Reads[(size_t)k];
+        const int64_t c0 = coff[(size_t)k], c1 = coff[(size_t)k + 1];
+        r.Hit.Best = best[(size_t)k]; r.Hit.Score = sc[(size_t)k]; r.Hit.TargetEnd = end[(size_t)k]; r.TargetStart = start[(size_t)k];
+        r.Hit.CandScores.assign(cs.begin() + c0, cs.begin() + c1);
+        r.CandStarts.assign(cb.begin() + c0, cb.begin() + c1);
+        r.CandEnds.assign(ce.begin() + c0, ce.begin() + c1);
+        if (r.Hit.Best >= 0) r.WindowStart = cstart[(size_t)(c0 + r.Hit.Best)];
+        r.HasSecond = second[(size_t)k] != INT64_MIN;
+        r.SecondScore = r.HasSecond ? second[(size_t)k] : 0;
+        for (int64_t x = cigar ? off[k] : 0; cigar && x < off[k + 1]; x++) r.Hit.Route.push_back(Cigar{ops[x].run_length, ops[x].op});
+    }
+    out.Proper.assign(proper.begin(), proper.begin() + n / 2);
+    out.Tlen.assign(tlen.begin(), tlen.begin() + n / 2);
+    if (cigar) { gnx_free(ops); gnx_free(off); }
+    return out;
+}
+} // namespace detail
+// candidates: windows of the resident reference or, with target given, of that sequence
+inline ReadPairs MapBestPair(const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, const std::vector<std::vector<dna::Base>> &reads,
+                             const std::vector<std::vector<RefCandidate>> &candidates, const PairOpts &o, bool cigar = true, const std::vector<dna::Base> *target = nullptr) {
+    std::vector<int64_t> coff(reads.size() + 1, 0), cstart, clen;
+    std::vector<uint8_t> cstrand;
+    for (size_t r = 0; r < reads.size(); r++) {
+        for (const auto &cd : candidates[r]) { cstart.push_back(cd.Start); clen.push_back(cd.Len); cstrand.push_back(cd.Strand); }
+        coff[r + 1] = (int64_t)cstart.size();
+    }
+    cstart.push_back(0); clen.push_back(0); cstrand.push_back(0); // (data() of an empty vector may be null)
+    return detail::best_pair(detail::params(GNX_AFFINE_GAP_LOCAL, scores, gapOpen, gapExtend, 10000, 10000), o, reads, target, coff, cstart, clen, cstrand, cigar);
+}
+// mate pairs in, placements out: SeedCandidates over all mates, then MapBestPair on its tables (WindowStart: a position of the resident reference)
+inline ReadPairs MapReadPairs(const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, const std::vector<std::vector<dna::Base>> &reads, const PairOpts &o,
+                              const SeedVoteOpts &vo = SeedVoteOpts(), bool cigar = true) {
+    const std::vector<std::vector<VotedCandidate>> voted = SeedCandidates(reads, vo);
+    std::vector<std::vector<RefCandidate>> cands(reads.size());
+    for (size_t r = 0; r < reads.size(); r++) for (const auto &v : voted[r]) cands[r].push_back(RefCandidate{v.Start, v.Len, v.Strand});
+    return MapBestPair(scores, gapOpen, gapExtend, reads, cands, o, cigar);
+}
+
 inline void AffineGapLocalEngine(const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, std::vector<TargetQueryPair> &pairs) {
     std::vector<std::vector<dna::Base>> t, q;
     for (auto &p : pairs) { t.push_back(p.Target); q.push_back(p.Query); }
