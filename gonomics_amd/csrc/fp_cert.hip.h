@@ -1,0 +1,184 @@
+// fp_cert.hip.h -- fast path: gapless reads leave by certificate before the sweep (scan + certify, live-list gather)
+// Part of libgonomics_align_hip.so; included by gnx_align.hip (one translation unit).  See DESIGN.md section 4.22.
+#pragma once
+#include "gnx_common.hip.h"
+#include "fp_cert_decide.h"
+
+namespace {
+// ------------------------------------------------------------------------------------------------------
+// A read that matches its window without an indel, with a small mismatch deficit and no second copy in the window has a provably
+// unique optimal alignment: leading gap, one diagonal, trailing gap (a few trailing bases possibly on the window's last columns).
+// fp_cert_kernel proves that per pair -- one wave per pair -- and writes score, run count and staged runs exactly as fp_walk_kernel
+// would have; every other pair gets live[p] = 1 and goes through sweep and walk as before.
+//   1. the read's n - 15 16-mers (2 bits per base) go into an open-addressing table in LDS (512 slots, full key compare) with a
+//      16 384-bit prefilter beside it;
+//   2. the window is streamed 16 columns per lane and round (one 16-byte load, or one dword of the packed reference): a lane packs
+//      its columns into a 32-bit code word, takes the word of the lane before it (__shfl_up) and looks up the 16 16-mers that START in
+//      that earlier word's last 15 columns or at its own first one (v_alignbit).  Bytes that are not A C G T count as their two low bits:
+//      a false hit can only refuse a pair, the decision below re-scores from the real bytes;
+//   3. all hits must share one diagonal c (wave-wide min == max); a read that holds a 16-mer twice puts two hits on two diagonals;
+//   4. the bases under the read on diagonal c, at the window's start and at its end are staged in LDS, and lane 0 runs the
+//      decision arithmetic the host shares (gnx_cert_decide).
+// Windows of the packed reference that hold an exception (N, byte >= 5) are not certified; bytes >= 5 raise the sweep's error flag.
+// ------------------------------------------------------------------------------------------------------
+constexpr int CERT_K = 16;
+constexpr int CERT_SLOTS = 512;  // table slots (at most 145 keys); the prefilter has 32 bits per slot word
+constexpr int CERT_NMAX = 160;   // one row block
+
+__device__ __forceinline__ unsigned cert_hash(unsigned code) { return code * 0x9E3779B1u; } // slot = top 9 bits, filter bit = top 14 bits
+// 2-bit codes of four dna.Base bytes -> 8 bits (byte k at bits 2k)
+__device__ __forceinline__ unsigned cert_pack4(unsigned w) {
+    unsigned x = w & 0x03030303u;
+    x = (x | (x >> 6)) & 0x000F000Fu;
+    return (x | (x >> 12)) & 0xFFu;
+}
+
+template <bool PK>
+__global__ __launch_bounds__(64) void fp_cert_kernel(const PairPlan *__restrict__ plans, int n_pairs,
+                                                     const uint8_t *__restrict__ a_buf, const int64_t *__restrict__ a_start,
+                                                     const uint8_t *__restrict__ b_buf, const int64_t *__restrict__ b_start,
+                                                     KParams kp, TbParams tp, gnx_cigar *__restrict__ stage, int cap,
+                                                     int64_t *__restrict__ score_out, int64_t *__restrict__ nops,
+                                                     int64_t *__restrict__ live, int *__restrict__ err) {
+    __shared__ unsigned keys[CERT_SLOTS];
+    __shared__ int qv[CERT_SLOTS];
+    __shared__ unsigned filt[CERT_SLOTS];
+    __shared__ uint8_t sa[CERT_NMAX], sd[CERT_NMAX], sf[CERT_NMAX], sl[CERT_NMAX];
+    __shared__ int64_t sc64[25];
+    __shared__ GnxCertMatrix smx;
+    __shared__ int64_t res[3];
+    const int p = (int)blockIdx.x;
+    if (p >= n_pairs) return;
+    const int lane = threadIdx.x;
+    const PairPlan pl = plans[p];
+    const int n = pl.n, m = pl.m;
+    bool bad = false;
+    bool out = n < CERT_K || n > CERT_NMAX || m < n + 2 || kp.o4 >= 0 || tp.ci < n || tp.cj < m; // (wave-uniform)
+    BetaSrcT<PK ? 1 : 0> bp;
+    const int64_t boff = b_start[pl.src];
+    bp.init(b_buf, kp, boff, m);
+    if (PK && bp.dirty) out = true;
+    if (out) { if (lane == 0) live[p] = 1; return; }
+    const uint8_t *ap = a_buf + a_start[pl.src];
+
+    // ---- 1. the read and its 16-mers ----
+    for (int x = lane; x < CERT_SLOTS; x += 64) { qv[x] = -1; filt[x] = 0; }
+    bool read_ok = true;
+    for (int i = lane; i < n; i += 64) { const uint8_t v = ap[i]; sa[i] = v; if (v >= 4) read_ok = false; }
+    if (__any(!read_ok)) { if (lane == 0) live[p] = 1; return; } // (N in the read: no certificate; a byte >= 5: the sweep flags it)
+    if (lane == 0) { // the call's matrix, rebased (kp holds 4 x the scores)
+#pragma unroll
+        for (int x = 0; x < 25; x++) sc64[x] = (int64_t)(kp.sc4[x] >> 2);
+        gnx_cert_matrix_init(&smx, sc64, (int64_t)(kp.o4 >> 2), (int64_t)(kp.e4 >> 2));
+    }
+    __syncthreads();
+    if (!smx.ok) { if (lane == 0) live[p] = 1; return; }
+    for (int q = lane; q + CERT_K <= n; q += 64) {
+        unsigned code = 0;
+#pragma unroll
+        for (int t = 0; t < CERT_K; t++) code |= (unsigned)sa[q + t] << (2 * t);
+        const unsigned h = cert_hash(code);
+        unsigned slot = h >> 23;
+        while (atomicCAS(&qv[slot], -1, q) != -1) slot = (slot + 1) & (CERT_SLOTS - 1); // (a key the read holds twice takes two slots)
+        keys[slot] = code;
+        atomicOr(&filt[h >> 23], 1u << ((h >> 18) & 31u));
+    }
+    __syncthreads();
+
+    // ---- 2. the window, 16 columns per lane and round, aligned to the 16-byte / dword grid of its buffer ----
+    const int sh = PK ? (int)(boff & 15) : (int)((uintptr_t)(b_buf + boff) & 15); // columns of the first group that lie before the window
+    const int n_groups = (sh + m + 15) >> 4;
+    const uint8_t *bw = b_buf + boff - sh;              // bytes: the first group's address (16-byte aligned)
+    const unsigned *w2 = PK ? kp.b2 + (boff >> 4) : nullptr; // packed: the first group's dword
+    auto load_group = [&](int g, bool &badv) -> unsigned {
+        if (g >= n_groups) return 0u;
+        if (PK) return w2[g];
+        const int c0 = 16 * g - sh; // the group's first column (0-based in the window)
+        if (c0 >= 0 && c0 + 16 <= m) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(bw + 16 * (int64_t)g);
+            const unsigned any = v.x | v.y | v.z | v.w | (v.x + 0x03030303u) | (v.y + 0x03030303u) | (v.z + 0x03030303u) | (v.w + 0x03030303u);
+            if (any & 0xF8F8F8F8u) badv = true; // a byte >= 5 (>= 8 has a high bit set; 5 .. 7 get one by the add; a carry needs one already)
+            return cert_pack4(v.x) | (cert_pack4(v.y) << 8) | (cert_pack4(v.z) << 16) | (cert_pack4(v.w) << 24);
+        }
+        unsigned cw = 0;
+        for (int t = 0; t < 16; t++) {
+            const int col = c0 + t;
+            if (col >= 0 && col < m) { const unsigned v = bw[16 * (int64_t)g + t]; if (v >= 5) badv = true; cw |= (v & 3u) << (2 * t); }
+        }
+        return cw;
+    };
+    int dmin = 0x7fffffff, dmax = -0x7fffffff - 1;
+    unsigned carry = 0;
+    unsigned nxt = load_group(lane, bad);
+    for (int g0 = 0; g0 < n_groups; g0 += 64) {
+        const unsigned cw = nxt;
+        nxt = load_group(g0 + 64 + lane, bad); // the next round's load is in flight while this one is looked up
+        unsigned prev = __shfl_up(cw, 1, 64);
+        if (lane == 0) prev = carry;
+        carry = __shfl(cw, 63, 64);
+        const int s0 = 16 * (g0 + lane) - sh - 16; // window column (0-based) of the earlier word's first base
+#pragma unroll
+        for (int t = 1; t <= 16; t++) {
+            const unsigned code = t < 16 ? __builtin_amdgcn_alignbit(cw, prev, 2 * t) : cw;
+            const unsigned h = cert_hash(code);
+            if ((filt[h >> 23] >> ((h >> 18) & 31u)) & 1u) {
+                const int s = s0 + t;
+                if (s >= 0 && s + CERT_K <= m) {
+                    unsigned slot = h >> 23;
+                    int q;
+                    while ((q = qv[slot]) != -1 && dmin >= dmax) {
+                        if (keys[slot] == code) { dmin = min(dmin, s - q); dmax = max(dmax, s - q); }
+                        slot = (slot + 1) & (CERT_SLOTS - 1);
+                    }
+                }
+            }
+        }
+        if (__any(dmin < dmax)) break; // two diagonals: no certificate (the rest of the window's bytes are the sweep's to check)
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { dmin = min(dmin, __shfl_xor(dmin, d, 64)); dmax = max(dmax, __shfl_xor(dmax, d, 64)); }
+    if (bad) atomicOr(err, 1);
+    const int c = dmin;
+    if (dmin != dmax || c <= 0 || c >= m - n) { if (lane == 0) live[p] = 1; return; } // (no hit at all: dmin > dmax)
+
+    // ---- 3. the real bases under the read on diagonal c, on the window's first and last columns; the decision ----
+    for (int i = lane; i < n; i += 64) {
+        sd[i] = (uint8_t)bp.at(c + i);
+        sf[i] = (uint8_t)bp.at(i);
+        sl[i] = (uint8_t)bp.at(m - n + i);
+    }
+    __syncthreads();
+    if (lane == 0) {
+        int64_t ds = 0, sc = 0;
+        const int ok = gnx_cert_decide(&smx, sa, n, sd, sf, sl, m, c, CERT_K, tp.ci, tp.cj, &ds, &sc);
+        res[0] = ok; res[1] = ds; res[2] = sc;
+    }
+    __syncthreads();
+    if (!res[0]) { if (lane == 0) live[p] = 1; return; }
+    if (lane == 0) {
+        // the runs in traceback order, as fp_walk_kernel stages them: [d* M] [m - n - c I] [n - d* M] [c I]
+        const int64_t ds = res[1];
+        gnx_cigar *stg = stage + (int64_t)p * cap;
+        int cnt = 0;
+        auto put = [&](int op, int64_t run) { gnx_cigar g; g.run_length = run; g.op = (uint8_t)op; for (int z = 0; z < 7; z++) g._pad[z] = 0; stg[cnt++] = g; };
+        if (ds > 0) put(0, ds);
+        put(1, (int64_t)m - n - c);
+        put(0, (int64_t)n - ds);
+        put(1, c);
+        nops[p] = cnt;
+        score_out[p] = res[2];
+        live[p] = 0;
+    }
+}
+
+// the live pairs in ascending order: list and gathered plans (off = exclusive scan of live[])
+__global__ __launch_bounds__(256) void fp_cert_gather_kernel(int n_pairs, const int64_t *__restrict__ live, const int64_t *__restrict__ off,
+                                                             const PairPlan *__restrict__ plans, int *__restrict__ list, PairPlan *__restrict__ out) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pairs || !live[p]) return;
+    const int64_t k = off[p];
+    list[k] = p;
+    out[k] = plans[p];
+}
+
+} // namespace

@@ -50,7 +50,7 @@ __global__ __launch_bounds__(64) void fp_walk_kernel(const PairPlan *__restrict_
     if (a >= n_active) return;
     const int lane = threadIdx.x & 63;
     const bool writer = !CW || lane == 0;
-    const int p = FIRST ? a + p_base : active[a];
+    const int p = FIRST ? (active ? active[a] : a + p_base) : active[a]; // (FIRST with a list: the pairs the gapless certificate left, fp_cert.hip.h)
     const PairPlan pl = plans[p];
     BetaSrc wbeta; // (the diagonal shortcuts read bases: FIRST walks, and window walks of reads with whole row blocks between two handed-down rows)
     const bool wb = FIRST || (!TILED && !XP && pl.strips >= 2);

@@ -39,6 +39,7 @@
 #include "fill_const.hip.h"
 #include "traceback.hip.h"
 #include "fp_walk.hip.h"
+#include "fp_cert.hip.h"
 #include "aux_kernels.hip.h"
 #include "const_long.hip.h"
 #include "const_long_wg.hip.h"
@@ -132,6 +133,7 @@ struct Ctx {
     hipStream_t own_stream = nullptr, s_in = nullptr;
     DevBuf trace, hcol, rowbuf, dcol, plans, nops, misc;
     DevBuf strip_map, tb_scr, tb_scr_off, scan_tmp, fp_tail, fp_rowi, fp_ckpt, fp_states, fp_stage, fp_wplans[2], fp_active[2], fp_thcol, fp_ttrace, fp_redo, fp_strag, mx_idx, mx_tab, mx_score, mx_off, mx_ops, fp_prog;
+    DevBuf fp_cflag, fp_live, fp_gplans; // the gapless certificate (fp_cert.hip.h): live flags + their scan, the live list, the live pairs' plans
     DevBuf in_a, in_b, in_as, in_al, in_bs, in_bl, out_score, out_off, out_ops, out_end, sc_pairs, sc_mat, sc_err;
     // pipelined host entry (gnx_host.hip.h): double-buffered inputs, results accumulated on the device, the resident reference
     DevBuf pin_a[2], pin_as[2], pin_b[2], pin_bs[2], res_score, res_off, res_ops, ref, gat_score, gat_off, gat_ops;
@@ -266,6 +268,8 @@ int64_t max_abs_pen(const gnx_params *p, bool affine) {
     return mx;
 }
 
+std::atomic<int64_t> g_cert_ok{0}, g_cert_offered{0}; // pairs certified gapless / offered to the certificate (gnx_debug_counter(9 / 10))
+
 // Fast path for batches of short-alpha global affine alignments (see fp_walk_kernel).  Returns GNX_OK, an error,
 // or -1 when the batch should go through the general path after all (workspace too small / staging overflow).
 // `first` = first sub-batch of a call: later sub-batches keep the error flags and the CIGAR offset carry.
@@ -347,7 +351,8 @@ int run_device_fp(const gnx_params *prm, const KParams &kp, const TbParams &tp, 
     const int WW = fp_spec_wwords(K);
     const size_t wtrace_b = (size_t)np * K * WW * QA * G * 16;
     const size_t need = wtrace_b + (size_t)coff * 8 + (size_t)roff * 4 + (size_t)rboff * 8 +
-                        (size_t)np * (CAP * sizeof(gnx_cigar) + sizeof(FpState) + (1 + 2 * K) * sizeof(PairPlan) + (size_t)K * (H * 4 + G * 4) + 40);
+                        (size_t)np * (CAP * sizeof(gnx_cigar) + sizeof(FpState) + (1 + 2 * K) * sizeof(PairPlan) + (size_t)K * (H * 4 + G * 4) + 40 +
+                                        ((S == 1 && !xp) ? 20 + sizeof(PairPlan) : 0)); // (.. + the gapless certificate's flags, their scan, the live list and the live pairs' plans)
     if ((int64_t)need > c.ws_limit) { if (getenv("GNX_DEBUG")) fprintf(stderr, "[gnx fp] working set %zu B exceeds the workspace limit -> general path\n", need); return -1; }
     if ((rc = c.trace.ensure(wtrace_b))) return rc;
     if ((rc = c.hcol.ensure((size_t)np * ((size_t)K * H + 1) * 4))) return rc;   // [0,np) h(n,m) of the forward sweep, then the window hcol slots
@@ -397,7 +402,46 @@ int run_device_fp(const gnx_params *prm, const KParams &kp, const TbParams &tp, 
     const int tiles_per = (int)((m_maxb + FP_TILE - 1) / FP_TILE);
     double refill_ms = 0;
 
-    auto forward = [&](int p0, int cnt, hipStream_t st) -> int {
+    // Gapless reads leave by certificate before the sweep (fp_cert.hip.h): reads of one row block, not transposed.
+    // GNX_FP_CERT=0: everyone through the sweep (same results).  The bases may differ from call to call: decided on every call.
+    // Only batches that fill the device more than once (8 pairs x 3 waves per SIMD): a sweep of fewer waves takes one wave's time however
+    // many pairs leave it, and the certificate's launches and its read-back would only add to a small call's latency (16 threads of
+    // single-pair calls, tests/test_concurrent_pairs.py: 9.1 -> 7.3 x the serial rate).  GNX_FP_CERT=2: whatever the batch size (tests).
+    const char *certenv = getenv("GNX_FP_CERT");
+    const bool cert = S == 1 && !xp && prm->gap_open < 0 && !(certenv && certenv[0] == '0') &&
+                      ((certenv && certenv[0] == '2') || n_pairs > (int64_t)G8 * 3 * 4 * c.n_cu);
+    int n_live = np; // pairs the sweep and the first walk run for
+    int64_t *d_cflag = nullptr, *d_coff = nullptr;
+    int *d_live = nullptr;
+    PairPlan *d_gpl = nullptr;
+    if (cert) {
+        if ((rc = c.fp_cflag.ensure((size_t)(2 * np + 2) * 8))) return rc;
+        if ((rc = c.fp_live.ensure((size_t)np * 4))) return rc;
+        if ((rc = c.fp_gplans.ensure((size_t)np * sizeof(PairPlan)))) return rc;
+        d_cflag = reinterpret_cast<int64_t *>(c.fp_cflag.p); d_coff = d_cflag + np + 1; // [np] of the flags = the scan's carry word
+        d_live = reinterpret_cast<int *>(c.fp_live.p);
+        d_gpl = reinterpret_cast<PairPlan *>(c.fp_gplans.p);
+    }
+    auto certify = [&](hipStream_t st) -> int {
+        HIPCHK(hipMemsetAsync(d_cflag + np, 0, 8, st));
+        auto kc = kp.b2 ? fp_cert_kernel<true> : fp_cert_kernel<false>;
+        hipLaunchKernelGGL(kc, dim3((unsigned)np), dim3(64), 0, st, dpl, np, d_a, d_as, d_b, d_bs, kp, tp, d_stage, CAP, d_score, d_nops, d_cflag, d_err);
+        HIPCHK(hipGetLastError());
+        if ((rc = launch_scan(d_cflag, np, d_coff, d_cflag + np, st))) return rc;
+        hipLaunchKernelGGL(fp_cert_gather_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, np, d_cflag, d_coff, dpl, d_live, d_gpl);
+        HIPCHK(hipGetLastError());
+        int64_t nl = 0;
+        HIPCHK(hipMemcpyAsync(&nl, d_coff + np, 8, hipMemcpyDeviceToHost, st)); // the sweep's grid
+        HIPCHK(hipStreamSynchronize(st));
+        n_live = (int)nl;
+        g_cert_offered += np; g_cert_ok += np - n_live;
+        if (getenv("GNX_DEBUG")) fprintf(stderr, "[gnx fp] gapless certificate: %d of %d pairs certified, %d go through the sweep\n", np - n_live, np, n_live);
+        return GNX_OK;
+    };
+
+    // (cert: `splans` = the live pairs' plans gathered in ascending order; every plan keeps its own output offsets)
+    auto forward = [&](const PairPlan *splans, int cnt, hipStream_t st) -> int {
+        if (cnt <= 0) return GNX_OK;
         const dim3 grid8((unsigned)((cnt + G8 - 1) / G8));
         if (two) { // S row blocks ("levels"): one launch, each level following the one above it through the row buffer (GNX_NO_PIPE: a launch per level)
             int2 *rb = reinterpret_cast<int2 *>(c.rowbuf.p);
@@ -411,7 +455,7 @@ int run_device_fp(const gnx_params *prm, const KParams &kp, const TbParams &tp, 
             if (!no_pipe()) {
                 HIPCHK(hipMemsetAsync(prog, 0, ((size_t)S * W * 2 + 2) * 4, st)); // progress words, claim words, test switch
                 if ((rc = claim_test_switch(prog + (size_t)S * W * 2, st))) return rc;
-                hipLaunchKernelGGL(klev, dim3((unsigned)(S * W)), blockF, 0, st, dpl + p0, cnt, d_a, d_as, d_b, d_bs, kp, d_hfwd, d_ckpt, d_rowi, d_tail, d_err, rb, S, W, 0, 1, prog);
+                hipLaunchKernelGGL(klev, dim3((unsigned)(S * W)), blockF, 0, st, splans, cnt, d_a, d_as, d_b, d_bs, kp, d_hfwd, d_ckpt, d_rowi, d_tail, d_err, rb, S, W, 0, 1, prog);
                 HIPCHK(hipGetLastError());
                 int e = 0; // a level that waited 5 s for the one above it (a bug trap: the level above is always claimed by a running workgroup): sweep again, level by level
                 HIPCHK(hipMemcpyAsync(&e, d_err, 4, hipMemcpyDeviceToHost, st));
@@ -423,14 +467,14 @@ int run_device_fp(const gnx_params *prm, const KParams &kp, const TbParams &tp, 
                 if (getenv("GNX_DEBUG")) fprintf(stderr, "[gnx fp] a row block timed out waiting for the one above it -> one launch per level\n");
             }
             for (int level = 0; level < S; level++)
-                hipLaunchKernelGGL(klev, grid8, blockF, 0, st, dpl + p0, cnt, d_a, d_as, d_b, d_bs, kp, d_hfwd, d_ckpt, d_rowi, d_tail, d_err, rb, S, W, level, 0, prog);
+                hipLaunchKernelGGL(klev, grid8, blockF, 0, st, splans, cnt, d_a, d_as, d_b, d_bs, kp, d_hfwd, d_ckpt, d_rowi, d_tail, d_err, rb, S, W, level, 0, prog);
             HIPCHK(hipGetLastError());
             return GNX_OK;
         }
         auto k = xp ? (rows_per_lane == 19 ? fp_sweep_kernel<19, true> : fp_sweep_kernel<20, true>)
                  : kp.b2 ? (rows_per_lane == 19 ? fp_sweep_kernel<19, false, true> : fp_sweep_kernel<20, false, true>)
                          : (rows_per_lane == 19 ? fp_sweep_kernel<19, false> : fp_sweep_kernel<20, false>);
-        hipLaunchKernelGGL(k, grid8, blockF, 0, st, dpl + p0, cnt, d_a, d_as, d_b, d_bs, kp, d_hfwd, d_ckpt, d_rowi, d_tail, d_err);
+        hipLaunchKernelGGL(k, grid8, blockF, 0, st, splans, cnt, d_a, d_as, d_b, d_bs, kp, d_hfwd, d_ckpt, d_rowi, d_tail, d_err);
         HIPCHK(hipGetLastError());
         return GNX_OK;
     };
@@ -439,7 +483,8 @@ int run_device_fp(const gnx_params *prm, const KParams &kp, const TbParams &tp, 
     // the same row block is a straggler (a long gap on a row without a stored plane) and gets all remaining columns of that block as
     // tiles in the same round; walks that leave a row block through its top ask for a window of the block above.  A read of S row
     // blocks takes S rounds (plus those of its stragglers).  cnt2: [0], [1] = window requests (ping-pong), [2] = stragglers.
-    auto post = [&](int p0, int cnt, hipStream_t st, int *cnt2, hipEvent_t e1, hipEvent_t e2) -> int {
+    // first_list / n_first: the pairs of the first walk (null: all of [p0, p0+cnt)); pairs left out have their results already (cert)
+    auto post = [&](int p0, int cnt, hipStream_t st, int *cnt2, hipEvent_t e1, hipEvent_t e2, const int *first_list, int n_first) -> int {
         uint4 *wtr = reinterpret_cast<uint4 *>(c.trace.p) + (int64_t)p0 * K * WW * QA * G;
         int *whc = d_whcol + (int64_t)p0 * K * H;
         unsigned *wdc = reinterpret_cast<unsigned *>(c.dcol.p) + (int64_t)p0 * K * G;
@@ -468,11 +513,13 @@ int run_device_fp(const gnx_params *prm, const KParams &kp, const TbParams &tp, 
         auto force = [&](int round) { return (max_it >= 0 && round >= max_it) ? 1 : 0; };
         int h_cnt[4] = {0, 0, 0, 0};
         HIPCHK(hipMemsetAsync(cnt2, 0, 16, st));
-        hipLaunchKernelGGL(k_first, dim3((unsigned)(cw_first ? cnt : (cnt + 63) / 64)), blockT, 0, st, dpl, (const int *)nullptr, cnt, d_st, d_hfwd, d_rowi, d_tail,
-                           (const PairPlan *)nullptr, wtr, whc, tp, d_stage, d_score, d_nops, d_act[0] + p0, cnt2, wpl[0], d_err, p0, d_strag, cnt2 + 2, force(0), srb, K, WW, d_a, d_as, d_b, d_bs, kp);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(h_cnt, cnt2, 16, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
+        if (n_first > 0) {
+            hipLaunchKernelGGL(k_first, dim3((unsigned)(cw_first ? n_first : (n_first + 63) / 64)), blockT, 0, st, dpl, first_list, n_first, d_st, d_hfwd, d_rowi, d_tail,
+                               (const PairPlan *)nullptr, wtr, whc, tp, d_stage, d_score, d_nops, d_act[0] + p0, cnt2, wpl[0], d_err, p0, d_strag, cnt2 + 2, force(0), srb, K, WW, d_a, d_as, d_b, d_bs, kp);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(h_cnt, cnt2, 16, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+        }
         n_act = h_cnt[0];
         int n_strag = h_cnt[2];
         const int max_rounds = 6 * S + 32;
@@ -554,9 +601,10 @@ int run_device_fp(const gnx_params *prm, const KParams &kp, const TbParams &tp, 
     };
 
     HIPCHK(hipEventRecord(c.ev[0], stream));
-    if ((rc = forward(0, np, stream))) return rc;
+    if (cert && (rc = certify(stream))) return rc; // (inside the bracket: fill_ms and dominant_ms include it)
+    if ((rc = forward(cert ? d_gpl : dpl, n_live, stream))) return rc;
     HIPCHK(hipEventRecord(c.ev[1], stream));
-    if ((rc = post(0, np, stream, d_cnt, c.ev[4], c.ev[5]))) return rc;
+    if ((rc = post(0, np, stream, d_cnt, c.ev[4], c.ev[5], cert ? d_live : nullptr, n_live))) return rc;
     if ((rc = launch_scan(d_nops, np, d_ops_off, d_carry, stream))) return rc;
     hipLaunchKernelGGL(fp_compact_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, stream, np, d_st, d_stage, d_nops, d_ops_off, d_ops, ops_capacity, d_err, CAP);
     HIPCHK(hipGetLastError());
@@ -1744,7 +1792,8 @@ int run_device(const gnx_params *prm, int64_t n_pairs,
         if (fp) {
             // sub-batches whose fast-path working set (checkpoints, planes, window slots, staging) fits the workspace
             const int Kw = S > 1 ? std::min(FP_SPEC, S) : 1; // windows per request (at most)
-            const size_t fixed = (size_t)Kw * ((size_t)fp_spec_wwords(Kw) * QA * G * 16 + H * 4 + G * 4 + 2 * sizeof(PairPlan)) + fp_cap(S) * sizeof(gnx_cigar) + sizeof(FpState) + sizeof(PairPlan) + 72;
+            const size_t fixed = (size_t)Kw * ((size_t)fp_spec_wwords(Kw) * QA * G * 16 + H * 4 + G * 4 + 2 * sizeof(PairPlan)) + fp_cap(S) * sizeof(gnx_cigar) + sizeof(FpState) + sizeof(PairPlan) + 72 +
+                                 ((S == 1 && !xp) ? 20 + sizeof(PairPlan) : 0); // (the gapless certificate's buffers, see run_device_fp)
             // ... of about equal size (a small last sub-batch would leave most of the GPU idle for the length of a sweep wave)
             std::vector<int64_t> cb{0};
             size_t acc_b = 0, total_b = 0;
@@ -2790,7 +2839,7 @@ void gnx_shutdown(void) {
         if (!c.inited) continue;
         (void)hipSetDevice(c.device);
         (void)hipDeviceSynchronize();
-        DevBuf *bufs[] = {&c.strip_map, &c.tb_scr, &c.tb_scr_off, &c.scan_tmp, &c.fp_redo, &c.fp_strag, &c.mx_idx, &c.mx_tab, &c.mx_score, &c.mx_off, &c.mx_ops, &c.fp_prog, &c.fp_tail, &c.fp_thcol, &c.fp_ttrace, &c.fp_rowi, &c.fp_ckpt, &c.fp_states, &c.fp_stage,
+        DevBuf *bufs[] = {&c.strip_map, &c.tb_scr, &c.tb_scr_off, &c.scan_tmp, &c.fp_redo, &c.fp_strag, &c.mx_idx, &c.mx_tab, &c.mx_score, &c.mx_off, &c.mx_ops, &c.fp_prog, &c.fp_cflag, &c.fp_live, &c.fp_gplans, &c.fp_tail, &c.fp_thcol, &c.fp_ttrace, &c.fp_rowi, &c.fp_ckpt, &c.fp_states, &c.fp_stage,
                           &c.fp_wplans[0], &c.fp_wplans[1], &c.fp_active[0], &c.fp_active[1], &c.trace, &c.hcol, &c.rowbuf, &c.dcol, &c.plans, &c.nops, &c.misc, &c.in_a, &c.in_b,
                           &c.in_as, &c.in_al, &c.in_bs, &c.in_bl, &c.out_score, &c.out_off, &c.out_ops, &c.out_end, &c.sc_pairs, &c.sc_mat, &c.sc_err,
                           &c.pin_a[0], &c.pin_a[1], &c.pin_as[0], &c.pin_as[1], &c.pin_b[0], &c.pin_b[1], &c.pin_bs[0], &c.pin_bs[1], &c.res_score, &c.res_off, &c.res_ops,
@@ -3806,13 +3855,41 @@ int gnx_debug_occupy(int n_workgroups, int milliseconds) {
     return GNX_OK;
 }
 
+/* diagnostics, host only (no device is touched): the fast path's gapless certificate for ONE pair, with a naive K-mer
+ * scan and the decision arithmetic the kernel runs (fp_cert_decide.h).  K is a parameter so that small pairs can exercise the
+ * "K is long enough" rule; the kernel uses 16.  out[0..4) = certified (0 / 1), diagonal c, d*, score. */
+int gnx_debug_gapless_certificate(const gnx_params *p, const uint8_t *a, int64_t n, const uint8_t *b, int64_t m, int64_t K, int64_t *out) {
+    g_err[0] = 0;
+    if (!getenv("GNX_DEBUG_ENTRY")) { set_err("gnx_debug_gapless_certificate is a test hook: set GNX_DEBUG_ENTRY=1%s", ""); return GNX_EINVAL; }
+    KParams kp; TbParams tp; bool affine, local, lowmem;
+    int rc = check_params(p, kp, tp, affine, local, lowmem);
+    if (rc) return rc;
+    if (!a || !b || !out || n < 1 || m < 1 || K < 1 || !affine || local) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    out[0] = out[1] = out[2] = out[3] = 0;
+    GnxCertMatrix mx;
+    gnx_cert_matrix_init(&mx, p->scores, p->gap_open, p->gap_extend);
+    int64_t c = 0, ds = 0, sc = 0;
+    for (int64_t j = 0; j < m; j++) if (b[j] >= 5) return GNX_OK; // (the kernel's scan raises the sweep's error flag for such a window: nothing is certified)
+    if (m < n + 2 || K > n || !gnx_cert_scan_naive(a, n, b, m, K, &c)) return GNX_OK;
+    if (c <= 0 || c >= m - n) return GNX_OK;
+    if (!gnx_cert_decide(&mx, a, n, b + c, b, b + (m - n), m, c, K, tp.ci, tp.cj, &ds, &sc)) return GNX_OK;
+    out[0] = 1; out[1] = c; out[2] = ds; out[3] = sc;
+    return GNX_OK;
+}
+
 /* diagnostics: counters kept on context 0's device.  which = 0: items of piped launches that were run by a workgroup other than
  * their own since the last reset (claim_items: the abnormal path the tests force); reset != 0 zeroes it after reading. */
 int gnx_debug_counter(int which, int reset, int64_t *out) {
     std::lock_guard<std::mutex> api(g_api_mu);
     CtxScope sc(ctx_at(0));
     g_err[0] = 0;
-    if (which < 0 || which > 8 || !out) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (which < 0 || which > 10 || !out) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (which >= 9) { // the fast path's gapless certificate: pairs certified / pairs offered to it
+        std::atomic<int64_t> &v = which == 9 ? g_cert_ok : g_cert_offered;
+        *out = v.load();
+        if (reset) v = 0;
+        return GNX_OK;
+    }
     if (which >= 7) { // gnx_seed_candidates: reads voted with the table in LDS / in a slab
         std::atomic<int64_t> &v = which == 7 ? g_sv_lds : g_sv_slab;
         *out = v.load();
