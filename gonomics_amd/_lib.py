@@ -24,7 +24,9 @@ EXPORTS = ["gnx_device_count", "gnx_init", "gnx_shutdown", "gnx_last_error", "gn
            "gnx_locate_span_batch", "gnx_locate_span_batch_windows", "gnx_locate_span_batch_by_offset",
            "gnx_affine_gap_chunk_score_batch", "gnx_multiple_affine_gap_score_batch",
            "gnx_best_of_by_offset", "gnx_best_of_windows", "gnx_best_pair_by_offset", "gnx_best_pair_windows",
-           "gnx_reference_index_build", "gnx_reference_index_info", "gnx_reference_index_get", "gnx_seed_candidates"]
+           "gnx_reference_index_build", "gnx_reference_index_info", "gnx_reference_index_get", "gnx_seed_candidates",
+           "gnx_summarize_batch", "gnx_summarize_batch_windows", "gnx_summarize_batch_by_offset"]
+GNX_XCOL_EQ, GNX_XCOL_X = 3, 4
 
 
 class GnxCigar(ctypes.Structure):
@@ -55,6 +57,16 @@ class GnxSeedVoteOpts(ctypes.Structure):
 
 class GnxPairOpts(ctypes.Structure):
     _fields_ = [("min_insert", ctypes.c_int64), ("max_insert", ctypes.c_int64), ("unpaired_penalty", ctypes.c_int64), ("_reserved", ctypes.c_int64)]
+
+
+SUMMARY_FIELDS = ("rescore", "alpha_used", "beta_used", "alpha_start", "alpha_end", "n_equal", "n_mismatch", "ins_bases", "del_bases", "gap_runs", "n_xops")
+
+
+class GnxAlnSummary(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_int64) for f in SUMMARY_FIELDS] + [("_reserved", ctypes.c_int64)]
+
+
+SUMMARY_DTYPE = np.dtype([(f, np.int64) for f in SUMMARY_FIELDS] + [("_reserved", np.int64)])
 
 
 class GnxError(RuntimeError):
@@ -154,6 +166,13 @@ def lib():
         L.gnx_reference_index_get.restype = ctypes.c_int
         L.gnx_seed_candidates.argtypes = [ctypes.POINTER(GnxSeedVoteOpts), i64, c_p, c_p] + [ctypes.POINTER(c_p)] * 5
         L.gnx_seed_candidates.restype = ctypes.c_int
+        if hasattr(L, "gnx_summarize_batch"):  # (absent from older builds loaded through GNX_LIB_PATH for A/B runs)
+            L.gnx_summarize_batch.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_p)]
+            L.gnx_summarize_batch.restype = ctypes.c_int
+            L.gnx_summarize_batch_windows.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, i64, c_p, c_p, c_p, i64, c_p, c_p, c_p, c_p, c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_p)]
+            L.gnx_summarize_batch_windows.restype = ctypes.c_int
+            L.gnx_summarize_batch_by_offset.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_p)]
+            L.gnx_summarize_batch_by_offset.restype = ctypes.c_int
         L.gnx_seed_index_build.argtypes = [c_p, c_p, i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(i64)]
         L.gnx_seed_index_build.restype = ctypes.c_int
         L.gnx_seed_index_set.argtypes = [c_p, c_p, i64, c_p, c_p, i64, ctypes.c_int]
@@ -627,6 +646,57 @@ def seed_candidates(read_cat, read_off, max_occ, bin, pad, max_cand, min_votes):
     nc = int(off[-1])
     return (off, _take_array(ptrs[1], nc, ctypes.c_int64, np.int64), _take_array(ptrs[2], nc, ctypes.c_int64, np.int64),
             _take_array(ptrs[3], nc, ctypes.c_uint8, np.uint8), _take_array(ptrs[4], nc, ctypes.c_int32, np.int32))
+
+
+# ---- alignment summaries (gnx_summarize_*): CIGARs walked against their sequences on the device ----
+def _ops_array(ops):
+    """CIGAR runs as a contiguous CIGAR_DTYPE array (padding bytes zero); at least one element so that the pointer is never null"""
+    ops = np.asarray(ops)
+    out = np.zeros(max(ops.shape[0], 1), dtype=CIGAR_DTYPE)
+    if ops.shape[0]:
+        out["run_length"][:ops.shape[0]] = ops["run_length"]
+        out["op"][:ops.shape[0]] = ops["op"]
+    return out
+
+
+def _summarize(call, n, xcigar, out=None):
+    """call(out_ptr, xops_ref, xoff_ref) -> rc.  Returns (summaries[SUMMARY_DTYPE], xops or None, xoff or None)."""
+    if out is None:
+        out = np.zeros(max(n, 1), dtype=SUMMARY_DTYPE)
+    ops_p, off_p = ctypes.c_void_p(), ctypes.c_void_p()
+    check(call(out.ctypes.data, ctypes.byref(ops_p) if xcigar else None, ctypes.byref(off_p) if xcigar else None))
+    xops, xoff = _take(ops_p, off_p, n) if xcigar else (None, None)
+    return out[:n], xops, xoff
+
+
+def summarize_batch_windows(params, a_buf, a_start, a_len, b_buf, b_start, b_len, ops, ops_off, xcigar=False, out=None):
+    """gnx_summarize_batch_windows: the CIGARs ops[ops_off[p] : ops_off[p + 1]] walked against windows of two buffers."""
+    L = lib()
+    a_buf, b_buf = _u8(a_buf), _u8(b_buf)
+    a_start, a_len, b_start, b_len, ops_off = _i64(a_start), _i64(a_len), _i64(b_start), _i64(b_len), _i64(ops_off)
+    n, ops = int(a_start.shape[0]), _ops_array(ops)
+    return _summarize(lambda o, xp, xo: L.gnx_summarize_batch_windows(ctypes.byref(params), n, a_buf.ctypes.data, a_buf.shape[0], a_start.ctypes.data, a_len.ctypes.data,
+                                                                      b_buf.ctypes.data, b_buf.shape[0], b_start.ctypes.data, b_len.ctypes.data,
+                                                                      ops.ctypes.data, ops_off.ctypes.data, o, xp, xo), n, xcigar, out)
+
+
+def summarize_batch(params, alphas, betas, ops, ops_off, xcigar=False, out=None):
+    """gnx_summarize_batch on lists of uint8 arrays."""
+    L = lib()
+    a_cat, a_off = _cat(list(alphas))
+    b_cat, b_off = _cat(list(betas))
+    n, ops, ops_off = len(alphas), _ops_array(ops), _i64(ops_off)
+    return _summarize(lambda o, xp, xo: L.gnx_summarize_batch(ctypes.byref(params), n, a_cat.ctypes.data, a_off.ctypes.data, b_cat.ctypes.data, b_off.ctypes.data,
+                                                              ops.ctypes.data, ops_off.ctypes.data, o, xp, xo), n, xcigar, out)
+
+
+def summarize_batch_by_offset(params, read_cat, read_off, ref_start, ref_len, ops, ops_off, xcigar=False, out=None):
+    """gnx_summarize_batch_by_offset: reads against windows of the resident reference, in the roles of best_of_by_offset."""
+    L = lib()
+    read_cat, read_off, ref_start, ref_len, ops_off = _u8(read_cat), _i64(read_off), _i64(ref_start), _i64(ref_len), _i64(ops_off)
+    n, ops = int(ref_start.shape[0]), _ops_array(ops)
+    return _summarize(lambda o, xp, xo: L.gnx_summarize_batch_by_offset(ctypes.byref(params), n, read_cat.ctypes.data, read_off.ctypes.data, ref_start.ctypes.data, ref_len.ctypes.data,
+                                                                        ops.ctypes.data, ops_off.ctypes.data, o, xp, xo), n, xcigar, out)
 
 
 def _chunk_pairs(alphas, betas):

@@ -356,6 +356,139 @@ def MapReadPairs(params, reads, min_insert, max_insert, unpaired_penalty=0, ciga
     return _pair_result(out, len(reads), c_off, start, cigar)
 
 
+# ---- alignment summaries (gnx_summarize_*): identity, edit distance, the =/X CIGAR and the column re-score of finished alignments ----
+ColEq, ColX = _lib.GNX_XCOL_EQ, _lib.GNX_XCOL_X
+
+
+def _routes_to_ops(routes):
+    off = np.zeros(len(routes) + 1, dtype=np.int64)
+    if routes:
+        off[1:] = np.cumsum([len(r) for r in routes])
+    ops = np.zeros(int(off[-1]), dtype=_lib.CIGAR_DTYPE)
+    flat = [c for r in routes for c in r]
+    if flat:
+        ops["run_length"] = [c[0] for c in flat]
+        ops["op"] = [c[1] for c in flat]
+    return ops, off
+
+
+def _summary_dicts(out, xops, xoff):
+    res = []
+    for k in range(out.shape[0]):
+        d = {f: int(out[f][k]) for f in _lib.SUMMARY_FIELDS}
+        if xops is not None:
+            d["xcigar"] = _to_route(xops[xoff[k]:xoff[k + 1]])
+        res.append(d)
+    return res
+
+
+def Summarize(params, alphas, betas, routes, xcigar=False):
+    """What is IN finished alignments (gnx_summarize_batch): routes[k] is the CIGAR of alphas[k] against betas[k] (a list of Cigar, as
+    AlignBatch returns it).  Returns one dict per pair with gnx_aln_summary's fields -- rescore, alpha_used, beta_used, alpha_start,
+    alpha_end, n_equal, n_mismatch, ins_bases, del_bases, gap_runs, n_xops (include/gnx_align.h defines each) -- plus "xcigar", the =/X
+    form of the route (ops ColEq / ColX in place of ColM), with xcigar=True."""
+    if not routes:
+        return []
+    ops, off = _routes_to_ops(routes)
+    try:
+        out, xops, xoff = _lib.summarize_batch(params, alphas, betas, ops, off, xcigar=xcigar)
+    except _lib.GnxError as e:
+        _raise(e)
+    return _summary_dicts(out, xops, xoff)
+
+
+def SummarizeByOffset(params, reads, windows, routes, xcigar=False):
+    """Summarize against the resident reference (gnx_summarize_batch_by_offset): windows[k] = (start, len), reads[k] in the orientation
+    it was aligned in (a strand-1 winner: dna.ReverseComplement of the read).  The roles are MapBestOf's: global modes read = alpha,
+    window = beta; GNX_AFFINE_GAP_LOCAL window = alpha (the target), read = beta."""
+    if not routes:
+        return []
+    ops, off = _routes_to_ops(routes)
+    r_cat, r_off = _lib._cat(list(reads))
+    try:
+        out, xops, xoff = _lib.summarize_batch_by_offset(params, r_cat, r_off, [w[0] for w in windows], [w[1] for w in windows], ops, off, xcigar=xcigar)
+    except _lib.GnxError as e:
+        _raise(e)
+    return _summary_dicts(out, xops, xoff)
+
+
+def FormatXCigar(route):
+    """An extended route as text, e.g. "12=1X30=2D5=" ("*" for an empty one)"""
+    runes = {ColM: "M", ColI: "I", ColD: "D", ColEq: "=", ColX: "X"}
+    return "".join("%d%s" % (c[0], runes[c[1]]) for c in route) or "*"
+
+
+def _report(params, reads, placed, extra):
+    """placed[r] = (best, strand, score, window (start, len) or None, route): one SummarizeByOffset call on the reads that have a winner"""
+    idx = [r for r, p in enumerate(placed) if p[0] >= 0]
+    oriented = [dna.ReverseComplement(np.array(reads[r], dtype=np.uint8)) if placed[r][1] else reads[r] for r in idx]  # (it works in place: on a copy)
+    sums = SummarizeByOffset(params, oriented, [placed[r][3] for r in idx], [placed[r][4] for r in idx], xcigar=True)
+    at = dict(zip(idx, sums))
+    rep = []
+    for r, (best, strand, score, win, route) in enumerate(placed):
+        d = {"best": best, "strand": strand, "score": score, "window_start": win[0] if win else None, "pos": None, "end": None, "route": route, "xcigar": []}
+        if r in at:
+            d.update(at[r])
+            d["pos"], d["end"] = win[0] + d["alpha_start"], win[0] + d["alpha_end"]
+        else:
+            d.update({f: 0 for f in _lib.SUMMARY_FIELDS})
+        d.update(extra[r])
+        rep.append(d)
+    return rep
+
+
+def _local_only(params, name):
+    if params.mode != _lib.GNX_AFFINE_GAP_LOCAL:
+        raise ValueError("%s: the mode must be GNX_AFFINE_GAP_LOCAL (positions are defined nowhere else)" % name)
+
+
+def MapReadsReport(params, reads, **vote_opts):
+    """MapReads (GNX_AFFINE_GAP_LOCAL) plus what is in each placement: the seed and best-of calls run unchanged, then ONE
+    SummarizeByOffset call on the winners (strand-1 winners as their reverse complements).  Returns one dict per read: best, strand,
+    score, window_start, pos (0-based reference position of the first aligned base = window_start + alpha_start), end, route, xcigar
+    and the summary fields; a read without a candidate has best -1, pos None and zero counts."""
+    _local_only(params, "MapReadsReport")
+    if not reads:
+        return []
+    r_cat, r_off = _lib._cat(list(reads))
+    try:
+        c_off, start, ln, strand, _ = _lib.seed_candidates(r_cat, r_off, **_vote_opts(vote_opts))
+        best, scores, _, _, ops, off = _lib.best_of_by_offset(params, r_cat, r_off, c_off, start, ln, strand, cigar=True)
+    except _lib.GnxError as e:
+        _raise(e)
+    placed = []
+    for r in range(len(reads)):
+        b = int(best[r])
+        c = int(c_off[r]) + b
+        placed.append((b, int(strand[c]) if b >= 0 else 0, int(scores[r]), (int(start[c]), int(ln[c])) if b >= 0 else None, _to_route(ops[off[r]:off[r + 1]])))
+    return _report(params, reads, placed, [{} for _ in reads])
+
+
+def MapReadPairsReport(params, reads, min_insert, max_insert, unpaired_penalty=0, **vote_opts):
+    """MapReadPairs plus what is in each placement (see MapReadsReport); every dict also has second_score (None without another
+    candidate) and its pair's proper / tlen."""
+    _local_only(params, "MapReadPairsReport")
+    if len(reads) % 2:
+        raise ValueError("MapReadPairsReport: reads come in mate pairs (an even number)")
+    if not reads:
+        return []
+    r_cat, r_off = _lib._cat(list(reads))
+    try:
+        c_off, start, ln, strand, _ = _lib.seed_candidates(r_cat, r_off, **_vote_opts(vote_opts))
+        out = _lib.best_pair_by_offset(params, _lib.pair_opts(min_insert, max_insert, unpaired_penalty), r_cat, r_off, c_off, start, ln, strand, cigar=True)
+    except _lib.GnxError as e:
+        _raise(e)
+    placed, extra = [], []
+    for r in range(len(reads)):
+        b = int(out["best"][r])
+        c = int(c_off[r]) + b
+        placed.append((b, int(strand[c]) if b >= 0 else 0, int(out["score"][r]), (int(start[c]), int(ln[c])) if b >= 0 else None,
+                       _to_route(out["ops"][out["off"][r]:out["off"][r + 1]])))
+        second = int(out["second_score"][r])
+        extra.append({"second_score": second if second != np.iinfo(np.int64).min else None, "proper": bool(out["proper"][r // 2]), "tlen": int(out["tlen"][r // 2])})
+    return _report(params, reads, placed, extra)
+
+
 def AffineGapChunk(alpha, beta, scores, gapOpen, gapExtend, chunkSize):
     """align.AffineGapChunk (/root/reference/align/affineGap_highMem.go:227-268)."""
     try:

@@ -55,6 +55,7 @@
 #include "n1_sweep.hip.h"
 #include "span_origin.hip.h"
 #include "ref_seeds.hip.h"
+#include "aln_summary.hip.h"
 
 namespace {
 
@@ -142,6 +143,7 @@ struct Ctx {
     DevBuf ss_len, res_end, gat_end; // gnx_locate_*: target lengths for the end read off a CIGAR, the ends of a host job, their gather on device 0
     DevBuf ss_plans, ss_rowbuf, ss_prog, ss_err, ss_off; // the score-only sweep (score_sweep.hip.h): plans, hand-over rows, progress / claim words, error flags; offsets of a dropped CIGAR
     DevBuf sd_keys, sd_locs, sd_nodes, sd_node_off, sd_word_off, sd_words, sd_tmp[8];
+    DevBuf sm[14]; // gnx_summarize_* (gnx_host.hip.h, SM_*): sequences, window tables, CIGAR runs and offsets, the score matrix, summaries, the extended CIGAR's counts / offsets / runs
     DevBuf bo[19]; // gnx_best_of_* / gnx_best_pair_* (gnx_host.hip.h, BO_*): reads + reverse complements, candidate tables and scores, per-read winners, the winners' tables
     int64_t sd_n = -1, sd_nodes_n = 0; int sd_seed_len = 0;
     // k-mer index of the resident reference (gnx_reference_index_build; context 0 only) and the scratch of gnx_seed_candidates (RS_*)
@@ -2847,6 +2849,7 @@ void gnx_shutdown(void) {
                           &c.sd_tmp[0], &c.sd_tmp[1], &c.sd_tmp[2], &c.sd_tmp[3], &c.sd_tmp[4], &c.sd_tmp[5], &c.sd_tmp[6], &c.sd_tmp[7]};
         for (DevBuf *b : bufs) b->release();
         for (DevBuf &b : c.bo) b.release();
+        for (DevBuf &b : c.sm) b.release();
         drop_reference_index(c);
         PinBuf *pins[] = {&c.h_plans, &c.st_a[0], &c.st_a[1], &c.st_as[0], &c.st_as[1], &c.st_b[0], &c.st_b[1], &c.st_bs[0], &c.st_bs[1]};
         for (PinBuf *b : pins) b->release();
@@ -3068,6 +3071,38 @@ int gnx_best_pair_windows(const gnx_params *p, const gnx_pair_opts *o, int64_t n
     const PairOut pr{o, out_target_start, out_second_score, out_proper, out_tlen, out_cand_start, out_cand_end};
     return run_best_of(p, n_reads, read_cat, read_off, false, target_buf, target_buf_len, cand_off, cand_start, cand_len, cand_strand, out_best, out_score, out_target_end, out_cand_score,
                        out_ops, out_ops_off, &pr);
+}
+
+/* ---- alignment summaries: CIGARs walked against their sequences on the device (gnx_align.h) ---- */
+int gnx_summarize_batch_windows(const gnx_params *p, int64_t n_pairs,
+                                const uint8_t *alpha_buf, int64_t alpha_buf_len, const int64_t *alpha_start, const int64_t *alpha_len,
+                                const uint8_t *beta_buf, int64_t beta_buf_len, const int64_t *beta_start, const int64_t *beta_len,
+                                const gnx_cigar *ops, const int64_t *ops_off, gnx_aln_summary *out, gnx_cigar **out_xops, int64_t **out_xops_off) {
+    std::lock_guard<std::mutex> api(g_api_mu);
+    g_err[0] = 0;
+    const SumSide sa{alpha_buf, alpha_buf_len, alpha_start, alpha_len, false}, sb{beta_buf, beta_buf_len, beta_start, beta_len, false};
+    return run_summarize(p, n_pairs, sa, sb, ops, ops_off, out, out_xops, out_xops_off);
+}
+
+int gnx_summarize_batch(const gnx_params *p, int64_t n_pairs, const uint8_t *alpha_cat, const int64_t *alpha_off, const uint8_t *beta_cat, const int64_t *beta_off,
+                        const gnx_cigar *ops, const int64_t *ops_off, gnx_aln_summary *out, gnx_cigar **out_xops, int64_t **out_xops_off) {
+    if (n_pairs < 0 || !alpha_off || !beta_off) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    std::vector<int64_t> al((size_t)n_pairs + 1), bl((size_t)n_pairs + 1);
+    for (int64_t q = 0; q < n_pairs; q++) { al[(size_t)q] = alpha_off[q + 1] - alpha_off[q]; bl[(size_t)q] = beta_off[q + 1] - beta_off[q]; }
+    return gnx_summarize_batch_windows(p, n_pairs, alpha_cat, alpha_off[n_pairs], alpha_off, al.data(), beta_cat, beta_off[n_pairs], beta_off, bl.data(),
+                                       ops, ops_off, out, out_xops, out_xops_off);
+}
+
+int gnx_summarize_batch_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *read_cat, const int64_t *read_off, const int64_t *ref_start, const int64_t *ref_len,
+                                  const gnx_cigar *ops, const int64_t *ops_off, gnx_aln_summary *out, gnx_cigar **out_xops, int64_t **out_xops_off) {
+    std::lock_guard<std::mutex> api(g_api_mu);
+    g_err[0] = 0;
+    if (!p || n_pairs < 0 || !read_off || !ref_start || !ref_len) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    std::vector<int64_t> rl((size_t)n_pairs + 1);
+    for (int64_t q = 0; q < n_pairs; q++) rl[(size_t)q] = read_off[q + 1] - read_off[q];
+    const SumSide reads{read_cat, read_off[n_pairs], read_off, rl.data(), false}, wins{nullptr, 0, ref_start, ref_len, true};
+    const bool local = p->mode == GNX_AFFINE_GAP_LOCAL; // the roles of gnx_best_of_by_offset: the window is the target (alpha) of the mapping mode, beta everywhere else
+    return run_summarize(p, n_pairs, local ? wins : reads, local ? reads : wins, ops, ops_off, out, out_xops, out_xops_off);
 }
 
 int gnx_score_batch_device(const gnx_params *p, int64_t n_pairs,

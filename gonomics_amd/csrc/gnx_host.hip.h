@@ -1075,4 +1075,187 @@ int run_best_of(const gnx_params *prm, int64_t n_reads, const uint8_t *read_cat,
     return GNX_OK;
 }
 
+// ---- gnx_summarize_*: CIGARs walked against their sequences (aln_summary.hip.h; contract: gnx_align.h) ----------------------------
+// One context (context 0).  Everything the host can check is checked before the device is touched: the tables, the windows, and
+// every CIGAR run (op, run length, consumption).  Sequences, tables and runs go up once; the summary kernel is launched per
+// sub-batch of GNX_HOST_SUB pairs (GNX_SUMMARY_SUB=<pairs> overrides the cut), and with an extended CIGAR asked for the scan
+// family chains the sub-batches' offsets through its carry and the WRITE instantiation follows.  Nothing is written to the
+// caller's outputs before every kernel has succeeded.
+enum { SM_A, SM_B, SM_AS, SM_AL, SM_BS, SM_BL, SM_OPS, SM_OFF, SM_SC, SM_OUT, SM_NX, SM_XOFF, SM_XOPS, SM_MISC, SM_COUNT };
+static_assert(SM_COUNT == sizeof(Ctx::sm) / sizeof(DevBuf), "Ctx::sm holds one buffer per SM_* index");
+struct SumSide { // one sequence per pair: a window (start, len) of buf, or of the resident reference
+    const uint8_t *buf;
+    int64_t buf_len;
+    const int64_t *start, *len;
+    bool resident;
+};
+int run_summarize(const gnx_params *prm, int64_t n_pairs, const SumSide &sa, const SumSide &sb, const gnx_cigar *ops, const int64_t *ops_off,
+                  gnx_aln_summary *out, gnx_cigar **out_xops, int64_t **out_xops_off) {
+    const auto t_entry = std::chrono::steady_clock::now();
+    // ---- argument checks: everything that needs no device ----
+    if (!prm || n_pairs < 0 || !ops_off || !out || !sa.start || !sa.len || !sb.start || !sb.len || sa.buf_len < 0 || sb.buf_len < 0) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if ((out_xops == nullptr) != (out_xops_off == nullptr)) { set_err("out_xops and out_xops_off must be given together%s", ""); return GNX_EINVAL; }
+    if (prm->mode < GNX_AFFINE_GAP || prm->mode > GNX_CONST_GAP_HIGHMEM) { set_err("unknown mode %s%lld", "", (long long)prm->mode); return GNX_EINVAL; }
+    const bool local = prm->mode == GNX_AFFINE_GAP_LOCAL, affine = local || prm->mode == GNX_AFFINE_GAP || prm->mode == GNX_AFFINE_GAP_HIGHMEM, xc = out_xops != nullptr;
+    if (ops_off[0] != 0) { set_err("ops_off must start at 0%s", ""); return GNX_EINVAL; }
+    for (int64_t q = 0; q < n_pairs; q++)
+        if (ops_off[q + 1] < ops_off[q]) { set_err("decreasing ops_off at pair %s%lld", "", (long long)q); return GNX_EINVAL; }
+    const int64_t n_runs = ops_off[n_pairs];
+    if (n_runs > 0 && !ops) { set_err("null CIGAR array%s", ""); return GNX_EINVAL; }
+    for (const SumSide *s : {&sa, &sb})
+        for (int64_t q = 0; q < n_pairs; q++) {
+            if (s->start[q] < 0 || s->len[q] < 0 || (!s->resident && s->len[q] > s->buf_len - s->start[q])) { set_err("window out of bounds at pair %s%lld", "", (long long)q); return GNX_EINVAL; }
+            if (!s->resident && s->len[q] > 0 && !s->buf) { set_err("null sequence buffer%s", ""); return GNX_EINVAL; }
+            if (s->len[q] >= ((int64_t)1 << 30)) { set_err("a sequence of 2^30 bases or more at pair %s%lld (the limit of the align entries)", "", (long long)q); return GNX_EINVAL; }
+        }
+    int64_t cells = 0;
+    for (int64_t q = 0; q < n_pairs; q++) {
+        int64_t fa = sa.len[q], fb = sb.len[q]; // what is left of either sequence
+        for (int64_t x = ops_off[q]; x < ops_off[q + 1]; x++) {
+            const int64_t len = ops[x].run_length;
+            const int op = ops[x].op;
+            if (op > GNX_COL_D) { set_err("unknown CIGAR op at run %s%lld", "", (long long)x); return GNX_EINVAL; }
+            if (len < 0) { set_err("negative run length at run %s%lld", "", (long long)x); return GNX_EINVAL; }
+            if ((op != GNX_COL_I && len > fa) || (op != GNX_COL_D && len > fb)) { set_err("the CIGAR of pair %s%lld consumes more than its sequences hold", "", (long long)q); return GNX_EINVAL; }
+            if (op != GNX_COL_I) fa -= len;
+            if (op != GNX_COL_D) fb -= len;
+            cells += len;
+        }
+    }
+    Ctx &c = ctx_at(0);
+    CtxScope scope(c);
+    int rc;
+    if ((rc = ensure_init())) return rc;
+    g_transport = 0; g_bcast_ms = 0;
+    if (sa.resident || sb.resident) {
+        if (c.ref_len < 0) { set_err("no resident reference: call gnx_set_reference first%s", ""); return GNX_EINVAL; }
+        const SumSide &s = sa.resident ? sa : sb;
+        for (int64_t q = 0; q < n_pairs; q++)
+            if (s.len[q] > c.ref_len - s.start[q]) { set_err("window out of bounds at pair %s%lld", "", (long long)q); return GNX_EINVAL; }
+    }
+    hipStream_t st = c.own_stream;
+    gnx_cigar *xops = nullptr;
+    int64_t *xoff = nullptr;
+    if (xc) {
+        xoff = (int64_t *)g_pool.get((size_t)(n_pairs + 1) * 8);
+        if (!xoff) { set_err("pinned host allocation failed%s", ""); return GNX_ENOMEM; }
+        xoff[0] = 0;
+    }
+    auto fail = [&](int r) { if (xoff) g_pool.put(xoff); if (xops) g_pool.put(xops); return r; };
+    gnx_timing t = {};
+    t.fast_path = 12; t.cells = cells; t.n_contexts = 1;
+    int64_t n_x = 0;
+    std::vector<gnx_aln_summary> h_out((size_t)n_pairs);
+    if (n_pairs > 0) {
+        int64_t sub = 131072;
+        if (const char *e = getenv("GNX_HOST_SUB")) sub = (std::max<int64_t>(atoll(e), 8) + 7) & ~(int64_t)7;
+        if (const char *e = getenv("GNX_SUMMARY_SUB")) sub = std::max<int64_t>(atoll(e), 1);
+        int cut = 64;
+        if (const char *e = getenv("GNX_SUMMARY_FORM")) cut = e[0] == '0' ? 1 : e[0] == '1' ? 0x7fffffff : 64;
+        DevBuf *sm = c.sm;
+        const size_t np = (size_t)n_pairs;
+        if ((rc = sm[SM_AS].ensure(np * 8)) || (rc = sm[SM_AL].ensure(np * 8)) || (rc = sm[SM_BS].ensure(np * 8)) || (rc = sm[SM_BL].ensure(np * 8)) ||
+            (rc = sm[SM_OPS].ensure((size_t)std::max<int64_t>(n_runs, 1) * sizeof(gnx_cigar))) || (rc = sm[SM_OFF].ensure((np + 1) * 8)) || (rc = sm[SM_SC].ensure(25 * 8)) ||
+            (rc = sm[SM_OUT].ensure(np * sizeof(gnx_aln_summary))) || (rc = sm[SM_NX].ensure(np * 8)) || (rc = sm[SM_XOFF].ensure((np + 1) * 8)) || (rc = sm[SM_MISC].ensure(64)) ||
+            (!sa.resident && (rc = sm[SM_A].ensure((size_t)sa.buf_len + 16))) || (!sb.resident && (rc = sm[SM_B].ensure((size_t)sb.buf_len + 16)))) return fail(rc);
+        auto run = [&]() -> int {
+            SumArgs a;
+            memset(&a, 0, sizeof(a));
+            for (int side = 0; side < 2; side++) {
+                const SumSide &s = side ? sb : sa;
+                KParams &k = a.kp;
+                if (s.resident) { k.b2 = (const unsigned *)c.ref.p; k.bflag = (const unsigned long long *)c.ref_flag.p; k.brank = (const unsigned *)c.ref_rank.p; k.bexc = (const unsigned long long *)c.ref_exc.p; }
+                else if (s.buf_len > 0) HIPCHK(hipMemcpyAsync(sm[side ? SM_B : SM_A].p, s.buf, (size_t)s.buf_len, hipMemcpyHostToDevice, st));
+                HIPCHK(hipMemcpyAsync(sm[side ? SM_BS : SM_AS].p, s.start, np * 8, hipMemcpyHostToDevice, st));
+                HIPCHK(hipMemcpyAsync(sm[side ? SM_BL : SM_AL].p, s.len, np * 8, hipMemcpyHostToDevice, st));
+            }
+            if (n_runs > 0) HIPCHK(hipMemcpyAsync(sm[SM_OPS].p, ops, (size_t)n_runs * sizeof(gnx_cigar), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(sm[SM_OFF].p, ops_off, (np + 1) * 8, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(sm[SM_SC].p, prm->scores, 25 * 8, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemsetAsync(sm[SM_MISC].p, 0, 64, st)); // [0] the error flags (int), [8 ..) the scan's carry (int64)
+            a.a_buf = sa.resident ? nullptr : (const uint8_t *)sm[SM_A].p; a.b_buf = sb.resident ? nullptr : (const uint8_t *)sm[SM_B].p;
+            a.ops = (const gnx_cigar *)sm[SM_OPS].p; a.scores = (const int64_t *)sm[SM_SC].p;
+            a.gap_open = prm->gap_open; a.gap_extend = prm->gap_extend; a.cut = cut; a.affine = affine; a.local = local;
+            a.err = (int *)sm[SM_MISC].p; a.xops = nullptr;
+            int64_t *d_carry = (int64_t *)sm[SM_MISC].p + 1;
+            const int pk = sa.resident ? 1 : sb.resident ? 2 : 0; // which side the kernels read packed
+            auto launch = [&](bool write) -> int {
+                for (int64_t b = 0; b < n_pairs; b += sub) {
+                    const int64_t cnt = std::min(sub, n_pairs - b);
+                    SumArgs s = a;
+                    s.a_start = (const int64_t *)sm[SM_AS].p + b; s.a_len = (const int64_t *)sm[SM_AL].p + b; s.b_start = (const int64_t *)sm[SM_BS].p + b; s.b_len = (const int64_t *)sm[SM_BL].p + b;
+                    s.ops_off = (const int64_t *)sm[SM_OFF].p + b; s.out = (gnx_aln_summary *)sm[SM_OUT].p + b; s.nx = (int64_t *)sm[SM_NX].p + b; s.xoff = (const int64_t *)sm[SM_XOFF].p + b;
+                    s.n_pairs = cnt;
+                    const dim3 grid((unsigned)std::min<int64_t>((cnt + 3) / 4, 1 << 20));
+                    // the base check: one workgroup per pair, or several that share a pair when the launch is a few long pairs
+                    int64_t longest = 0;
+                    for (int64_t q = b; q < b + cnt; q++) longest = std::max(longest, std::max(sa.len[q], sb.len[q]));
+                    const int chunks = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(longest / 8192, 256), ((int64_t)1 << 16) / cnt));
+                    const dim3 bgrid((unsigned)std::min<int64_t>(cnt, 1 << 20), (unsigned)chunks);
+                    s.slice = (int)((((longest + chunks - 1) / chunks) + 255) & ~(int64_t)255) + 256;
+                    if (write) {
+                        if (pk == 1) hipLaunchKernelGGL((aln_summary_kernel<true, 1>), grid, dim3(256), 0, st, s);
+                        else if (pk == 2) hipLaunchKernelGGL((aln_summary_kernel<true, 2>), grid, dim3(256), 0, st, s);
+                        else hipLaunchKernelGGL((aln_summary_kernel<true, 0>), grid, dim3(256), 0, st, s);
+                    } else if (pk == 1) {
+                        hipLaunchKernelGGL(aln_summary_bases_kernel<1>, bgrid, dim3(256), 0, st, s);
+                        hipLaunchKernelGGL((aln_summary_kernel<false, 1>), grid, dim3(256), 0, st, s);
+                    } else if (pk == 2) {
+                        hipLaunchKernelGGL(aln_summary_bases_kernel<2>, bgrid, dim3(256), 0, st, s);
+                        hipLaunchKernelGGL((aln_summary_kernel<false, 2>), grid, dim3(256), 0, st, s);
+                    } else {
+                        hipLaunchKernelGGL(aln_summary_bases_kernel<0>, bgrid, dim3(256), 0, st, s);
+                        hipLaunchKernelGGL((aln_summary_kernel<false, 0>), grid, dim3(256), 0, st, s);
+                    }
+                    HIPCHK(hipGetLastError());
+                    int r;
+                    if (!write && xc && (r = launch_scan(s.nx, (int)cnt, (int64_t *)sm[SM_XOFF].p + b, d_carry, st))) return r;
+                    t.n_launches++;
+                }
+                return GNX_OK;
+            };
+            int r;
+            HIPCHK(hipEventRecord(c.ev[0], st));
+            if ((r = launch(false))) return r;
+            HIPCHK(hipEventRecord(c.ev[1], st));
+            int ef = 0;
+            HIPCHK(hipMemcpyAsync(&ef, sm[SM_MISC].p, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(h_out.data(), sm[SM_OUT].p, np * sizeof(gnx_aln_summary), hipMemcpyDeviceToHost, st));
+            if (xc) HIPCHK(hipMemcpyAsync(xoff, sm[SM_XOFF].p, (np + 1) * 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st)); // (also: the sources are pageable memory of the caller -- no return while a copy may still read them)
+            if (ef & 1) { set_err("a base >= 5 was found: the reference would panic (index out of range)%s", ""); return GNX_EBASE; }
+            float ms = 0;
+            HIPCHK(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+            t.fill_ms = ms;
+            if (xc) {
+                n_x = xoff[n_pairs];
+                xops = (gnx_cigar *)g_pool.get((size_t)std::max<int64_t>(n_x, 1) * sizeof(gnx_cigar));
+                if (!xops) { set_err("pinned host allocation failed%s", ""); return GNX_ENOMEM; }
+                if (n_x > 0) {
+                    if ((r = sm[SM_XOPS].ensure((size_t)n_x * sizeof(gnx_cigar)))) return r;
+                    a.xops = (gnx_cigar *)sm[SM_XOPS].p;
+                    HIPCHK(hipEventRecord(c.ev[2], st));
+                    if ((r = launch(true))) return r;
+                    HIPCHK(hipEventRecord(c.ev[3], st));
+                    HIPCHK(hipMemcpyAsync(xops, sm[SM_XOPS].p, (size_t)n_x * sizeof(gnx_cigar), hipMemcpyDeviceToHost, st));
+                    HIPCHK(hipStreamSynchronize(st));
+                    HIPCHK(hipEventElapsedTime(&ms, c.ev[2], c.ev[3]));
+                    t.fill_ms += ms;
+                }
+            }
+            return GNX_OK;
+        };
+        if ((rc = run())) { (void)hipStreamSynchronize(st); return fail(rc); }
+    } else if (xc) {
+        xops = (gnx_cigar *)g_pool.get(sizeof(gnx_cigar));
+        if (!xops) { set_err("pinned host allocation failed%s", ""); return fail(GNX_ENOMEM); }
+    }
+    if (n_pairs > 0) memcpy(out, h_out.data(), (size_t)n_pairs * sizeof(gnx_aln_summary));
+    if (xc) { *out_xops = xops; *out_xops_off = xoff; }
+    t.dominant_ms = t.total_ms = t.fill_ms; t.dominant_launches = t.n_launches;
+    t.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count();
+    c.timing = t;
+    return GNX_OK;
+}
+
 } // namespace

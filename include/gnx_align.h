@@ -105,6 +105,7 @@ typedef struct gnx_timing {
                             span_origin.hip.h): fill_ms and total_ms cover both stages, dominant_ms is the sweep's.
                             11: gnx_seed_candidates ran (ref_seeds.hip.h): fill_ms = lookup + vote kernels, dominant_ms = the vote kernels, cells = seed
                             hits that voted, n_launches = vote sub-batches.
+                            12: gnx_summarize_* ran (aln_summary.hip.h): fill_ms = dominant_ms = the summary kernels, cells = columns walked.
                             Multi-context score calls report the maximum over contexts. */
     int32_t _pad;
     /* host-buffer entry points only (wall clock inside the library): */
@@ -419,6 +420,69 @@ typedef struct gnx_seed_vote_opts {
  * form; GNX_SEED_SUB=<hits> sets the hits per vote launch.  gnx_get_timing afterwards: fast_path 11. */
 int gnx_seed_candidates(const gnx_seed_vote_opts *o, int64_t n_reads, const uint8_t *read_cat, const int64_t *read_off,
                         int64_t **out_cand_off, int64_t **out_cand_start, int64_t **out_cand_len, uint8_t **out_cand_strand, int32_t **out_cand_votes);
+
+/* ---- alignment summaries: what is IN a finished alignment (an extension; the reference's notion is scoreAffineAln, ------------------- */
+/* align/affineGap_highMem.go:355-385: a score computed from the columns of an alignment) */
+#define GNX_XCOL_EQ 3   /* extended CIGAR only: an M column whose two bases are the same byte  ('=') */
+#define GNX_XCOL_X  4   /* extended CIGAR only: an M column whose two bases differ             ('X') */
+typedef struct gnx_aln_summary {      /* 12 x int64 = 96 bytes */
+    int64_t rescore;
+    int64_t alpha_used, beta_used;
+    int64_t alpha_start, alpha_end;
+    int64_t n_equal, n_mismatch;
+    int64_t ins_bases, del_bases;
+    int64_t gap_runs;
+    int64_t n_xops;
+    int64_t _reserved;                /* 0 */
+} gnx_aln_summary;
+/* Walk the CIGARs of a batch against their sequences on the device: identities and substitutions, edit distance, the column re-score,
+ * the =/X form of the CIGAR.  Sequences as in gnx_align_batch / _windows; ops / ops_off[n_pairs + 1] in the layout the align entries
+ * return.  out[n_pairs] is required.  out_xops / out_xops_off are given together or both NULL (no extended CIGAR is produced); when
+ * given they are malloc'd (gnx_free) in the layout of out_ops / out_ops_off.
+ * _by_offset has the roles of gnx_best_of_by_offset, whose CIGARs it exists for: the four global modes alpha = the read, beta = the
+ * window of the resident reference; GNX_AFFINE_GAP_LOCAL alpha (target) = the window, beta (query) = the read.  The caller passes each
+ * read in the orientation it was aligned in (a strand-1 winner as its reverse complement).
+ * Everything is a function of the pair's COLUMN SEQUENCE: the CIGAR expanded run by run into M / I / D columns.  Runs of length 0
+ * contribute nothing, so adjacent runs of one op are one run.  The sequence is anchored at (0, 0): an M column consumes alpha[i] and
+ * beta[j], I consumes beta[j] only, D alpha[i] only (align/view.go:47-55).
+ *   alpha_used, beta_used   bases consumed; may be fewer than the sequences hold (quirk Q2 produces such CIGARs; a caller who wants
+ *                           one anchored at the end passes shifted windows).
+ *   n_equal / n_mismatch    M columns with alpha[i] == beta[j] as bytes (N against N is equal) / the others.
+ *   charged columns         GNX_AFFINE_GAP_LOCAL: the leading maximal D run and the trailing maximal D run of the column sequence are
+ *                           free (freeEndGaps, affineGap_highMem.go:188-210); a sequence that is one D run is free as a whole.  In
+ *                           every other mode nothing is free.
+ *   ins_bases / del_bases   charged I / D columns.
+ *   gap_runs                maximal runs of equal gap op among the charged columns (an I run directly followed by a D run: two).
+ *   alpha_start, alpha_end  local mode: the length of the free leading run, and alpha_used minus the free trailing run (one free run
+ *                           as a whole: 0 / 0, as gnx_locate_span_* defines it); other modes: 0 and alpha_used.
+ *   rescore                 the sum of scores[alpha[i] * 5 + beta[j]] over the M columns, plus -- affine modes (0, 2, 3) --
+ *                           gap_open * gap_runs + gap_extend * (ins_bases + del_bases) (scoreAffineAln's rule), or -- constant-gap
+ *                           modes (1, 4) -- gap_open * (ins_bases + del_bases).  checkersize_* are ignored.
+ *   extended CIGAR          the maximal runs of the column sequence with every M column retyped GNX_XCOL_EQ or GNX_XCOL_X; I = 1 and
+ *                           D = 2 are kept, free D runs included.  n_xops = the number of those runs, also without out_xops.
+ * Return codes, all before any output is written: GNX_EINVAL for a null required pointer, a negative count, an unknown mode, ops_off
+ * not starting at 0 or decreasing, an op > 2, a negative run length, a CIGAR that consumes more than its alpha or beta holds, exactly
+ * one of out_xops / out_xops_off NULL, a window outside its buffer or the reference, a sequence of 2^30 bases or more (the limit of the
+ * align entries); GNX_EBASE exactly where the align twin reports it
+ * for the same sequences (a byte >= 5 anywhere in either); GNX_EDEVICE without a device, after the argument checks (no CPU fallback);
+ * n_pairs == 0: GNX_OK; never GNX_ERANGE.
+ * Runs on context 0.  aln_summary_kernel (aln_summary.hip.h): one wave per pair, the CIGAR in blocks of 64 runs, long M runs 64 columns
+ * per step, the packed reference read in place.  Calls are cut into launches of GNX_HOST_SUB pairs.  Switches, read per call:
+ * GNX_SUMMARY_SUB=<pairs> overrides that cut; GNX_SUMMARY_FORM=0 / 1 walks every M run a lane per column / a lane per run (same results).
+ * gnx_get_timing afterwards: fast_path 12. */
+int gnx_summarize_batch(const gnx_params *p, int64_t n_pairs,
+                        const uint8_t *alpha_cat, const int64_t *alpha_off, const uint8_t *beta_cat, const int64_t *beta_off,
+                        const gnx_cigar *ops, const int64_t *ops_off,
+                        gnx_aln_summary *out, gnx_cigar **out_xops, int64_t **out_xops_off);
+int gnx_summarize_batch_windows(const gnx_params *p, int64_t n_pairs,
+                                const uint8_t *alpha_buf, int64_t alpha_buf_len, const int64_t *alpha_start, const int64_t *alpha_len,
+                                const uint8_t *beta_buf, int64_t beta_buf_len, const int64_t *beta_start, const int64_t *beta_len,
+                                const gnx_cigar *ops, const int64_t *ops_off,
+                                gnx_aln_summary *out, gnx_cigar **out_xops, int64_t **out_xops_off);
+int gnx_summarize_batch_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *read_cat, const int64_t *read_off,
+                                  const int64_t *ref_start, const int64_t *ref_len,
+                                  const gnx_cigar *ops, const int64_t *ops_off,
+                                  gnx_aln_summary *out, gnx_cigar **out_xops, int64_t **out_xops_off);
 
 int gnx_get_timing(gnx_timing *out);
 /* Diagnostics (tests only; nothing in the reference corresponds to it): launch n_workgroups workgroups that each hold one CU's whole

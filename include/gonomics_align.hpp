@@ -390,6 +390,62 @@ inline ReadPairs MapReadPairs(const ScoreMatrix &scores, int64_t gapOpen, int64_
     return MapBestPair(scores, gapOpen, gapExtend, reads, cands, o, cigar);
 }
 
+// ---- alignment summaries (gnx_summarize_*, an extension): what is IN finished alignments -- identities, substitutions, gap bases and
+// runs, the column re-score, the =/X form of the route (ops ColEq / ColX in place of ColM; only with xcigar).  gnx_align.h defines each field.
+constexpr ColType ColEq = GNX_XCOL_EQ, ColX = GNX_XCOL_X;
+struct Summary { gnx_aln_summary S{}; std::vector<Cigar> XCigar; };
+namespace detail {
+inline void flatten(const std::vector<std::vector<dna::Base>> &seqs, std::vector<dna::Base> &cat, std::vector<int64_t> &off) {
+    off.assign(seqs.size() + 1, 0);
+    for (size_t k = 0; k < seqs.size(); k++) { cat.insert(cat.end(), seqs[k].begin(), seqs[k].end()); off[k + 1] = (int64_t)cat.size(); }
+    cat.push_back(0); // (data() of an empty vector may be null)
+}
+// by_offset: betas is unused, windows = (start, len) of the resident reference
+inline std::vector<Summary> summarize(const gnx_params &p, const std::vector<std::vector<dna::Base>> &alphas, const std::vector<std::vector<dna::Base>> *betas,
+                                      const std::vector<std::pair<int64_t, int64_t>> *windows, const std::vector<std::vector<Cigar>> &routes, bool xcigar) {
+    const int64_t n = (int64_t)routes.size();
+    std::vector<dna::Base> acat, bcat;
+    std::vector<int64_t> aoff, boff, ooff((size_t)n + 1, 0), ws, wl;
+    std::vector<gnx_cigar> ops;
+    flatten(alphas, acat, aoff);
+    if (betas) flatten(*betas, bcat, boff);
+    else for (const auto &w : *windows) { ws.push_back(w.first); wl.push_back(w.second); }
+    ws.push_back(0); wl.push_back(0);
+    for (int64_t k = 0; k < n; k++) {
+        for (const Cigar &c : routes[(size_t)k]) { gnx_cigar g{}; g.run_length = c.RunLength; g.op = c.Op; ops.push_back(g); }
+        ooff[(size_t)k + 1] = (int64_t)ops.size();
+    }
+    ops.push_back(gnx_cigar{});
+    std::vector<gnx_aln_summary> out((size_t)n + 1);
+    gnx_cigar *xops = nullptr;
+    int64_t *xoff = nullptr;
+    const int rc = betas ? gnx_summarize_batch(&p, n, acat.data(), aoff.data(), bcat.data(), boff.data(), ops.data(), ooff.data(), out.data(), xcigar ? &xops : nullptr, xcigar ? &xoff : nullptr)
+                         : gnx_summarize_batch_by_offset(&p, n, acat.data(), aoff.data(), ws.data(), wl.data(), ops.data(), ooff.data(), out.data(), xcigar ? &xops : nullptr, xcigar ? &xoff : nullptr);
+    if (rc) raise(rc);
+    std::vector<Summary> res((size_t)n);
+    for (int64_t k = 0; k < n; k++) {
+        res[(size_t)k].S = out[(size_t)k];
+        if (xcigar) for (int64_t x = xoff[k]; x < xoff[k + 1]; x++) res[(size_t)k].XCigar.push_back(Cigar{xops[x].run_length, xops[x].op});
+    }
+    if (xcigar) { gnx_free(xops); gnx_free(xoff); }
+    return res;
+}
+} // namespace detail
+inline std::vector<Summary> Summarize(int mode, const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, const std::vector<std::vector<dna::Base>> &alphas,
+                                      const std::vector<std::vector<dna::Base>> &betas, const std::vector<std::vector<Cigar>> &routes, bool xcigar = false) {
+    return detail::summarize(detail::params(mode, scores, gapOpen, gapExtend, 10000, 10000), alphas, &betas, nullptr, routes, xcigar);
+}
+// reads against windows (start, len) of the resident reference, in MapBestOf's roles; a strand-1 winner's read goes in reverse-complemented
+inline std::vector<Summary> SummarizeByOffset(int mode, const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, const std::vector<std::vector<dna::Base>> &reads,
+                                              const std::vector<std::pair<int64_t, int64_t>> &windows, const std::vector<std::vector<Cigar>> &routes, bool xcigar = false) {
+    return detail::summarize(detail::params(mode, scores, gapOpen, gapExtend, 10000, 10000), reads, nullptr, &windows, routes, xcigar);
+}
+inline std::string FormatXCigar(const std::vector<Cigar> &route) { // e.g. "12=1X30=2D5=" ("*" for an empty one)
+    std::string s;
+    for (const Cigar &c : route) s += std::to_string(c.RunLength) + "MID=X"[c.Op];
+    return s.empty() ? "*" : s;
+}
+
 inline void AffineGapLocalEngine(const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, std::vector<TargetQueryPair> &pairs) {
     std::vector<std::vector<dna::Base>> t, q;
     for (auto &p : pairs) { t.push_back(p.Target); q.push_back(p.Query); }
