@@ -6,7 +6,7 @@
 
 namespace {
 // ------------------------------------------------------------------------------------------------------
-// A read that matches its window without an indel, with a small mismatch deficit and no second copy in the window has a provably
+// A read that matches its window without an indel, with a mismatch deficit below two gap opens and no second copy in the window has a provably
 // unique optimal alignment: leading gap, one diagonal, trailing gap (a few trailing bases possibly on the window's last columns).
 // fp_cert_kernel proves that per pair -- one wave per pair -- and writes score, run count and staged runs exactly as fp_walk_kernel
 // would have; every other pair gets live[p] = 1 and goes through sweep and walk as before.

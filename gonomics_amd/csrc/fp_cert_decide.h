@@ -40,8 +40,9 @@ GNX_CERT_HD inline void gnx_cert_matrix_init(GnxCertMatrix *mx, const int64_t *s
 
 // Items 1 (shape and checkerboard), 2 (no N in the read), 4, 5 and 6 of the certificate for a pair whose exact K-mer matches all lie on
 // diagonal c (item 3, the caller's scan).  a[0..n) = the read; bd / bf / bl[0..n) = the window's bases under the read on diagonal c, on
-// the window's first n columns and on its last n columns (b + c, b, b + m - n).  Returns 1 and the closed form -- d* = the trailing read
-// bases that sit on the window's last columns, the score -- or 0: the pair goes through the sweep.
+// the window's first n columns and on its last n columns (b + c, b, b + m - n).  Item 4 has two branches: deficit < -o, or
+// -o < deficit < -2o with the edge rule (a second pass over at most T2 rows from each end, running sums only).  Returns 1 and the
+// closed form -- d* = the trailing read bases that sit on the window's last columns, the score -- or 0: the pair goes through the sweep.
 GNX_CERT_HD inline int gnx_cert_decide(const GnxCertMatrix *mx, const uint8_t *a, int64_t n, const uint8_t *bd, const uint8_t *bf, const uint8_t *bl,
                                        int64_t m, int64_t c, int64_t K, int64_t ci, int64_t cj, int64_t *d_star, int64_t *score) {
     if (!mx->ok || n < 1 || K < 1 || m < n + 2 || c <= 0 || c >= m - n) return 0;
@@ -56,10 +57,26 @@ GNX_CERT_HD inline int gnx_cert_decide(const GnxCertMatrix *mx, const uint8_t *a
         F += mx->w[x * 5 + bf[i]] - mid; // the first i + 1 rows on the window's first columns instead (ties stay on the diagonal)
         if (F > 0) return 0;
     }
-    if (deficit >= -mx->o) return 0;
-    const int64_t J = deficit / mx->lambda, J1 = (deficit - mx->o) / mx->lambda;
+    const int64_t O = -mx->o;
+    if (deficit == O || deficit >= 2 * O) return 0; // (deficit == -o: a perfect path with three gap runs ties; refused, not argued)
+    const int64_t J = deficit / mx->lambda, J1 = (deficit + O) / mx->lambda;
     if (n - J <= 0 || n - J1 <= 0) return 0;
     if (K > (n - J + (3 + J) - 1) / (3 + J) || K > (n - J1 + (2 + J1) - 1) / (2 + J1)) return 0;
+    if (deficit > O) {
+        // -o < deficit < -2o: paths with three gap runs.  Off diagonal c they need an exact run of K rows (the third inequality); with a
+        // segment on diagonal c they have to save -o or more on the rows outside it: at most T1 rows at one end and T2 at the other.
+        const int64_t J3 = (deficit - O) / mx->lambda;
+        if (K > (n - J3 + (4 + J3) - 1) / (4 + J3)) return 0;
+        const int64_t T1 = (1 + J3) * (K - 1) + J3, T2 = (2 + J3) * (K - 1) + J3;
+        if (T1 + T2 >= n) return 0; // (every row is an edge row: E = deficit)
+        int64_t h1 = 0, h2 = 0, t1 = 0, t2 = 0; // the loss of the first / last T1 and T2 rows
+        for (int64_t i = 0; i < T2; i++) {
+            const int64_t lh = mx->R[a[i]] - mx->w[a[i] * 5 + bd[i]], lt = mx->R[a[n - 1 - i]] - mx->w[a[n - 1 - i] * 5 + bd[n - 1 - i]];
+            h2 += lh; t2 += lt;
+            if (i < T1) { h1 += lh; t1 += lt; }
+        }
+        if (h1 + t2 >= O || h2 + t1 >= O) return 0;
+    }
     int64_t G = 0, best = 0, ds = 0;
     for (int64_t d = 1; d <= n; d++) { // the last d rows on the window's last columns instead: the LARGEST d that attains the maximum
         const int64_t i = n - d;
