@@ -32,6 +32,7 @@
 //   affine_long.hip.h  the same scheme for affine pairs whose matrix does not fit     seed_kernels.hip.h  the graph aligner's index / seed search
 //   lat_fill.hip.h     lat_fill_kernel: one pair per wave (64 lanes x 2 rows), launches of few long pairs
 //   gnx_host.hip.h     host-buffer entry points: pinned staging, sub-batches, resident reference, contexts per GPU, RCCL
+//   host_cut.h         the sub-batch cut of the host flows (plain C++, tested on the CPU)
 //   gnx_align.hip      host orchestration + C ABI (this file)
 #include "gnx_common.hip.h"
 #include "fill_affine.hip.h"
@@ -2757,6 +2758,23 @@ std::atomic<int64_t> g_sv_lds{0}, g_sv_slab{0}; // reads voted with the table in
 
 #include "gnx_host.hip.h"
 
+namespace {
+struct ApiCall { // a host entry's frame: the entries run one at a time, and each starts with no error text of its own
+    std::lock_guard<std::mutex> lk;
+    ApiCall() : lk(g_api_mu) { g_err[0] = 0; }
+};
+const uint8_t g_none = 0; // what a null buffer of an entry stands for (its windows are all empty)
+const uint8_t *or_none(const uint8_t *buf) { return buf ? buf : &g_none; }
+std::vector<int64_t> lengths_of(const int64_t *off, int64_t n) { // of n sequences given by n + 1 offsets (one spare element: data() is a table also for n == 0)
+    std::vector<int64_t> len((size_t)n + 1);
+    for (int64_t q = 0; q < n; q++) len[(size_t)q] = off[q + 1] - off[q];
+    return len;
+}
+SeqSide cat_side(const uint8_t *cat, const int64_t *off, int64_t n, const std::vector<int64_t> &len) { return SeqSide{cat, off[n], off, len.data(), false}; } // sequence q = [off[q], off[q + 1]) of cat
+SeqSide ref_side(const int64_t *start, const int64_t *len) { return SeqSide{nullptr, 0, start, len, true}; } // windows of the resident reference
+HostWant scores_only() { HostWant w; w.cigars = false; return w; } // the score-only entries: no CIGARs
+} // namespace
+
 // ------------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------------
@@ -2769,10 +2787,9 @@ int gnx_device_count(void) {
 }
 
 int gnx_init(int device, int64_t workspace_bytes) {
-    std::lock_guard<std::mutex> api(g_api_mu);
+    ApiCall api;
     Ctx &c = ctx_at(0);
     CtxScope sc(c);
-    g_err[0] = 0;
     if (c.inited) {
         if (device == c.device) { if (workspace_bytes > 0) c.ws_limit = workspace_bytes; return GNX_OK; }
         set_err("already bound to another device%s", ""); return GNX_EINVAL;
@@ -2784,8 +2801,7 @@ int gnx_init(int device, int64_t workspace_bytes) {
 }
 
 int gnx_init_devices(int n_devices, const int *devices, int64_t workspace_bytes) {
-    std::lock_guard<std::mutex> api(g_api_mu);
-    g_err[0] = 0;
+    ApiCall api;
     int cnt = 0;
     if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) { set_err("no HIP device available (this library has no CPU fallback)%s", ""); return GNX_EDEVICE; }
     if (n_devices <= 0) n_devices = cnt;
@@ -2882,15 +2898,13 @@ const char *gnx_last_error(void) {
 void gnx_free(void *p) { if (p && !g_pool.put(p)) free(p); }
 
 int gnx_set_reference(const uint8_t *ref, int64_t len) {
-    std::lock_guard<std::mutex> api(g_api_mu);
-    g_err[0] = 0;
+    ApiCall api;
     if (len < 0 || (len > 0 && !ref)) { set_err("bad argument%s", ""); return GNX_EINVAL; }
     return set_reference_packed(ref, len, 0);
 }
 
 int gnx_set_reference_synthetic(int64_t len, uint64_t seed) {
-    std::lock_guard<std::mutex> api(g_api_mu);
-    g_err[0] = 0;
+    ApiCall api;
     if (len < 0) { set_err("bad argument%s", ""); return GNX_EINVAL; }
     return set_reference_packed(nullptr, len, seed);
 }
@@ -2909,30 +2923,25 @@ int gnx_reference_info(int64_t *out_bases, int64_t *out_device_bytes, int64_t *o
 int gnx_align_batch_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *alpha_cat, const int64_t *alpha_off,
                               const int64_t *ref_start, const int64_t *ref_len,
                               int64_t *out_score, gnx_cigar **out_ops, int64_t **out_ops_off) {
-    std::lock_guard<std::mutex> api(g_api_mu);
-    g_err[0] = 0;
+    ApiCall api;
     if (n_pairs < 0 || !alpha_off || (n_pairs > 0 && (!ref_start || !ref_len))) { set_err("bad argument%s", ""); return GNX_EINVAL; }
-    std::vector<int64_t> al((size_t)n_pairs);
-    for (int64_t q = 0; q < n_pairs; q++) al[(size_t)q] = alpha_off[q + 1] - alpha_off[q];
-    return run_host_sharded(p, n_pairs, alpha_cat, alpha_off[n_pairs], alpha_off, al.data(), nullptr, 0, ref_start, ref_len, out_score, out_ops, out_ops_off);
+    const std::vector<int64_t> al = lengths_of(alpha_off, n_pairs);
+    return run_host_sharded(p, n_pairs, cat_side(alpha_cat, alpha_off, n_pairs, al), ref_side(ref_start, ref_len), out_score, out_ops, out_ops_off);
 }
 
 int gnx_align_batch_windows(const gnx_params *p, int64_t n_pairs,
                             const uint8_t *alpha_buf, int64_t alpha_buf_len, const int64_t *alpha_start, const int64_t *alpha_len,
                             const uint8_t *beta_buf, int64_t beta_buf_len, const int64_t *beta_start, const int64_t *beta_len,
                             int64_t *out_score, gnx_cigar **out_ops, int64_t **out_ops_off) {
-    std::lock_guard<std::mutex> api(g_api_mu);
-    g_err[0] = 0;
-    static const uint8_t none = 0;
-    return run_host_sharded(p, n_pairs, alpha_buf ? alpha_buf : &none, alpha_buf_len, alpha_start, alpha_len, beta_buf ? beta_buf : &none, beta_buf_len, beta_start, beta_len,
+    ApiCall api;
+    return run_host_sharded(p, n_pairs, SeqSide{or_none(alpha_buf), alpha_buf_len, alpha_start, alpha_len, false}, SeqSide{or_none(beta_buf), beta_buf_len, beta_start, beta_len, false},
                             out_score, out_ops, out_ops_off);
 }
 
 int gnx_align_batch(const gnx_params *p, int64_t n_pairs, const uint8_t *alpha_cat, const int64_t *alpha_off,
                     const uint8_t *beta_cat, const int64_t *beta_off, int64_t *out_score, gnx_cigar **out_ops, int64_t **out_ops_off) {
     if (n_pairs < 0 || !alpha_off || !beta_off) { set_err("bad argument%s", ""); return GNX_EINVAL; }
-    std::vector<int64_t> al((size_t)n_pairs), bl((size_t)n_pairs);
-    for (int64_t q = 0; q < n_pairs; q++) { al[(size_t)q] = alpha_off[q + 1] - alpha_off[q]; bl[(size_t)q] = beta_off[q + 1] - beta_off[q]; }
+    const std::vector<int64_t> al = lengths_of(alpha_off, n_pairs), bl = lengths_of(beta_off, n_pairs);
     return gnx_align_batch_windows(p, n_pairs, alpha_cat, alpha_off[n_pairs], alpha_off, al.data(), beta_cat, beta_off[n_pairs], beta_off, bl.data(),
                                    out_score, out_ops, out_ops_off);
 }
@@ -2940,110 +2949,104 @@ int gnx_align_batch(const gnx_params *p, int64_t n_pairs, const uint8_t *alpha_c
 /* ---- score-only entries: the align entries minus the CIGAR (gnx_align.h) ---- */
 int gnx_score_batch_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *alpha_cat, const int64_t *alpha_off,
                               const int64_t *ref_start, const int64_t *ref_len, int64_t *out_score) {
-    std::lock_guard<std::mutex> api(g_api_mu);
-    g_err[0] = 0;
+    ApiCall api;
     if (n_pairs < 0 || !alpha_off || (n_pairs > 0 && (!ref_start || !ref_len))) { set_err("bad argument%s", ""); return GNX_EINVAL; }
-    std::vector<int64_t> al((size_t)n_pairs);
-    for (int64_t q = 0; q < n_pairs; q++) al[(size_t)q] = alpha_off[q + 1] - alpha_off[q];
-    return run_host_sharded(p, n_pairs, alpha_cat, alpha_off[n_pairs], alpha_off, al.data(), nullptr, 0, ref_start, ref_len, out_score, nullptr, nullptr, true);
+    const std::vector<int64_t> al = lengths_of(alpha_off, n_pairs);
+    return run_host_sharded(p, n_pairs, cat_side(alpha_cat, alpha_off, n_pairs, al), ref_side(ref_start, ref_len), out_score, nullptr, nullptr, scores_only());
 }
 
 int gnx_score_batch_windows(const gnx_params *p, int64_t n_pairs,
                             const uint8_t *alpha_buf, int64_t alpha_buf_len, const int64_t *alpha_start, const int64_t *alpha_len,
                             const uint8_t *beta_buf, int64_t beta_buf_len, const int64_t *beta_start, const int64_t *beta_len, int64_t *out_score) {
-    std::lock_guard<std::mutex> api(g_api_mu);
-    g_err[0] = 0;
-    static const uint8_t none = 0;
-    return run_host_sharded(p, n_pairs, alpha_buf ? alpha_buf : &none, alpha_buf_len, alpha_start, alpha_len, beta_buf ? beta_buf : &none, beta_buf_len, beta_start, beta_len,
-                            out_score, nullptr, nullptr, true);
+    ApiCall api;
+    return run_host_sharded(p, n_pairs, SeqSide{or_none(alpha_buf), alpha_buf_len, alpha_start, alpha_len, false}, SeqSide{or_none(beta_buf), beta_buf_len, beta_start, beta_len, false},
+                            out_score, nullptr, nullptr, scores_only());
 }
 
 int gnx_score_batch(const gnx_params *p, int64_t n_pairs, const uint8_t *alpha_cat, const int64_t *alpha_off,
                     const uint8_t *beta_cat, const int64_t *beta_off, int64_t *out_score) {
     if (n_pairs < 0 || !alpha_off || !beta_off) { set_err("bad argument%s", ""); return GNX_EINVAL; }
-    std::vector<int64_t> al((size_t)n_pairs), bl((size_t)n_pairs);
-    for (int64_t q = 0; q < n_pairs; q++) { al[(size_t)q] = alpha_off[q + 1] - alpha_off[q]; bl[(size_t)q] = beta_off[q + 1] - beta_off[q]; }
+    const std::vector<int64_t> al = lengths_of(alpha_off, n_pairs), bl = lengths_of(beta_off, n_pairs);
     return gnx_score_batch_windows(p, n_pairs, alpha_cat, alpha_off[n_pairs], alpha_off, al.data(), beta_cat, beta_off[n_pairs], beta_off, bl.data(), out_score);
 }
 
-/* ---- locate entries: AffineGapLocal's score and target end (gnx_align.h) ---- */
+/* ---- locate entries: AffineGapLocal's score and target end (gnx_align.h); span entries: the target START of the alignment as well ---- */
+// alpha = target, beta = query, both host windows
+static int locate_windows(const gnx_params *p, int64_t n_pairs, const SeqSide &target, const SeqSide &query, int64_t *out_score, int64_t *out_target_start, int64_t *out_target_end) {
+    HostWant want = scores_only();
+    want.end = out_target_end; want.start = out_target_start;
+    return run_host_sharded(p, n_pairs, target, query, out_score, nullptr, nullptr, want);
+}
+// alpha = query (concatenated reads), beta = target (windows of the resident reference)
+static int locate_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *query_cat, const int64_t *query_off, const int64_t *ref_start, const int64_t *ref_len,
+                            int64_t *out_score, int64_t *out_target_start, int64_t *out_target_end) {
+    const std::vector<int64_t> ql = lengths_of(query_off, n_pairs);
+    HostWant want = scores_only();
+    want.end = out_target_end; want.start = out_target_start; want.query_is_alpha = true;
+    return run_host_sharded(p, n_pairs, cat_side(query_cat, query_off, n_pairs, ql), ref_side(ref_start, ref_len), out_score, nullptr, nullptr, want);
+}
+
 int gnx_locate_batch_windows(const gnx_params *p, int64_t n_pairs,
                              const uint8_t *target_buf, int64_t target_buf_len, const int64_t *target_start, const int64_t *target_len,
                              const uint8_t *query_buf, int64_t query_buf_len, const int64_t *query_start, const int64_t *query_len,
                              int64_t *out_score, int64_t *out_target_end) {
-    std::lock_guard<std::mutex> api(g_api_mu);
-    g_err[0] = 0;
-    static const uint8_t none = 0;
+    ApiCall api;
     if (!out_target_end) { set_err("bad argument%s", ""); return GNX_EINVAL; }
-    return run_host_sharded(p, n_pairs, target_buf ? target_buf : &none, target_buf_len, target_start, target_len, query_buf ? query_buf : &none, query_buf_len, query_start, query_len,
-                            out_score, nullptr, nullptr, true, out_target_end, 1);
+    return locate_windows(p, n_pairs, SeqSide{or_none(target_buf), target_buf_len, target_start, target_len, false}, SeqSide{or_none(query_buf), query_buf_len, query_start, query_len, false},
+                          out_score, nullptr, out_target_end);
 }
 
 int gnx_locate_batch(const gnx_params *p, int64_t n_pairs, const uint8_t *target_cat, const int64_t *target_off,
                      const uint8_t *query_cat, const int64_t *query_off, int64_t *out_score, int64_t *out_target_end) {
     if (n_pairs < 0 || !target_off || !query_off) { set_err("bad argument%s", ""); return GNX_EINVAL; }
-    std::vector<int64_t> tl((size_t)n_pairs), ql((size_t)n_pairs);
-    for (int64_t q = 0; q < n_pairs; q++) { tl[(size_t)q] = target_off[q + 1] - target_off[q]; ql[(size_t)q] = query_off[q + 1] - query_off[q]; }
+    const std::vector<int64_t> tl = lengths_of(target_off, n_pairs), ql = lengths_of(query_off, n_pairs);
     return gnx_locate_batch_windows(p, n_pairs, target_cat, target_off[n_pairs], target_off, tl.data(), query_cat, query_off[n_pairs], query_off, ql.data(), out_score, out_target_end);
 }
 
 int gnx_locate_batch_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *query_cat, const int64_t *query_off,
                                const int64_t *ref_start, const int64_t *ref_len, int64_t *out_score, int64_t *out_target_end) {
-    std::lock_guard<std::mutex> api(g_api_mu);
-    g_err[0] = 0;
+    ApiCall api;
     if (n_pairs < 0 || !query_off || !out_target_end || (n_pairs > 0 && (!ref_start || !ref_len))) { set_err("bad argument%s", ""); return GNX_EINVAL; }
-    std::vector<int64_t> ql((size_t)n_pairs);
-    for (int64_t q = 0; q < n_pairs; q++) ql[(size_t)q] = query_off[q + 1] - query_off[q];
-    return run_host_sharded(p, n_pairs, query_cat, query_off[n_pairs], query_off, ql.data(), nullptr, 0, ref_start, ref_len, out_score, nullptr, nullptr, true, out_target_end, 2);
+    return locate_by_offset(p, n_pairs, query_cat, query_off, ref_start, ref_len, out_score, nullptr, out_target_end);
 }
 
-/* ---- span entries: the locate entries plus the target START of the alignment (gnx_align.h) ---- */
 int gnx_locate_span_batch_windows(const gnx_params *p, int64_t n_pairs,
                                   const uint8_t *target_buf, int64_t target_buf_len, const int64_t *target_start, const int64_t *target_len,
                                   const uint8_t *query_buf, int64_t query_buf_len, const int64_t *query_start, const int64_t *query_len,
                                   int64_t *out_score, int64_t *out_target_start, int64_t *out_target_end) {
-    std::lock_guard<std::mutex> api(g_api_mu);
-    g_err[0] = 0;
-    static const uint8_t none = 0;
+    ApiCall api;
     if (!out_target_end || !out_target_start) { set_err("bad argument%s", ""); return GNX_EINVAL; }
-    return run_host_sharded(p, n_pairs, target_buf ? target_buf : &none, target_buf_len, target_start, target_len, query_buf ? query_buf : &none, query_buf_len, query_start, query_len,
-                            out_score, nullptr, nullptr, true, out_target_end, 3, out_target_start);
+    return locate_windows(p, n_pairs, SeqSide{or_none(target_buf), target_buf_len, target_start, target_len, false}, SeqSide{or_none(query_buf), query_buf_len, query_start, query_len, false},
+                          out_score, out_target_start, out_target_end);
 }
 
 int gnx_locate_span_batch(const gnx_params *p, int64_t n_pairs, const uint8_t *target_cat, const int64_t *target_off,
                           const uint8_t *query_cat, const int64_t *query_off, int64_t *out_score, int64_t *out_target_start, int64_t *out_target_end) {
     if (n_pairs < 0 || !target_off || !query_off) { set_err("bad argument%s", ""); return GNX_EINVAL; }
-    std::vector<int64_t> tl((size_t)n_pairs), ql((size_t)n_pairs);
-    for (int64_t q = 0; q < n_pairs; q++) { tl[(size_t)q] = target_off[q + 1] - target_off[q]; ql[(size_t)q] = query_off[q + 1] - query_off[q]; }
+    const std::vector<int64_t> tl = lengths_of(target_off, n_pairs), ql = lengths_of(query_off, n_pairs);
     return gnx_locate_span_batch_windows(p, n_pairs, target_cat, target_off[n_pairs], target_off, tl.data(), query_cat, query_off[n_pairs], query_off, ql.data(),
                                          out_score, out_target_start, out_target_end);
 }
 
 int gnx_locate_span_batch_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *query_cat, const int64_t *query_off,
                                     const int64_t *ref_start, const int64_t *ref_len, int64_t *out_score, int64_t *out_target_start, int64_t *out_target_end) {
-    std::lock_guard<std::mutex> api(g_api_mu);
-    g_err[0] = 0;
+    ApiCall api;
     if (n_pairs < 0 || !query_off || !out_target_end || !out_target_start || (n_pairs > 0 && (!ref_start || !ref_len))) { set_err("bad argument%s", ""); return GNX_EINVAL; }
-    std::vector<int64_t> ql((size_t)n_pairs);
-    for (int64_t q = 0; q < n_pairs; q++) ql[(size_t)q] = query_off[q + 1] - query_off[q];
-    return run_host_sharded(p, n_pairs, query_cat, query_off[n_pairs], query_off, ql.data(), nullptr, 0, ref_start, ref_len, out_score, nullptr, nullptr, true, out_target_end, 4,
-                            out_target_start);
+    return locate_by_offset(p, n_pairs, query_cat, query_off, ref_start, ref_len, out_score, out_target_start, out_target_end);
 }
 
 /* ---- best of K on both strands: score every candidate, keep the first maximum, align the winners (gnx_align.h) ---- */
 int gnx_best_of_by_offset(const gnx_params *p, int64_t n_reads, const uint8_t *read_cat, const int64_t *read_off,
                           const int64_t *cand_off, const int64_t *cand_start, const int64_t *cand_len, const uint8_t *cand_strand,
                           int32_t *out_best, int64_t *out_score, int64_t *out_target_end, int64_t *out_cand_score, gnx_cigar **out_ops, int64_t **out_ops_off) {
-    std::lock_guard<std::mutex> api(g_api_mu);
-    g_err[0] = 0;
+    ApiCall api;
     return run_best_of(p, n_reads, read_cat, read_off, true, nullptr, 0, cand_off, cand_start, cand_len, cand_strand, out_best, out_score, out_target_end, out_cand_score, out_ops, out_ops_off);
 }
 
 int gnx_best_of_windows(const gnx_params *p, int64_t n_reads, const uint8_t *read_cat, const int64_t *read_off, const uint8_t *target_buf, int64_t target_buf_len,
                         const int64_t *cand_off, const int64_t *cand_start, const int64_t *cand_len, const uint8_t *cand_strand,
                         int32_t *out_best, int64_t *out_score, int64_t *out_target_end, int64_t *out_cand_score, gnx_cigar **out_ops, int64_t **out_ops_off) {
-    std::lock_guard<std::mutex> api(g_api_mu);
-    g_err[0] = 0;
+    ApiCall api;
     return run_best_of(p, n_reads, read_cat, read_off, false, target_buf, target_buf_len, cand_off, cand_start, cand_len, cand_strand, out_best, out_score, out_target_end, out_cand_score,
                        out_ops, out_ops_off);
 }
@@ -3054,8 +3057,7 @@ int gnx_best_pair_by_offset(const gnx_params *p, const gnx_pair_opts *o, int64_t
                             int32_t *out_best, int64_t *out_score, int64_t *out_target_start, int64_t *out_target_end,
                             int64_t *out_second_score, uint8_t *out_proper, int64_t *out_tlen,
                             int64_t *out_cand_score, int64_t *out_cand_start, int64_t *out_cand_end, gnx_cigar **out_ops, int64_t **out_ops_off) {
-    std::lock_guard<std::mutex> api(g_api_mu);
-    g_err[0] = 0;
+    ApiCall api;
     const PairOut pr{o, out_target_start, out_second_score, out_proper, out_tlen, out_cand_start, out_cand_end};
     return run_best_of(p, n_reads, read_cat, read_off, true, nullptr, 0, cand_off, cand_start, cand_len, cand_strand, out_best, out_score, out_target_end, out_cand_score, out_ops, out_ops_off, &pr);
 }
@@ -3066,8 +3068,7 @@ int gnx_best_pair_windows(const gnx_params *p, const gnx_pair_opts *o, int64_t n
                           int32_t *out_best, int64_t *out_score, int64_t *out_target_start, int64_t *out_target_end,
                           int64_t *out_second_score, uint8_t *out_proper, int64_t *out_tlen,
                           int64_t *out_cand_score, int64_t *out_cand_start, int64_t *out_cand_end, gnx_cigar **out_ops, int64_t **out_ops_off) {
-    std::lock_guard<std::mutex> api(g_api_mu);
-    g_err[0] = 0;
+    ApiCall api;
     const PairOut pr{o, out_target_start, out_second_score, out_proper, out_tlen, out_cand_start, out_cand_end};
     return run_best_of(p, n_reads, read_cat, read_off, false, target_buf, target_buf_len, cand_off, cand_start, cand_len, cand_strand, out_best, out_score, out_target_end, out_cand_score,
                        out_ops, out_ops_off, &pr);
@@ -3078,29 +3079,25 @@ int gnx_summarize_batch_windows(const gnx_params *p, int64_t n_pairs,
                                 const uint8_t *alpha_buf, int64_t alpha_buf_len, const int64_t *alpha_start, const int64_t *alpha_len,
                                 const uint8_t *beta_buf, int64_t beta_buf_len, const int64_t *beta_start, const int64_t *beta_len,
                                 const gnx_cigar *ops, const int64_t *ops_off, gnx_aln_summary *out, gnx_cigar **out_xops, int64_t **out_xops_off) {
-    std::lock_guard<std::mutex> api(g_api_mu);
-    g_err[0] = 0;
-    const SumSide sa{alpha_buf, alpha_buf_len, alpha_start, alpha_len, false}, sb{beta_buf, beta_buf_len, beta_start, beta_len, false};
+    ApiCall api;
+    const SeqSide sa{alpha_buf, alpha_buf_len, alpha_start, alpha_len, false}, sb{beta_buf, beta_buf_len, beta_start, beta_len, false};
     return run_summarize(p, n_pairs, sa, sb, ops, ops_off, out, out_xops, out_xops_off);
 }
 
 int gnx_summarize_batch(const gnx_params *p, int64_t n_pairs, const uint8_t *alpha_cat, const int64_t *alpha_off, const uint8_t *beta_cat, const int64_t *beta_off,
                         const gnx_cigar *ops, const int64_t *ops_off, gnx_aln_summary *out, gnx_cigar **out_xops, int64_t **out_xops_off) {
     if (n_pairs < 0 || !alpha_off || !beta_off) { set_err("bad argument%s", ""); return GNX_EINVAL; }
-    std::vector<int64_t> al((size_t)n_pairs + 1), bl((size_t)n_pairs + 1);
-    for (int64_t q = 0; q < n_pairs; q++) { al[(size_t)q] = alpha_off[q + 1] - alpha_off[q]; bl[(size_t)q] = beta_off[q + 1] - beta_off[q]; }
+    const std::vector<int64_t> al = lengths_of(alpha_off, n_pairs), bl = lengths_of(beta_off, n_pairs);
     return gnx_summarize_batch_windows(p, n_pairs, alpha_cat, alpha_off[n_pairs], alpha_off, al.data(), beta_cat, beta_off[n_pairs], beta_off, bl.data(),
                                        ops, ops_off, out, out_xops, out_xops_off);
 }
 
 int gnx_summarize_batch_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *read_cat, const int64_t *read_off, const int64_t *ref_start, const int64_t *ref_len,
                                   const gnx_cigar *ops, const int64_t *ops_off, gnx_aln_summary *out, gnx_cigar **out_xops, int64_t **out_xops_off) {
-    std::lock_guard<std::mutex> api(g_api_mu);
-    g_err[0] = 0;
+    ApiCall api;
     if (!p || n_pairs < 0 || !read_off || !ref_start || !ref_len) { set_err("bad argument%s", ""); return GNX_EINVAL; }
-    std::vector<int64_t> rl((size_t)n_pairs + 1);
-    for (int64_t q = 0; q < n_pairs; q++) rl[(size_t)q] = read_off[q + 1] - read_off[q];
-    const SumSide reads{read_cat, read_off[n_pairs], read_off, rl.data(), false}, wins{nullptr, 0, ref_start, ref_len, true};
+    const std::vector<int64_t> rl = lengths_of(read_off, n_pairs);
+    const SeqSide reads = cat_side(read_cat, read_off, n_pairs, rl), wins = ref_side(ref_start, ref_len);
     const bool local = p->mode == GNX_AFFINE_GAP_LOCAL; // the roles of gnx_best_of_by_offset: the window is the target (alpha) of the mapping mode, beta everywhere else
     return run_summarize(p, n_pairs, local ? wins : reads, local ? reads : wins, ops, ops_off, out, out_xops, out_xops_off);
 }
@@ -3110,9 +3107,8 @@ int gnx_score_batch_device(const gnx_params *p, int64_t n_pairs,
                            const uint8_t *d_beta_buf, const int64_t *d_beta_start, const int64_t *d_beta_len,
                            const int64_t *h_alpha_len, const int64_t *h_beta_len, int64_t *d_score, void *stream) {
     (void)d_alpha_len; (void)d_beta_len; // lengths are taken from the host copies (planning needs them anyway)
-    std::lock_guard<std::mutex> api(g_api_mu);
+    ApiCall api;
     CtxScope sc(ctx_at(0));
-    g_err[0] = 0;
     int rc = ensure_init();
     if (rc) return rc;
     if (!p || n_pairs < 0 || !d_score || (n_pairs > 0 && (!h_alpha_len || !h_beta_len || !d_alpha_start || !d_beta_start))) {
@@ -3124,9 +3120,8 @@ int gnx_score_batch_device(const gnx_params *p, int64_t n_pairs,
 int gnx_gsw_extend_batch(int side, const int64_t *scores, int64_t gap_pen, int64_t n_pairs,
                          const uint8_t *alpha_cat, const int64_t *alpha_off, const uint8_t *beta_cat, const int64_t *beta_off,
                          int64_t *out_score, int64_t *out_end_i, int64_t *out_end_j, gnx_cigar **out_ops, int64_t **out_ops_off) {
-    std::lock_guard<std::mutex> api(g_api_mu);
+    ApiCall api;
     CtxScope sc(ctx_at(0));
-    g_err[0] = 0;
     if ((side != GNX_GSW_LEFT && side != GNX_GSW_RIGHT) || !scores || n_pairs < 0 || !alpha_off || !beta_off) { set_err("bad argument%s", ""); return GNX_EINVAL; }
     int rc = ensure_init();
     if (rc) return rc;
@@ -3163,9 +3158,8 @@ std::atomic<int64_t> g_pq_batches{0}, g_pq_pairs{0}; // combined batches run / p
 int run_pair_alone(PairReq &r) {
     const int64_t zero = 0;
     int64_t *off = nullptr;
-    static const uint8_t none = 0;
     g_err[0] = 0;
-    int rc = run_host_sharded(r.p, 1, r.a ? r.a : &none, r.n, &zero, &r.n, r.b ? r.b : &none, r.m, &zero, &r.m, &r.score, &r.ops, &off);
+    int rc = run_host_sharded(r.p, 1, SeqSide{or_none(r.a), r.n, &zero, &r.n, false}, SeqSide{or_none(r.b), r.m, &zero, &r.m, false}, &r.score, &r.ops, &off);
     if (rc == GNX_OK) { r.n_ops = off[1]; gnx_free(off); }
     else memcpy(r.err, g_err, sizeof(r.err));
     return rc;
@@ -3186,7 +3180,7 @@ void run_pair_batch(const gnx_params *p, std::vector<PairReq *> &batch) {
         gnx_cigar *ops = nullptr;
         int64_t *off = nullptr;
         g_err[0] = 0;
-        int rc = run_host_sharded(p, nb, ca.data(), ta, as.data(), al.data(), cb.data(), tb, bs.data(), bl.data(), sc.data(), &ops, &off);
+        int rc = run_host_sharded(p, nb, SeqSide{ca.data(), ta, as.data(), al.data(), false}, SeqSide{cb.data(), tb, bs.data(), bl.data(), false}, sc.data(), &ops, &off);
         if (rc == GNX_OK) {
             for (int64_t k = 0; k < nb && rc == GNX_OK; k++) {
                 PairReq &r = *batch[(size_t)k];
@@ -3287,9 +3281,8 @@ int gnx_align_batch_device(const gnx_params *p, int64_t n_pairs,
                            int64_t *d_score, gnx_cigar *d_ops, int64_t ops_capacity, int64_t *d_ops_off,
                            int64_t *out_total_ops, void *stream) {
     (void)d_alpha_len; (void)d_beta_len; // lengths are taken from the host copies (planning needs them anyway)
-    std::lock_guard<std::mutex> api(g_api_mu);
+    ApiCall api;
     CtxScope sc(ctx_at(0));
-    g_err[0] = 0;
     int rc = ensure_init();
     if (rc) return rc;
     if (!p || n_pairs < 0 || !d_score || !d_ops_off || ops_capacity < 0 || (n_pairs > 0 && (!h_alpha_len || !h_beta_len || !d_alpha_start || !d_beta_start))) {
@@ -3302,9 +3295,8 @@ int gnx_align_batch_device(const gnx_params *p, int64_t n_pairs,
 int gnx_affine_gap_chunk_batch(const gnx_params *p, int64_t chunk_size, int64_t n_pairs,
                                const uint8_t *alpha_cat, const int64_t *alpha_off, const uint8_t *beta_cat, const int64_t *beta_off,
                                int64_t *out_score, gnx_cigar **out_ops, int64_t **out_ops_off) {
-    std::lock_guard<std::mutex> api(g_api_mu);
+    ApiCall api;
     CtxScope sc(ctx_at(0));
-    g_err[0] = 0;
     int rc = ensure_init();
     if (rc) return rc;
     if (n_pairs < 0 || chunk_size < 1 || (n_pairs > 0 && (!alpha_off || !beta_off))) { set_err("bad argument%s", ""); return GNX_EINVAL; }
@@ -3327,9 +3319,8 @@ int gnx_multiple_affine_gap_batch(const gnx_params *p, int64_t chunk_size, int64
                                   const int64_t *group_off, const int32_t *group_nseq, const int64_t *group_len,
                                   int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b,
                                   int64_t *out_score, gnx_cigar **out_ops, int64_t **out_ops_off) {
-    std::lock_guard<std::mutex> api(g_api_mu);
+    ApiCall api;
     CtxScope sc(ctx_at(0));
-    g_err[0] = 0;
     int rc = ensure_init();
     if (rc) return rc;
     if (n_pairs < 0 || n_groups < 0 || chunk_size < 1 || (n_groups > 0 && (!group_off || !group_nseq || !group_len)) || (n_pairs > 0 && (!pair_a || !pair_b))) {
@@ -3358,9 +3349,8 @@ int gnx_multiple_affine_gap_batch(const gnx_params *p, int64_t chunk_size, int64
 // score-only twins: the same validation, the same errors, out_score alone (run_host_scored, score_only)
 int gnx_affine_gap_chunk_score_batch(const gnx_params *p, int64_t chunk_size, int64_t n_pairs,
                                      const uint8_t *alpha_cat, const int64_t *alpha_off, const uint8_t *beta_cat, const int64_t *beta_off, int64_t *out_score) {
-    std::lock_guard<std::mutex> api(g_api_mu);
+    ApiCall api;
     CtxScope sc(ctx_at(0));
-    g_err[0] = 0;
     // (what needs no device is refused before one is looked for)
     if (!p || !out_score || n_pairs < 0 || chunk_size < 1 || chunk_size > (1 << 20) || (n_pairs > 0 && (!alpha_off || !beta_off))) { set_err("bad argument%s", ""); return GNX_EINVAL; }
     if (p->mode != GNX_AFFINE_GAP_HIGHMEM) { set_err("the chunk / multiple-alignment variants have AffineGap_highMem semantics (mode %s%lld)", "", (long long)GNX_AFFINE_GAP_HIGHMEM); return GNX_EINVAL; }
@@ -3384,9 +3374,8 @@ int gnx_affine_gap_chunk_score_batch(const gnx_params *p, int64_t chunk_size, in
 int gnx_multiple_affine_gap_score_batch(const gnx_params *p, int64_t chunk_size, int64_t n_groups, const uint8_t *group_bases,
                                         const int64_t *group_off, const int32_t *group_nseq, const int64_t *group_len,
                                         int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b, int64_t *out_score) {
-    std::lock_guard<std::mutex> api(g_api_mu);
+    ApiCall api;
     CtxScope sc(ctx_at(0));
-    g_err[0] = 0;
     if (!p || !out_score || n_pairs < 0 || n_groups < 0 || chunk_size < 1 || chunk_size > (1 << 20) || (n_groups > 0 && (!group_off || !group_nseq || !group_len)) || (n_pairs > 0 && (!pair_a || !pair_b))) {
         set_err("bad argument%s", ""); return GNX_EINVAL;
     }
@@ -3416,9 +3405,8 @@ int gnx_multiple_affine_gap_score_batch(const gnx_params *p, int64_t chunk_size,
 /* ---- "next" row N4: seed index and seed search of the graph aligner (see seed_kernels.hip.h) ---- */
 int gnx_seed_index_build(const uint8_t *node_cat, const int64_t *node_off, int64_t n_nodes, int seed_len, int seed_step,
                          uint64_t **out_keys, uint64_t **out_locs, int64_t *out_n) {
-    std::lock_guard<std::mutex> api(g_api_mu);
+    ApiCall api;
     CtxScope sc(ctx_at(0));
-    g_err[0] = 0;
     if (!node_off || n_nodes < 0 || n_nodes > 0x7ffffff0 || seed_len < 2 || seed_len > 32 || seed_step < 1 || !out_keys || !out_locs || !out_n) { set_err("bad argument%s", ""); return GNX_EINVAL; }
     int rc = ensure_init();
     if (rc) return rc;
@@ -3623,9 +3611,8 @@ static_assert(RS_COUNT == sizeof(Ctx::rs) / sizeof(DevBuf), "Ctx::rs holds one b
 } // namespace
 
 int gnx_reference_index_build(int seed_len, int seed_step) {
-    std::lock_guard<std::mutex> api(g_api_mu);
+    ApiCall api;
     CtxScope sc(ctx_at(0));
-    g_err[0] = 0;
     if (seed_len < 8 || seed_len > 32 || seed_step < 1) { set_err("gnx_reference_index_build: seed_len must be 8 .. 32 and seed_step >= 1%s", ""); return GNX_EINVAL; }
     Ctx &c = g_ctx;
     if (!c.inited || c.ref_len < 0) { set_err("no resident reference: call gnx_set_reference first%s", ""); return GNX_EINVAL; }
@@ -3683,10 +3670,9 @@ int gnx_reference_index_build(int seed_len, int seed_step) {
 }
 
 int gnx_reference_index_info(int64_t *out_n_kmers, int64_t *out_device_bytes, int *out_seed_len, int *out_seed_step) {
-    std::lock_guard<std::mutex> api(g_api_mu);
+    ApiCall api;
     Ctx &c = ctx_at(0);
     CtxScope sc(c);
-    g_err[0] = 0;
     if (!reference_index_live(c)) { set_err("no reference index: call gnx_reference_index_build first%s", ""); return GNX_EINVAL; }
     if (out_n_kmers) *out_n_kmers = c.ri_n;
     if (out_device_bytes) *out_device_bytes = c.ri_n * 16 + (((int64_t)1 << c.ri_dir_bits) + 1) * 8; // keys, positions, the prefix directory
@@ -3696,10 +3682,9 @@ int gnx_reference_index_info(int64_t *out_n_kmers, int64_t *out_device_bytes, in
 }
 
 int gnx_reference_index_get(uint64_t **out_keys, uint64_t **out_pos, int64_t *out_n) {
-    std::lock_guard<std::mutex> api(g_api_mu);
+    ApiCall api;
     Ctx &c = ctx_at(0);
     CtxScope sc(c);
-    g_err[0] = 0;
     if (!out_keys || !out_pos || !out_n) { set_err("bad argument%s", ""); return GNX_EINVAL; }
     if (!reference_index_live(c)) { set_err("no reference index: call gnx_reference_index_build first%s", ""); return GNX_EINVAL; }
     int rc = ensure_init();
@@ -3876,9 +3861,8 @@ int gnx_seed_candidates(const gnx_seed_vote_opts *o, int64_t n_reads, const uint
  * n_workgroups workgroups that each hold a whole CU's LDS and spin for `milliseconds`, on a stream of their own; returns
  * at once.  The stress leg of the claim protocol (tests/test_ticket.py): piped launches must finish with half the CUs taken away. */
 int gnx_debug_occupy(int n_workgroups, int milliseconds) {
-    std::lock_guard<std::mutex> api(g_api_mu);
+    ApiCall api;
     CtxScope sc(ctx_at(0));
-    g_err[0] = 0;
     if (!getenv("GNX_DEBUG_ENTRY")) { set_err("gnx_debug_occupy is a test hook: set GNX_DEBUG_ENTRY=1%s", ""); return GNX_EINVAL; }
     int rc = ensure_init();
     if (rc) return rc;
@@ -3915,9 +3899,8 @@ int gnx_debug_gapless_certificate(const gnx_params *p, const uint8_t *a, int64_t
 /* diagnostics: counters kept on context 0's device.  which = 0: items of piped launches that were run by a workgroup other than
  * their own since the last reset (claim_items: the abnormal path the tests force); reset != 0 zeroes it after reading. */
 int gnx_debug_counter(int which, int reset, int64_t *out) {
-    std::lock_guard<std::mutex> api(g_api_mu);
+    ApiCall api;
     CtxScope sc(ctx_at(0));
-    g_err[0] = 0;
     if (which < 0 || which > 10 || !out) { set_err("bad argument%s", ""); return GNX_EINVAL; }
     if (which >= 9) { // the fast path's gapless certificate: pairs certified / pairs offered to it
         std::atomic<int64_t> &v = which == 9 ? g_cert_ok : g_cert_offered;

@@ -15,6 +15,7 @@
 #include <map>
 #include <thread>
 #include <unordered_map>
+#include "host_cut.h"
 
 namespace {
 
@@ -275,17 +276,26 @@ int set_reference_packed(const uint8_t *ref, int64_t len, uint64_t seed) {
 }
 
 // ---- one context's share of a batch ---------------------------------------------------------------------------------------------
+struct SeqSide { // one sequence per pair: a window (start, len) of buf, or of the resident reference
+    const uint8_t *buf;
+    int64_t buf_len;
+    const int64_t *start, *len;
+    bool resident;
+};
+struct HostWant { // what a host call gives back beside the scores, and which side plays which role
+    bool cigars = true;          // false: gnx_score_* / gnx_locate_* (the score sweep, or the ordinary route with its CIGAR left on the device)
+    int64_t *end = nullptr;      // gnx_locate_* (AffineGapLocal, no CIGARs): the target end of every pair
+    int64_t *start = nullptr;    // gnx_locate_span_* (with end): the target start as well
+    bool query_is_alpha = false; // with end: alpha = query, beta = target (windows of the resident reference); else alpha = target, beta = query
+};
 struct HostJob {
     Ctx *c = nullptr;
     const gnx_params *prm = nullptr;
     int64_t p0 = 0, p1 = 0; // pairs [p0, p1) of the call
-    const uint8_t *a_buf = nullptr; const int64_t *a_start = nullptr, *a_len = nullptr; // host windows
-    const uint8_t *b_buf = nullptr; const int64_t *b_start = nullptr, *b_len = nullptr; // host windows, or windows into b_dev
+    SeqSide a = {}, b = {};  // host windows; b.resident: windows into b_dev
+    HostWant want;           // (end / start: asked for or not -- the values stay on the device until the gather)
     const uint8_t *b_dev = nullptr; // != nullptr: the whole beta buffer / the resident reference is on this context's device
     bool packed = false;            // b_dev is the PACKED resident reference (beta windows = base positions in it)
-    bool score_only = false;        // gnx_score_*: scores only (the score sweep, or the ordinary route with its CIGAR left on the device)
-    bool span = false;              // gnx_locate_span_*: the target start as well (res_start)
-    int locate = 0;                 // gnx_locate_* (score_only as well): 1: alpha = target, beta = query; 2: alpha = query, beta = target (windows of the resident reference)
     int64_t total_ops = 0;
     int rc = GNX_OK;
     char err[512] = "";
@@ -303,6 +313,38 @@ int grow_ops(Ctx &c, int64_t keep_elems, int64_t want_elems, hipStream_t st) {
     }
     c.res_ops.release();
     c.res_ops = nb;
+    return GNX_OK;
+}
+
+// While one lives, run_device and run_score_sweep read the context's beta windows as positions in its packed reference
+// (Ctx::beta_packed, when `on`); the flag is down again on every way out of the scope.
+struct PackedBeta {
+    Ctx &c;
+    PackedBeta(Ctx &c_, bool on) : c(c_) { c.beta_packed = on; }
+    ~PackedBeta() { c.beta_packed = false; }
+};
+
+// sum += the device timing of one sub-batch; fast_path: the last sub-batch's, or the largest code seen (the score-only flows)
+void add_timing(gnx_timing &sum, const gnx_timing &t, bool max_fast_path) {
+    sum.fill_ms += t.fill_ms; sum.traceback_ms += t.traceback_ms; sum.total_ms += t.total_ms; sum.cells += t.cells;
+    sum.n_launches += t.n_launches; sum.trace_bytes += t.trace_bytes; sum.dominant_ms += t.dominant_ms;
+    sum.dominant_launches += t.dominant_launches; sum.fast_path = max_fast_path ? std::max(sum.fast_path, t.fast_path) : t.fast_path;
+}
+
+// `cnt` windows of the context's packed reference (device starts, host lengths) as bytes in c.in_b, their offsets in c.in_bl
+// (AffineGapLocal off the sweep reads its target as the kernels' alpha; GNX_REF_UNPACK: A/B)
+int unpack_ref_windows(Ctx &c, const int64_t *d_starts, const int64_t *h_lens, int64_t cnt, hipStream_t st) {
+    std::vector<int64_t> uoff((size_t)cnt + 1, 0);
+    for (int64_t q = 0; q < cnt; q++) uoff[(size_t)q + 1] = uoff[(size_t)q] + h_lens[q];
+    int r;
+    if ((r = c.in_b.ensure((size_t)uoff[(size_t)cnt] + 64)) || (r = c.in_bl.ensure((size_t)(cnt + 1) * 8))) return r;
+    KParams ukp;
+    memset(&ukp, 0, sizeof(ukp));
+    ukp.b2 = (const unsigned *)c.ref.p; ukp.bflag = (const unsigned long long *)c.ref_flag.p; ukp.brank = (const unsigned *)c.ref_rank.p; ukp.bexc = (const unsigned long long *)c.ref_exc.p;
+    HIPCHK(hipMemcpyAsync(c.in_bl.p, uoff.data(), (size_t)(cnt + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st)); // (uoff is a local)
+    hipLaunchKernelGGL(unpack_windows_kernel, dim3((unsigned)cnt), dim3(256), 0, st, ukp, d_starts, (const int64_t *)c.in_bl.p, (int)cnt, (uint8_t *)c.in_b.p);
+    HIPCHK(hipGetLastError());
     return GNX_OK;
 }
 
@@ -337,6 +379,46 @@ int score_or_fallback(Ctx &c, const gnx_params *prm, int64_t cnt, const uint8_t 
     return rc;
 }
 
+// AffineGapLocal without CIGARs, the reads (queries) as the kernels' alpha against target windows as their beta: the sweep as it
+// is (query_is_alpha), reading the windows where they are -- `packed`: in the packed reference; off the sweep the ordinary route
+// with the two sides swapped, which wants the windows as bytes.
+int locate_reads_in_windows(Ctx &c, const gnx_params *prm, int64_t cnt, const uint8_t *d_reads, const int64_t *d_rs, const int64_t *h_rlen,
+                            const uint8_t *d_win, const int64_t *d_ws, const int64_t *h_wlen, bool packed, int64_t *d_score, int64_t *d_end, int64_t *d_start, hipStream_t st) {
+    int rc;
+    { PackedBeta pb(c, packed); rc = run_score_sweep(prm, cnt, d_reads, d_rs, d_win, d_ws, h_rlen, h_wlen, d_score, st, d_end, true, d_start); }
+    if (rc != -1) return rc;
+    if (packed) {
+        if ((rc = unpack_ref_windows(c, d_ws, h_wlen, cnt, st))) return rc;
+        d_win = (const uint8_t *)c.in_b.p; d_ws = (const int64_t *)c.in_bl.p;
+    }
+    return score_or_fallback(c, prm, cnt, d_win, d_ws, d_reads, d_rs, h_wlen, h_rlen, d_score, st, d_end, false, d_start);
+}
+
+// The CIGAR tail of one sub-batch, pairs [done, done + cnt) of n: `run(d_score, d_ops, cap, d_off, &tot)` is the flow's run_device
+// call (the flows differ in which side is alpha), writing scores and offsets at `done` of the context's result buffers and runs
+// behind the `total` kept so far.  GNX_ECAPACITY grows the run buffer and tries again; then the offsets, which a sub-batch counts
+// from 0, are rebased and `total` moves on.
+template <class Run>
+int run_sub_batch_cigars(Ctx &c, int64_t n, int64_t done, int64_t cnt, int64_t &total, hipStream_t st, Run run) {
+    int64_t tot = 0;
+    int rc;
+    for (int attempt = 0;; attempt++) {
+        const int64_t cap = (int64_t)(c.res_ops.cap / sizeof(gnx_cigar)) - total;
+        rc = run((int64_t *)c.res_score.p + done, (gnx_cigar *)c.res_ops.p + total, cap, (int64_t *)c.res_off.p + done, &tot);
+        if (rc != GNX_ECAPACITY || attempt >= 8) break;
+        // the reported total is exact (every sub-batch of the device flow is counted); leave room for the sub-batches to come
+        const int64_t left = (n - done + cnt - 1) / cnt;
+        if ((rc = grow_ops(c, total, total + tot * std::min<int64_t>(left, 4) + 1024, st))) break;
+    }
+    if (rc) return rc;
+    if (total > 0) {
+        hipLaunchKernelGGL(add_offset_kernel, dim3((unsigned)((cnt + 1 + 255) / 256)), dim3(256), 0, st, (int64_t *)c.res_off.p + done, cnt + 1, total);
+        HIPCHK(hipGetLastError());
+    }
+    total += tot;
+    return GNX_OK;
+}
+
 // runs on the thread that owns the context (t_ctx == job.c, device current)
 int run_host_job(HostJob &j) {
     Ctx &c = *j.c;
@@ -344,15 +426,12 @@ int run_host_job(HostJob &j) {
     int rc;
     if ((rc = c.res_score.ensure((size_t)std::max<int64_t>(n, 1) * 8))) return rc;
     if ((rc = c.res_off.ensure((size_t)(n + 1) * 8))) return rc;
-    if (j.locate && (rc = c.res_end.ensure((size_t)std::max<int64_t>(n, 1) * 8))) return rc;
-    if (j.span && (rc = c.res_start.ensure((size_t)std::max<int64_t>(n, 1) * 8))) return rc;
+    if (j.want.end && (rc = c.res_end.ensure((size_t)std::max<int64_t>(n, 1) * 8))) return rc;
+    if (j.want.start && (rc = c.res_start.ensure((size_t)std::max<int64_t>(n, 1) * 8))) return rc;
     if (n == 0) { HIPCHK(hipMemsetAsync(c.res_off.p, 0, 8, c.own_stream)); HIPCHK(hipStreamSynchronize(c.own_stream)); return GNX_OK; }
-    int64_t sub = 131072;
-    if (const char *e = getenv("GNX_HOST_SUB")) sub = (std::max<int64_t>(atoll(e), 8) + 7) & ~(int64_t)7;
-    const int64_t K0 = (n + sub - 1) / sub;
-    const int64_t size = (((n + K0 - 1) / K0) + 7) & ~(int64_t)7; // equal sub-batches (the fast path re-uses its plans), whole waves
-    const int64_t K = (n + size - 1) / size;                      // rounding `size` up can save a sub-batch: never index past n
-    const int64_t *as = j.a_start + j.p0, *al = j.a_len + j.p0, *bs = j.b_start + j.p0, *bl = j.b_len + j.p0;
+    const int64_t size = sub_batch_size(n, gnx_host_sub(getenv("GNX_HOST_SUB")));
+    const int64_t K = (n + size - 1) / size;
+    const int64_t *as = j.a.start + j.p0, *al = j.a.len + j.p0, *bs = j.b.start + j.p0, *bl = j.b.len + j.p0;
 
     // stage(k): inputs of sub-batch k -> device buffers of slot k & 1 (H2D on s_in, event ev_in[slot]).  k == 0 copies straight from
     // the caller's memory (nothing to overlap with); later ones go through pinned memory so that the DMA runs under the kernels.
@@ -375,7 +454,7 @@ int run_host_job(HostJob &j) {
         if ((r = c.pin_bs[slot].ensure((size_t)cnt * 8))) return r;
         if (!j.b_dev && (r = c.pin_b[slot].ensure((size_t)(bhi - blo) + 16))) return r;
         int64_t *has, *hbs;
-        const uint8_t *src_a = j.a_buf + alo, *src_b = j.b_dev ? nullptr : j.b_buf + blo;
+        const uint8_t *src_a = j.a.buf + alo, *src_b = j.b_dev ? nullptr : j.b.buf + blo;
         if (pinned) {
             if ((r = c.st_a[slot].ensure((size_t)(ahi - alo) + 16))) return r;
             if ((r = c.st_as[slot].ensure((size_t)cnt * 8))) return r;
@@ -405,7 +484,7 @@ int run_host_job(HostJob &j) {
     // CIGAR capacity: a guess that fits every workload of the path's callers, grown (with a retry of the sub-batch) when it does not
     int64_t worst = 0;
     for (int64_t q = 0; q < n; q++) worst += al[q] + bl[q] + 1;
-    if (!j.score_only && (rc = grow_ops(c, 0, std::max<int64_t>(std::min<int64_t>(worst, std::max<int64_t>((int64_t)1 << 20, 64 * std::min(n, size))), 1), c.own_stream))) return rc;
+    if (j.want.cigars && (rc = grow_ops(c, 0, std::max<int64_t>(std::min<int64_t>(worst, std::max<int64_t>((int64_t)1 << 20, 64 * std::min(n, size))), 1), c.own_stream))) return rc;
     gnx_timing tsum = {};
     for (int64_t k = 0; k < K; k++) {
         const int slot = (int)(k & 1);
@@ -420,64 +499,34 @@ int run_host_job(HostJob &j) {
                 if (stage_rc) memcpy(stage_err, g_err, sizeof(stage_err));
             });
         }
-        rc = GNX_OK;
-        if (hipStreamWaitEvent(c.own_stream, c.ev_in[slot], 0) != hipSuccess) { set_err("hipStreamWaitEvent failed%s", ""); rc = GNX_EDEVICE; }
-        int64_t tot = 0;
-        const uint8_t *db = j.b_dev ? j.b_dev : (const uint8_t *)c.pin_b[slot].p;
-        const int64_t *dbs = (const int64_t *)c.pin_bs[slot].p;
-        bool packed = j.packed;
-        // the windows as bytes (AffineGapLocal's transposed fast path reads the long sequence as the kernels' alpha; GNX_REF_UNPACK: A/B)
-        auto unpack_windows = [&]() -> int {
-            std::vector<int64_t> uoff((size_t)cnt + 1, 0);
-            for (int64_t q = 0; q < cnt; q++) { uoff[(size_t)q + 1] = uoff[(size_t)q] + bl[b + q]; }
+        // the sub-batch on the device (no return past the stager: it is joined below)
+        auto run_sub = [&]() -> int {
+            if (hipStreamWaitEvent(c.own_stream, c.ev_in[slot], 0) != hipSuccess) { set_err("hipStreamWaitEvent failed%s", ""); return GNX_EDEVICE; }
+            const uint8_t *da = (const uint8_t *)c.pin_a[slot].p, *db = j.b_dev ? j.b_dev : (const uint8_t *)c.pin_b[slot].p;
+            const int64_t *das = (const int64_t *)c.pin_as[slot].p, *dbs = (const int64_t *)c.pin_bs[slot].p;
+            int64_t *d_sc = (int64_t *)c.res_score.p + done, *d_en = j.want.end ? (int64_t *)c.res_end.p + done : nullptr, *d_st = j.want.start ? (int64_t *)c.res_start.p + done : nullptr;
+            bool packed = j.packed;
             int r;
-            if ((r = c.in_b.ensure((size_t)uoff[(size_t)cnt] + 64)) || (r = c.in_bl.ensure((size_t)(cnt + 1) * 8))) return r;
-            KParams ukp;
-            memset(&ukp, 0, sizeof(ukp));
-            ukp.b2 = (const unsigned *)c.ref.p; ukp.bflag = (const unsigned long long *)c.ref_flag.p; ukp.brank = (const unsigned *)c.ref_rank.p; ukp.bexc = (const unsigned long long *)c.ref_exc.p;
-            if (hipMemcpyAsync(c.in_bl.p, uoff.data(), (size_t)(cnt + 1) * 8, hipMemcpyHostToDevice, c.own_stream) != hipSuccess || hipStreamSynchronize(c.own_stream) != hipSuccess) { set_err("upload of the window table failed%s", ""); return GNX_EDEVICE; }
-            hipLaunchKernelGGL(unpack_windows_kernel, dim3((unsigned)cnt), dim3(256), 0, c.own_stream, ukp, dbs, (const int64_t *)c.in_bl.p, (int)cnt, (uint8_t *)c.in_b.p);
-            if (hipGetLastError() != hipSuccess) { set_err("unpack_windows_kernel failed to launch%s", ""); return GNX_EDEVICE; }
-            db = (const uint8_t *)c.in_b.p; dbs = (const int64_t *)c.in_bl.p; packed = false;
+            if (j.want.end && j.want.query_is_alpha) // (gnx_locate_batch_by_offset: the local sweep reads its target packed; only its fallback needs bytes)
+                r = locate_reads_in_windows(c, j.prm, cnt, da, das, al + b, db, dbs, bl + b, packed, d_sc, d_en, d_st, c.own_stream);
+            else {
+                // the windows as bytes (AffineGapLocal's transposed fast path reads the long sequence as the kernels' alpha; GNX_REF_UNPACK: A/B)
+                if (packed && (j.prm->mode == GNX_AFFINE_GAP_LOCAL || getenv("GNX_REF_UNPACK"))) {
+                    if ((r = unpack_ref_windows(c, dbs, bl + b, cnt, c.own_stream))) return r;
+                    db = (const uint8_t *)c.in_b.p; dbs = (const int64_t *)c.in_bl.p; packed = false;
+                }
+                PackedBeta pb(c, packed);
+                if (!j.want.cigars) r = score_or_fallback(c, j.prm, cnt, da, das, db, dbs, al + b, bl + b, d_sc, c.own_stream, d_en, true, d_st);
+                else r = run_sub_batch_cigars(c, n, done, cnt, total, c.own_stream, [&](int64_t *d_score, gnx_cigar *d_ops, int64_t cap, int64_t *d_off, int64_t *tot) {
+                    return run_device(j.prm, cnt, da, das, db, dbs, al + b, bl + b, d_score, d_ops, cap, d_off, tot, c.own_stream);
+                });
+            }
+            if (r) return r;
+            add_timing(tsum, c.timing, !j.want.cigars);
+            done += cnt;
             return GNX_OK;
         };
-        // (gnx_locate_batch_by_offset: the local sweep reads its target packed; only its fallback needs bytes)
-        if (packed && rc == GNX_OK && j.locate != 2 && (j.prm->mode == GNX_AFFINE_GAP_LOCAL || getenv("GNX_REF_UNPACK"))) rc = unpack_windows();
-        if (j.score_only && j.locate == 2 && rc == GNX_OK) { // alpha = queries, beta = targets: the sweep as it is, the ordinary route with the two swapped
-            int64_t *d_sc = (int64_t *)c.res_score.p + done, *d_en = (int64_t *)c.res_end.p + done, *d_st = j.span ? (int64_t *)c.res_start.p + done : nullptr;
-            c.beta_packed = packed;
-            rc = run_score_sweep(j.prm, cnt, (const uint8_t *)c.pin_a[slot].p, (const int64_t *)c.pin_as[slot].p, db, dbs, al + b, bl + b, d_sc, c.own_stream, d_en, true, d_st);
-            c.beta_packed = false;
-            if (rc == -1 && (!packed || (rc = unpack_windows()) == GNX_OK))
-                rc = score_or_fallback(c, j.prm, cnt, db, dbs, (const uint8_t *)c.pin_a[slot].p, (const int64_t *)c.pin_as[slot].p, bl + b, al + b, d_sc, c.own_stream, d_en, false, d_st);
-        } else if (j.score_only && rc == GNX_OK) {
-            c.beta_packed = packed;
-            rc = score_or_fallback(c, j.prm, cnt, (const uint8_t *)c.pin_a[slot].p, (const int64_t *)c.pin_as[slot].p, db, dbs, al + b, bl + b, (int64_t *)c.res_score.p + done, c.own_stream,
-                                   j.locate ? (int64_t *)c.res_end.p + done : nullptr, true, j.span ? (int64_t *)c.res_start.p + done : nullptr);
-            c.beta_packed = false;
-        }
-        for (int attempt = 0; rc == GNX_OK && !j.score_only; attempt++) {
-            const int64_t cap = (int64_t)(c.res_ops.cap / sizeof(gnx_cigar)) - total;
-            c.beta_packed = packed;
-            rc = run_device(j.prm, cnt, (const uint8_t *)c.pin_a[slot].p, (const int64_t *)c.pin_as[slot].p,
-                            db, dbs, al + b, bl + b,
-                            (int64_t *)c.res_score.p + done, (gnx_cigar *)c.res_ops.p + total, cap, (int64_t *)c.res_off.p + done, &tot, c.own_stream);
-            c.beta_packed = false;
-            if (rc != GNX_ECAPACITY || attempt >= 8) break;
-            // the reported total is exact (every sub-batch of the device flow is counted); leave room for the sub-batches to come
-            const int64_t left = (n - done + cnt - 1) / cnt;
-            rc = grow_ops(c, total, total + tot * std::min<int64_t>(left, 4) + 1024, c.own_stream);
-        }
-        if (rc == GNX_OK) {
-            tsum.fill_ms += c.timing.fill_ms; tsum.traceback_ms += c.timing.traceback_ms; tsum.total_ms += c.timing.total_ms; tsum.cells += c.timing.cells;
-            tsum.n_launches += c.timing.n_launches; tsum.trace_bytes += c.timing.trace_bytes; tsum.dominant_ms += c.timing.dominant_ms;
-            tsum.dominant_launches += c.timing.dominant_launches; tsum.fast_path = j.score_only ? std::max(tsum.fast_path, c.timing.fast_path) : c.timing.fast_path;
-            if (total > 0 && !j.score_only) { // offsets of a sub-batch start at 0
-                hipLaunchKernelGGL(add_offset_kernel, dim3((unsigned)((cnt + 1 + 255) / 256)), dim3(256), 0, c.own_stream, (int64_t *)c.res_off.p + done, cnt + 1, total);
-                if (hipGetLastError() != hipSuccess) { set_err("add_offset_kernel failed to launch%s", ""); rc = GNX_EDEVICE; }
-            }
-            total += tot; done += cnt;
-        }
+        rc = run_sub();
         if (stager.joinable()) stager.join();
         if (rc) return rc;
         if (stage_rc) { memcpy(g_err, stage_err, sizeof(stage_err)); publish_err(); return stage_rc; }
@@ -590,21 +639,16 @@ int ensure_reference(int nc) {
     return GNX_OK;
 }
 
-// The sharded host flow.  b_buf == nullptr: beta windows index the resident reference (gnx_set_reference).
-int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
-                     const uint8_t *a_buf, int64_t a_len_total, const int64_t *a_start, const int64_t *a_lens,
-                     const uint8_t *b_buf, int64_t b_len_total, const int64_t *b_start, const int64_t *b_lens,
-                     int64_t *out_score, gnx_cigar **out_ops, int64_t **out_ops_off, bool score_only = false, int64_t *out_end = nullptr, int locate_arg = 0,
-                     int64_t *out_start = nullptr) {
-    // locate_arg: 0 none; 1 / 2 gnx_locate_* (alpha = target / alpha = query); 3 / 4 gnx_locate_span_* with the same two roles
-    const bool span = locate_arg >= 3;
-    const int locate = span ? locate_arg - 2 : locate_arg;
+// The sharded host flow.  b.resident: beta windows index the resident reference (gnx_set_reference).
+int run_host_sharded(const gnx_params *prm, int64_t n_pairs, const SeqSide &a, const SeqSide &b, int64_t *out_score, gnx_cigar **out_ops, int64_t **out_ops_off,
+                     const HostWant &want = HostWant()) {
+    const bool score_only = !want.cigars, locate = want.end || want.start, span = want.start != nullptr, resident = b.resident;
+    int64_t b_len_total = b.buf_len;
     const auto t_entry = std::chrono::steady_clock::now();
-    if (!prm || n_pairs < 0 || !out_score || (!score_only && (!out_ops || !out_ops_off)) || a_len_total < 0 || b_len_total < 0) { set_err("bad argument%s", ""); return GNX_EINVAL; }
-    if (n_pairs > 0 && (!a_start || !a_lens || !b_start || !b_lens)) { set_err("null window table%s", ""); return GNX_EINVAL; }
-    if (locate && (!score_only || !out_end || (span && !out_start))) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (!prm || n_pairs < 0 || !out_score || (!score_only && (!out_ops || !out_ops_off)) || a.buf_len < 0 || b_len_total < 0) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (n_pairs > 0 && (!a.start || !a.len || !b.start || !b.len)) { set_err("null window table%s", ""); return GNX_EINVAL; }
+    if (locate && (!score_only || !want.end)) { set_err("bad argument%s", ""); return GNX_EINVAL; }
     if (locate && prm->mode != GNX_AFFINE_GAP_LOCAL) { set_err("gnx_locate_*: the mode must be GNX_AFFINE_GAP_LOCAL%s", ""); return GNX_EINVAL; }
-    const bool resident = (b_buf == nullptr);
     Ctx &c0 = ctx_at(0);
     int rc;
     { CtxScope sc(c0); if ((rc = ensure_init())) return rc; }
@@ -615,13 +659,13 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
     }
     long double sum_b = 0;
     for (int64_t p = 0; p < n_pairs; p++) {
-        if (a_start[p] < 0 || a_lens[p] < 0 || a_start[p] + a_lens[p] > a_len_total || b_start[p] < 0 || b_lens[p] < 0 || b_start[p] + b_lens[p] > b_len_total) {
+        if (a.start[p] < 0 || a.len[p] < 0 || a.start[p] + a.len[p] > a.buf_len || b.start[p] < 0 || b.len[p] < 0 || b.start[p] + b.len[p] > b_len_total) {
             set_err("window out of bounds at pair %s%lld", "", (long long)p); return GNX_EINVAL;
         }
-        sum_b += (long double)b_lens[p];
+        sum_b += (long double)b.len[p];
     }
     const int nc = std::max(1, std::min<int>(g_nctx, (int)std::max<int64_t>(n_pairs / 8, 1)));
-    const std::vector<int64_t> bounds = partition_by_cells(a_lens, b_lens, n_pairs, nc);
+    const std::vector<int64_t> bounds = partition_by_cells(a.len, b.len, n_pairs, nc);
     // a beta buffer that the pairs share (one chunk for every read; windows that overlap) goes to the devices whole -- once to
     // device 0, from there over RCCL; disjoint windows (one per pair) travel with their sub-batches instead
     const bool whole_b = !resident && b_len_total > 0 && (sum_b > 1.5L * (long double)b_len_total || b_len_total <= ((int64_t)16 << 20));
@@ -640,19 +684,16 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
             if ((rc = c.in_b.ensure((size_t)b_len_total + 16))) return rc;
             bdev[(size_t)d] = c.in_b.p;
         }
-        { CtxScope sc(c0); HIPCHK(hipSetDevice(c0.device)); HIPCHK(hipMemcpy(c0.in_b.p, b_buf, (size_t)b_len_total, hipMemcpyHostToDevice)); }
+        { CtxScope sc(c0); HIPCHK(hipSetDevice(c0.device)); HIPCHK(hipMemcpy(c0.in_b.p, b.buf, (size_t)b_len_total, hipMemcpyHostToDevice)); }
         if ((rc = broadcast_from_ctx0(c0.in_b.p, bdev, (size_t)b_len_total))) return rc;
     }
     std::vector<HostJob> jobs((size_t)nc);
     for (int d = 0; d < nc; d++) {
         HostJob &j = jobs[(size_t)d];
         j.c = &ctx_at(d); j.prm = prm; j.p0 = bounds[(size_t)d]; j.p1 = bounds[(size_t)d + 1];
-        j.a_buf = a_buf; j.a_start = a_start; j.a_len = a_lens; j.b_buf = b_buf; j.b_start = b_start; j.b_len = b_lens;
+        j.a = a; j.b = b; j.want = want;
         j.b_dev = (const uint8_t *)bdev[(size_t)d];
         j.packed = resident;
-        j.score_only = score_only;
-        j.locate = locate;
-        j.span = span;
     }
     auto work = [](HostJob *j) {
         CtxScope sc(*j->c);
@@ -769,8 +810,8 @@ int run_host_sharded(const gnx_params *prm, int64_t n_pairs,
     auto fetch = [&]() -> int {
         hipStream_t st = c0.own_stream;
         if (n_pairs) HIPCHK(hipMemcpyAsync(out_score, d_score, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
-        if (n_pairs && locate) HIPCHK(hipMemcpyAsync(out_end, nc > 1 ? c0.gat_end.p : c0.res_end.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
-        if (n_pairs && span) HIPCHK(hipMemcpyAsync(out_start, nc > 1 ? c0.gat_start.p : c0.res_start.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
+        if (n_pairs && locate) HIPCHK(hipMemcpyAsync(want.end, nc > 1 ? c0.gat_end.p : c0.res_end.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
+        if (n_pairs && span) HIPCHK(hipMemcpyAsync(want.start, nc > 1 ? c0.gat_start.p : c0.res_start.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
         if (total) HIPCHK(hipMemcpyAsync(ops, d_ops, (size_t)total * sizeof(gnx_cigar), hipMemcpyDeviceToHost, st));
         if (score_only) { /* only the score vector comes back */ }
         else if (nc == 1) HIPCHK(hipMemcpyAsync(off, d_off, (size_t)(n_pairs + 1) * 8, hipMemcpyDeviceToHost, st));
@@ -866,9 +907,7 @@ int run_best_of(const gnx_params *prm, int64_t n_reads, const uint8_t *read_cat,
             if (cand_len[q] > c.ref_len - cand_start[q]) { set_err("window out of bounds at candidate %s%lld", "", (long long)q); return GNX_EINVAL; }
     }
     hipStream_t st = c.own_stream;
-    int64_t sub = 131072;
-    if (const char *e = getenv("GNX_HOST_SUB")) sub = (std::max<int64_t>(atoll(e), 8) + 7) & ~(int64_t)7;
-    auto cut = [&](int64_t n) { const int64_t K0 = (n + sub - 1) / sub; return (((n + K0 - 1) / K0) + 7) & ~(int64_t)7; }; // equal sub-batches, whole waves (run_host_job)
+    const int64_t sub = gnx_host_sub(getenv("GNX_HOST_SUB"));
 
     // ---- host tables: per candidate its read as a window of [reads | reverse complements]; the reads that have candidates ----
     std::vector<int64_t> h_rs((size_t)n_cand), h_rlen((size_t)n_cand), win_read;
@@ -907,47 +946,23 @@ int run_best_of(const gnx_params *prm, int64_t n_reads, const uint8_t *read_cat,
         }
         HIPCHK(hipStreamSynchronize(st)); // (the sources are pageable memory of the caller and locals of this call: no return while a copy may still read them)
     }
-    // windows of the packed reference as bytes in c.in_b / c.in_bl (AffineGapLocal off the sweep reads its target as the kernels' alpha)
-    auto unpack = [&](const int64_t *d_starts, const int64_t *h_lens, int64_t cnt) -> int {
-        std::vector<int64_t> uoff((size_t)cnt + 1, 0);
-        for (int64_t q = 0; q < cnt; q++) uoff[(size_t)q + 1] = uoff[(size_t)q] + h_lens[q];
-        int r;
-        if ((r = c.in_b.ensure((size_t)uoff[(size_t)cnt] + 64)) || (r = c.in_bl.ensure((size_t)(cnt + 1) * 8))) return r;
-        KParams ukp;
-        memset(&ukp, 0, sizeof(ukp));
-        ukp.b2 = (const unsigned *)c.ref.p; ukp.bflag = (const unsigned long long *)c.ref_flag.p; ukp.brank = (const unsigned *)c.ref_rank.p; ukp.bexc = (const unsigned long long *)c.ref_exc.p;
-        HIPCHK(hipMemcpyAsync(c.in_bl.p, uoff.data(), (size_t)(cnt + 1) * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipStreamSynchronize(st)); // (uoff is a local)
-        hipLaunchKernelGGL(unpack_windows_kernel, dim3((unsigned)cnt), dim3(256), 0, st, ukp, d_starts, (const int64_t *)c.in_bl.p, (int)cnt, (uint8_t *)c.in_b.p);
-        HIPCHK(hipGetLastError());
-        return GNX_OK;
-    };
-
     // ---- score stage ----
     gnx_timing tsum = {};
     if (n_cand > 0) {
-        const int64_t size = cut(n_cand);
+        const int64_t size = sub_batch_size(n_cand, sub);
         for (int64_t b = 0; b < n_cand; b += size) {
             const int64_t cnt = std::min(size, n_cand - b);
             const int64_t *h_rl = h_rlen.data() + b, *h_wl = cand_len + b;
             int64_t *d_st = d_cstart ? d_cstart + b : nullptr;
             if (!local) { // alpha = the read or its reverse complement, beta = the window
-                c.beta_packed = resident;
+                PackedBeta pb(c, resident);
                 rc = score_or_fallback(c, prm, cnt, d_reads, d_rs + b, d_tbuf, d_ws + b, h_rl, h_wl, d_cscore + b, st);
-                c.beta_packed = false;
-            } else if (!resident) { // target (alpha) = the window, query (beta) = the read
+            } else if (!resident) // target (alpha) = the window, query (beta) = the read
                 rc = score_or_fallback(c, prm, cnt, d_tbuf, d_ws + b, d_reads, d_rs + b, h_wl, h_rl, d_cscore + b, st, d_cend + b, true, d_st);
-            } else { // the local sweep reads its target packed (the kernels' beta); only its fallback needs bytes
-                c.beta_packed = true;
-                rc = run_score_sweep(prm, cnt, d_reads, d_rs + b, d_tbuf, d_ws + b, h_rl, h_wl, d_cscore + b, st, d_cend + b, true, d_st);
-                c.beta_packed = false;
-                if (rc == -1 && (rc = unpack(d_ws + b, h_wl, cnt)) == GNX_OK)
-                    rc = score_or_fallback(c, prm, cnt, (const uint8_t *)c.in_b.p, (const int64_t *)c.in_bl.p, d_reads, d_rs + b, h_wl, h_rl, d_cscore + b, st, d_cend + b, false, d_st);
-            }
+            else // the local sweep reads its target packed (the kernels' beta); only its fallback needs bytes
+                rc = locate_reads_in_windows(c, prm, cnt, d_reads, d_rs + b, h_rl, d_tbuf, d_ws + b, h_wl, true, d_cscore + b, d_cend + b, d_st, st);
             if (rc) return rc;
-            tsum.fill_ms += c.timing.fill_ms; tsum.traceback_ms += c.timing.traceback_ms; tsum.total_ms += c.timing.total_ms; tsum.cells += c.timing.cells;
-            tsum.n_launches += c.timing.n_launches; tsum.trace_bytes += c.timing.trace_bytes; tsum.dominant_ms += c.timing.dominant_ms;
-            tsum.dominant_launches += c.timing.dominant_launches; tsum.fast_path = std::max(tsum.fast_path, c.timing.fast_path);
+            add_timing(tsum, c.timing, true);
         }
         if (pr) {
             PairSelectArgs pa{d_cscore, d_cstart, d_cend, d_ws, (const int64_t *)bo[BO_COFF].p, (const uint8_t *)bo[BO_STRAND].p, n_reads / 2, pr->o->min_insert, pr->o->max_insert,
@@ -980,35 +995,21 @@ int run_best_of(const gnx_params *prm, int64_t n_reads, const uint8_t *read_cat,
             w_rlen[(size_t)w] = read_off[r + 1] - read_off[r]; w_wlen[(size_t)w] = cand_len[cand_off[r] + h_best[(size_t)r]];
             worst += w_rlen[(size_t)w] + w_wlen[(size_t)w] + 1;
         }
-        const int64_t size = cut(n_win);
+        const int64_t size = sub_batch_size(n_win, sub);
         if ((rc = grow_ops(c, 0, std::max<int64_t>(std::min<int64_t>(worst, std::max<int64_t>((int64_t)1 << 20, 64 * std::min(n_win, size))), 1), st))) return rc;
         gnx_timing tal = {};
         for (int64_t b = 0; b < n_win; b += size) {
             const int64_t cnt = std::min(size, n_win - b);
             const int64_t *h_rl = w_rlen.data() + b, *h_wl = w_wlen.data() + b;
-            if (local && resident && (rc = unpack(d_ww + b, h_wl, cnt))) return rc; // only the winners' windows
-            int64_t tot = 0;
-            for (int attempt = 0;; attempt++) {
-                const int64_t cap = (int64_t)(c.res_ops.cap / sizeof(gnx_cigar)) - total;
-                int64_t *d_sc = (int64_t *)c.res_score.p + b, *d_off = (int64_t *)c.res_off.p + b;
-                gnx_cigar *d_ops = (gnx_cigar *)c.res_ops.p + total;
-                if (!local) {
-                    c.beta_packed = resident;
-                    rc = run_device(prm, cnt, d_reads, d_wr + b, d_tbuf, d_ww + b, h_rl, h_wl, d_sc, d_ops, cap, d_off, &tot, st);
-                    c.beta_packed = false;
-                } else if (resident) rc = run_device(prm, cnt, (const uint8_t *)c.in_b.p, (const int64_t *)c.in_bl.p, d_reads, d_wr + b, h_wl, h_rl, d_sc, d_ops, cap, d_off, &tot, st);
-                else rc = run_device(prm, cnt, d_tbuf, d_ww + b, d_reads, d_wr + b, h_wl, h_rl, d_sc, d_ops, cap, d_off, &tot, st);
-                if (rc != GNX_ECAPACITY || attempt >= 8) break;
-                const int64_t left = (n_win - b + cnt - 1) / cnt;
-                if ((rc = grow_ops(c, total, total + tot * std::min<int64_t>(left, 4) + 1024, st))) break;
-            }
+            if (local && resident && (rc = unpack_ref_windows(c, d_ww + b, h_wl, cnt, st))) return rc; // only the winners' windows
+            PackedBeta pb(c, !local && resident);
+            rc = run_sub_batch_cigars(c, n_win, b, cnt, total, st, [&](int64_t *d_sc, gnx_cigar *d_ops, int64_t cap, int64_t *d_off, int64_t *tot) {
+                if (!local) return run_device(prm, cnt, d_reads, d_wr + b, d_tbuf, d_ww + b, h_rl, h_wl, d_sc, d_ops, cap, d_off, tot, st);
+                if (resident) return run_device(prm, cnt, (const uint8_t *)c.in_b.p, (const int64_t *)c.in_bl.p, d_reads, d_wr + b, h_wl, h_rl, d_sc, d_ops, cap, d_off, tot, st);
+                return run_device(prm, cnt, d_tbuf, d_ww + b, d_reads, d_wr + b, h_wl, h_rl, d_sc, d_ops, cap, d_off, tot, st);
+            });
             if (rc) return rc;
             tal.total_ms += c.timing.total_ms;
-            if (total > 0) { // offsets of a sub-batch start at 0
-                hipLaunchKernelGGL(add_offset_kernel, dim3((unsigned)((cnt + 1 + 255) / 256)), dim3(256), 0, st, (int64_t *)c.res_off.p + b, cnt + 1, total);
-                HIPCHK(hipGetLastError());
-            }
-            total += tot;
         }
         tsum.total_ms += tal.total_ms;
     }
@@ -1083,13 +1084,7 @@ int run_best_of(const gnx_params *prm, int64_t n_reads, const uint8_t *read_cat,
 // caller's outputs before every kernel has succeeded.
 enum { SM_A, SM_B, SM_AS, SM_AL, SM_BS, SM_BL, SM_OPS, SM_OFF, SM_SC, SM_OUT, SM_NX, SM_XOFF, SM_XOPS, SM_MISC, SM_COUNT };
 static_assert(SM_COUNT == sizeof(Ctx::sm) / sizeof(DevBuf), "Ctx::sm holds one buffer per SM_* index");
-struct SumSide { // one sequence per pair: a window (start, len) of buf, or of the resident reference
-    const uint8_t *buf;
-    int64_t buf_len;
-    const int64_t *start, *len;
-    bool resident;
-};
-int run_summarize(const gnx_params *prm, int64_t n_pairs, const SumSide &sa, const SumSide &sb, const gnx_cigar *ops, const int64_t *ops_off,
+int run_summarize(const gnx_params *prm, int64_t n_pairs, const SeqSide &sa, const SeqSide &sb, const gnx_cigar *ops, const int64_t *ops_off,
                   gnx_aln_summary *out, gnx_cigar **out_xops, int64_t **out_xops_off) {
     const auto t_entry = std::chrono::steady_clock::now();
     // ---- argument checks: everything that needs no device ----
@@ -1102,7 +1097,7 @@ int run_summarize(const gnx_params *prm, int64_t n_pairs, const SumSide &sa, con
         if (ops_off[q + 1] < ops_off[q]) { set_err("decreasing ops_off at pair %s%lld", "", (long long)q); return GNX_EINVAL; }
     const int64_t n_runs = ops_off[n_pairs];
     if (n_runs > 0 && !ops) { set_err("null CIGAR array%s", ""); return GNX_EINVAL; }
-    for (const SumSide *s : {&sa, &sb})
+    for (const SeqSide *s : {&sa, &sb})
         for (int64_t q = 0; q < n_pairs; q++) {
             if (s->start[q] < 0 || s->len[q] < 0 || (!s->resident && s->len[q] > s->buf_len - s->start[q])) { set_err("window out of bounds at pair %s%lld", "", (long long)q); return GNX_EINVAL; }
             if (!s->resident && s->len[q] > 0 && !s->buf) { set_err("null sequence buffer%s", ""); return GNX_EINVAL; }
@@ -1129,7 +1124,7 @@ int run_summarize(const gnx_params *prm, int64_t n_pairs, const SumSide &sa, con
     g_transport = 0; g_bcast_ms = 0;
     if (sa.resident || sb.resident) {
         if (c.ref_len < 0) { set_err("no resident reference: call gnx_set_reference first%s", ""); return GNX_EINVAL; }
-        const SumSide &s = sa.resident ? sa : sb;
+        const SeqSide &s = sa.resident ? sa : sb;
         for (int64_t q = 0; q < n_pairs; q++)
             if (s.len[q] > c.ref_len - s.start[q]) { set_err("window out of bounds at pair %s%lld", "", (long long)q); return GNX_EINVAL; }
     }
@@ -1147,8 +1142,7 @@ int run_summarize(const gnx_params *prm, int64_t n_pairs, const SumSide &sa, con
     int64_t n_x = 0;
     std::vector<gnx_aln_summary> h_out((size_t)n_pairs);
     if (n_pairs > 0) {
-        int64_t sub = 131072;
-        if (const char *e = getenv("GNX_HOST_SUB")) sub = (std::max<int64_t>(atoll(e), 8) + 7) & ~(int64_t)7;
+        int64_t sub = gnx_host_sub(getenv("GNX_HOST_SUB"));
         if (const char *e = getenv("GNX_SUMMARY_SUB")) sub = std::max<int64_t>(atoll(e), 1);
         int cut = 64;
         if (const char *e = getenv("GNX_SUMMARY_FORM")) cut = e[0] == '0' ? 1 : e[0] == '1' ? 0x7fffffff : 64;
@@ -1162,7 +1156,7 @@ int run_summarize(const gnx_params *prm, int64_t n_pairs, const SumSide &sa, con
             SumArgs a;
             memset(&a, 0, sizeof(a));
             for (int side = 0; side < 2; side++) {
-                const SumSide &s = side ? sb : sa;
+                const SeqSide &s = side ? sb : sa;
                 KParams &k = a.kp;
                 if (s.resident) { k.b2 = (const unsigned *)c.ref.p; k.bflag = (const unsigned long long *)c.ref_flag.p; k.brank = (const unsigned *)c.ref_rank.p; k.bexc = (const unsigned long long *)c.ref_exc.p; }
                 else if (s.buf_len > 0) HIPCHK(hipMemcpyAsync(sm[side ? SM_B : SM_A].p, s.buf, (size_t)s.buf_len, hipMemcpyHostToDevice, st));

@@ -43,6 +43,65 @@ def test_pipelined_sub_batches(gpu_lib, monkeypatch):
         common.assert_same(gpu_lib.align_batch(pm, alphas, betas), oracle.align_batch(mode, MX["Default"], go, ge, alphas, betas, threads=8), "mode %d" % mode)
 
 
+def _many_runs_case(n_pairs, length=720):
+    """`n_pairs` copies of one ConstGap pair whose CIGAR is nearly all runs of length 1: alpha = AGAG.., beta = ATAT.., gaps free, a match
+    +1 and a mismatch never worth taking -- every A matches, every G and every T is a gap run of its own (1.5 runs per base).  The
+    oracle aligns the pair once; the batch's expected result is that CIGAR replicated."""
+    a1, b1 = np.tile(np.asarray([0, 2], np.uint8), length // 2), np.tile(np.asarray([0, 3], np.uint8), length // 2)
+    mx = np.full((5, 5), -1000, dtype=np.int64)
+    np.fill_diagonal(mx, 1)
+    s1, ops1, off1 = oracle.align_batch(oracle.MODE_CONST, mx, 0, 0, [a1], [b1])
+    per = int(off1[1])
+    exp = (np.repeat(s1, n_pairs), np.tile(ops1, n_pairs), np.arange(n_pairs + 1, dtype=np.int64) * per)
+    starts, lens = np.arange(n_pairs, dtype=np.int64) * length, np.full(n_pairs, length, dtype=np.int64)
+    return mx, np.tile(a1, n_pairs), np.tile(b1, n_pairs), starts, lens, per, exp
+
+
+def _first_sub_batch_that_grows(n, sub, per):
+    """the sub-batch (and the runs kept before it) at which the host flow's first CIGAR capacity guess, min(worst, max(2^20, 64 * min(n,
+    size))) runs, no longer holds the batch -- from the oracle's run count alone; None: the guess holds everything"""
+    k0 = (n + sub - 1) // sub
+    size = (((n + k0 - 1) // k0) + 7) & ~7
+    cap = max(1 << 20, 64 * min(n, size))
+    for b in range(0, n, size):
+        if (b + min(size, n - b)) * per > cap:
+            return b // size, b * per
+    return None
+
+
+def test_cigar_capacity_growth(gpu_lib, monkeypatch):
+    """The CIGAR buffer of a host call starts from a guess and is grown, with a retry of the sub-batch, when a sub-batch reports
+    GNX_ECAPACITY: with nothing to keep (the first sub-batch overflows: GNX_HOST_SUB unset and 1024) and with the runs of earlier
+    sub-batches to keep and the later offsets to rebase (GNX_HOST_SUB=256: the fourth sub-batch is the first that overflows).
+    The second leg reaches the same branch in the CIGAR stage of gnx_best_of_windows, one candidate per read."""
+    n = 2048
+    mx, a, b, starts, lens, per, exp = _many_runs_case(n)
+    # preconditions, from the oracle alone: the whole batch and the first sub-batch of 1024 pairs exceed the first guess of 2^20 runs
+    assert n * per > 1 << 20
+    assert _first_sub_batch_that_grows(n, 131072, per) == (0, 0)
+    assert 1024 * per > max(1 << 20, 64 * 1024) and _first_sub_batch_that_grows(n, 1024, per) == (0, 0)
+    k_keep, kept = _first_sub_batch_that_grows(n, 256, per)
+    assert k_keep > 0 and kept > 0  # a later sub-batch grows the buffer: earlier runs are kept
+    p = gpu_lib.make_params(gpu_lib.GNX_CONST_GAP, mx, 0)
+    monkeypatch.delenv("GNX_HOST_SUB", raising=False)
+    common.assert_same(gpu_lib.align_batch_windows(p, a, starts, lens, b, starts, lens), exp, "one sub-batch, nothing kept")
+    for sub in ("1024", "256"):
+        monkeypatch.setenv("GNX_HOST_SUB", sub)
+        common.assert_same(gpu_lib.align_batch_windows(p, a, starts, lens, b, starts, lens), exp, "sub " + sub)
+    # best-of, CIGARs asked for: every read has one candidate, so every read is a winner with the same CIGAR
+    m = 1024
+    assert m * per > 1 << 20 and _first_sub_batch_that_grows(m, 131072, per) == (0, 0) and _first_sub_batch_that_grows(m, 256, per)[0] > 0
+    read_off, cand_off = np.arange(m + 1, dtype=np.int64) * lens[0], np.arange(m + 1, dtype=np.int64)
+    for sub in (None, "256"):
+        if sub is None:
+            monkeypatch.delenv("GNX_HOST_SUB")
+        else:
+            monkeypatch.setenv("GNX_HOST_SUB", sub)
+        best, score, _, cand, ops, off = gpu_lib.best_of_windows(p, a[:m * lens[0]], read_off, b[:m * lens[0]], cand_off, starts[:m], lens[:m], np.zeros(m, np.uint8))
+        assert np.array_equal(best, np.zeros(m, np.int32)) and np.array_equal(cand, exp[0][:m]), "best-of sub %s" % sub
+        common.assert_same((score, ops, off), (exp[0][:m], exp[1][:m * per], exp[2][:m + 1]), "best-of sub %s" % sub)
+
+
 def test_sub_batches_with_reads_of_several_row_blocks(gpu_lib, monkeypatch):
     """the host entry point with reads of 100 .. 700 bases (1 .. 5 row blocks of the fast path, grouped per sub-batch) against windows
     of 800 .. 2500 bases: sub-batches, the CIGAR buffer retry, global and local mode"""
