@@ -313,6 +313,21 @@ int launch_scan(const int64_t *d_nops, int n, int64_t *d_off, int64_t *d_carry, 
     return GNX_OK;
 }
 
+// The end of a device call: the 64 bytes of `misc` read back behind everything queued on the stream -- word 0: the error flags, bytes 16 .. 23: the CIGAR runs the call needs
+int read_call_flags(Ctx &c, hipStream_t stream, int (&h_misc)[16], int64_t &total) {
+    HIPCHK(hipMemcpyAsync(h_misc, c.misc.p, 64, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    memcpy(&total, reinterpret_cast<char *>(h_misc) + 16, 8);
+    return GNX_OK;
+}
+// ... and the flags every driver reports alike: bit 1, 2, 4 of ef, in that order (bit 16, a strip that waited 5 s, is each driver's own: it runs again another way, or fails)
+int flag_error(int ef, int64_t total) {
+    if (ef & 1) { set_err("a base >= 5 was found: the reference would panic (index out of range)%s", ""); return GNX_EBASE; }
+    if (ef & 2) { set_err("unexpected traceback%s", ""); return GNX_ETRACE; }
+    if (ef & 4) { set_err("CIGAR buffer too small: need %s%lld elements", "", (long long)total); return GNX_ECAPACITY; }
+    return GNX_OK;
+}
+
 int run_device_fp(const gnx_params *prm, const KParams &kp, const TbParams &tp, int64_t n_pairs,
                   const uint8_t *d_a, const int64_t *d_as, const uint8_t *d_b, const int64_t *d_bs,
                   const int64_t *h_alen, const int64_t *h_blen, int rows_per_lane,
@@ -613,8 +628,8 @@ int run_device_fp(const gnx_params *prm, const KParams &kp, const TbParams &tp, 
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c.ev[3], stream));
     int h_misc[16];
-    HIPCHK(hipMemcpyAsync(h_misc, c.misc.p, 64, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
+    int64_t total;
+    if ((rc = read_call_flags(c, stream, h_misc, total))) return rc;
     float tot = 0, fa = 0;
     HIPCHK(hipEventElapsedTime(&tot, c.ev[0], c.ev[3]));
     HIPCHK(hipEventElapsedTime(&fa, c.ev[0], c.ev[1]));
@@ -624,13 +639,9 @@ int run_device_fp(const gnx_params *prm, const KParams &kp, const TbParams &tp, 
     c.timing.fill_ms += forward_ms + refill_ms; c.timing.traceback_ms += std::max(0.0, (double)tot - fa - refill_ms); c.timing.total_ms += tot;
     c.timing.cells += cells; c.timing.n_launches += 1; c.timing.trace_bytes += (int64_t)coff * 8 + (int64_t)roff * 4;
     c.timing.dominant_ms += forward_ms; c.timing.dominant_launches += 1; c.timing.fast_path = 1;
-    int64_t total;
-    memcpy(&total, reinterpret_cast<char *>(h_misc) + 16, 8);
     if (out_total) *out_total = total;
     const int ef = h_misc[0];
-    if (ef & 1) { set_err("a base >= 5 was found: the reference would panic (index out of range)%s", ""); return GNX_EBASE; }
-    if (ef & 2) { set_err("unexpected traceback%s", ""); return GNX_ETRACE; }
-    if (ef & 4) { set_err("CIGAR buffer too small: need %s%lld elements", "", (long long)total); return GNX_ECAPACITY; }
+    if ((rc = flag_error(ef, total))) return rc;
     if (ef & 8) {
         // some CIGARs have more than fp_cap(S) runs: their run counts (and so every offset) are right, their runs were not staged.
         // Align those pairs again on the general path and put the results in place; the batch goes back only if they are many.
@@ -692,20 +703,23 @@ int w64_farm_tiles(bool affine = false, int64_t n_pairs = 1 << 20) {
     return v <= 0 ? 0 : std::min(v, (int)FARM_MAX);
 }
 
-// Rows per lane of the affine 64-lane sweep (affine_long64.hip.h): call f with the compile-time constant of the instantiation
+// Launch selectors of the snapshot path: a run-time value of a small closed set becomes the compile-time constant of the instantiation, f is called with it
 template <typename F>
-void w64_rows_dispatch(int rw, F &&f) {
-    switch (rw) {
-    case 6: f(std::integral_constant<int, 6>{}); break;
-    case 8: f(std::integral_constant<int, 8>{}); break;
-    case 16: f(std::integral_constant<int, 16>{}); break;
-    default: f(std::integral_constant<int, R>{}); break;
-    }
+void bool_dispatch(bool v, F &&f) {
+    if (v) f(std::true_type{});
+    else f(std::false_type{});
 }
+template <int V0, int... Vs, typename F>
+void int_dispatch(int v, F &&f) { // (v is one of V0, Vs...; the last of them takes every other value)
+    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V0>{});
+    else if (v == V0) f(std::integral_constant<int, V0>{});
+    else int_dispatch<Vs...>(v, f);
+}
+// Rows per lane of the 64-lane sweeps and the farm: 6 / 8 / R / 16 for affine (affine_long64.hip.h), 4 / R for constant gap (const_long64.hip.h); f(AFF, RW)
 template <typename F>
-void w64c_rows_dispatch(int rw, F &&f) { // (the constant-gap twins: const_long64.hip.h)
-    if (rw == 4) f(std::integral_constant<int, 4>{});
-    else f(std::integral_constant<int, R>{});
+void rows_dispatch(bool affine, int rw, F &&f) {
+    if (affine) int_dispatch<6, 8, 16, R>(rw, [&](auto rwc) { f(std::true_type{}, rwc); });
+    else int_dispatch<4, R>(rw, [&](auto rwc) { f(std::false_type{}, rwc); });
 }
 constexpr int W64_ROWS[4] = {6, 8, R, 16};
 constexpr int W64C_ROWS[2] = {4, R};
@@ -746,6 +760,110 @@ int w64_pick_rows(const Ctx &c, bool affine, int64_t n_pairs, const int64_t *h_a
     return best_rw;
 }
 
+// int16 profile of the snapshot path: when every entry 4 (s - 2g) + 1 fits (half the LDS reads per step)
+bool snap_profile_fits_int16(const gnx_params *prm, bool affine) {
+    for (int x = 0; x < 25; x++) { const int64_t v = 4 * (prm->scores[x] - 2 * (affine ? prm->gap_extend : prm->gap_open)) + 1; if (v > 32767 || v < -32768) return false; }
+    return true;
+}
+
+// What a pair of the snapshot path keeps between its sweep and its walk, in the units its buffers are counted in
+struct SnapGeo {
+    int64_t HS, GS, rbw, ck, snw; // rows per strip, lanes per pair, row-buffer entry bytes, snapshot spacing (steps), dwords per lane and snapshot
+    bool rebase;
+    SnapGeo(bool affine, bool w64, int rw64, int64_t ck_, bool rebase_)
+        : HS(w64 ? (int64_t)G64 * rw64 : H), GS(w64 ? G64 : G), rbw(affine ? 8 : 4), ck(ck_), snw(affine ? (w64 ? al64_snapw(rw64) : AL_SNAPW) : (w64 ? cl64_snapw(rw64) : SNAPW)), rebase(rebase_) {}
+    int64_t strips(int64_t n) const { return (n + HS - 1) / HS; }
+    int64_t row_entries(int64_t strips, int64_t m) const { return (strips - 1) * (m + 1); }                // the bottom rows of all strips but the last
+    int64_t snap_dwords(int64_t strips, int64_t m) const { return (m + GS - 1) / ck * strips * GS * snw; } // a snapshot of the wavefront every ck steps
+    int64_t scratch_runs(int64_t n, int64_t m) const { return n + m + 2; }                                 // the walk's runs in traceback order
+    int64_t base_blocks(int64_t m) const { return rebase ? (((m + GS + 14) & ~(int64_t)15) / ck + 2) : 0; } // K-step blocks of a strip (REBASE: one int64 base each)
+    int64_t base_words(int64_t strips, int64_t m) const { return strips * base_blocks(m); }
+};
+
+// What the sweeps and the one-launch walks of the snapshot path take (const_long*.hip.h, affine_long*.hip.h)
+struct SnapArgs {
+    const PairPlan *plans; int np;
+    const uint8_t *a; const int64_t *as; const uint8_t *b; const int64_t *bs;
+    KParams kp; TbParams tp;
+    void *rows; // the row buffer: int2 entries for affine, int for constant gap
+    int *snap; int64_t *hfin; int64_t *score; int64_t *nops; gnx_cigar *scr; const int64_t *scr_off;
+    int *err;
+    const int2 *smap; int *sprog; // piped sweeps: strip map and progress words
+    long long *bases; MegaState *mst;
+};
+// ... and which instantiation a launch takes
+struct SnapSel {
+    bool affine, p16, rebase, w64;
+    bool piped, wg;  // sweep: strips piped through the row buffer; several of them per workgroup (cl_sweep_wg_kernel: constant gap, int16, not REBASE)
+    int rw;          // w64: rows per lane
+    int ckc;         // constant-gap one-workgroup walk: CKC / CKC_SMALL
+    int spec, wnp;   // ... without REBASE: tiles per round of cl_walk_spec_kernel (0: the plain walk), pairs per workgroup of the plain walk (with REBASE: 0, 1)
+    bool two_waves;  // w64 walk: the second wave that re-fills the tile to the left
+};
+constexpr int CLW_NW = 4; // strips per workgroup of cl_sweep_wg_kernel
+
+// The score-only sweep of one launch: `n_blocks` workgroups (strips, or items of CLW_NW strips); strips_max: the most strips of a pair (wg only)
+void launch_snap_sweep(const SnapSel &s, const SnapArgs &a, unsigned n_blocks, int strips_max, hipStream_t stream) {
+    const dim3 grid(n_blocks);
+    int *rb = static_cast<int *>(a.rows);
+    int2 *rb2 = static_cast<int2 *>(a.rows);
+    auto sweep = [&](auto kern, auto *rows) { hipLaunchKernelGGL(kern, grid, dim3(64), 0, stream, a.plans, a.np, a.a, a.as, a.b, a.bs, a.kp, rows, a.snap, a.hfin, a.err, a.smap, a.sprog, a.bases); };
+    if (s.wg) {
+        if (GNX_CLW_SENT) { // the item boundaries' rows start as "not written yet" (const_long_wg.hip.h)
+            const dim3 gfs((unsigned)std::max((strips_max + CLW_NW - 1) / CLW_NW, 1), (unsigned)a.np);
+            hipLaunchKernelGGL(clw_fill_sentinel_kernel, gfs, dim3(256), 0, stream, a.plans, a.np, CLW_NW, rb);
+        }
+        hipLaunchKernelGGL(cl_sweep_wg_kernel<CLW_NW>, grid, dim3(64 * CLW_NW), 0, stream, a.plans, a.np, a.a, a.as, a.b, a.bs, a.kp, rb, a.snap, a.hfin, a.err, a.smap, a.sprog);
+        return;
+    }
+    bool_dispatch(s.p16, [&](auto p16c) {
+        constexpr bool P16 = decltype(p16c)::value;
+        if (s.w64) rows_dispatch(s.affine, s.rw, [&](auto affc, auto rwc) {
+            constexpr int RW = decltype(rwc)::value;
+            if constexpr (decltype(affc)::value) sweep(al64_sweep_kernel<RW, P16>, rb2);
+            else sweep(cl64_sweep_kernel<RW, P16>, rb);
+        });
+        else bool_dispatch(s.rebase, [&](auto rbc) {
+            constexpr bool REBASE = decltype(rbc)::value;
+            if (s.affine) sweep(al_sweep_kernel<P16, REBASE>, rb2);
+            else if (s.piped) sweep(cl_sweep_kernel<P16, REBASE>, rb);
+            else hipLaunchKernelGGL((cl_sweep_flat_kernel<P16, REBASE>), grid, dim3(64), 0, stream, a.plans, a.np, a.a, a.as, a.b, a.bs, a.kp, rb, a.snap, a.hfin, a.err, a.bases);
+        });
+    });
+}
+
+// The walk of one launch on one workgroup per pair (or per 4 / wnp pairs: the 16-lane kernels); the farm's rounds: run_walk_farm
+void launch_snap_walk(const SnapSel &s, const SnapArgs &a, hipStream_t stream) {
+    const int *rb = static_cast<const int *>(a.rows);
+    const int2 *rb2 = static_cast<const int2 *>(a.rows);
+    const dim3 per_pair((unsigned)a.np);
+    auto walk = [&](auto kern, dim3 grid, int threads, auto *rows) {
+        hipLaunchKernelGGL(kern, grid, dim3(threads), 0, stream, a.plans, a.np, a.a, a.as, a.b, a.bs, a.kp, a.tp, rows, a.snap, a.hfin, a.score, a.nops, a.scr_off, a.scr, a.err, a.bases, a.mst);
+    };
+    bool_dispatch(s.p16, [&](auto p16c) {
+        constexpr bool P16 = decltype(p16c)::value;
+        if (s.w64 && s.affine) { // (two waves: the tile to the left re-filled by a second wave while the first re-fills the walk's: GNX_W64_SPEC=0 switches it off)
+            if (s.two_waves) walk(al64_walk2_kernel<P16>, per_pair, 128, rb2);
+            else walk(al64_walk_kernel<P16>, per_pair, 64, rb2);
+        } else if (s.w64) {
+            if (s.two_waves) walk(cl64_walk2_kernel<P16>, per_pair, 128, rb);
+            else walk(cl64_walk_kernel<P16>, per_pair, 64, rb);
+        } else if (s.affine) bool_dispatch(s.rebase, [&](auto rbc) { walk(al_walk_kernel<P16, decltype(rbc)::value>, dim3((unsigned)((a.np + 3) / 4)), 64, rb2); });
+        else int_dispatch<CKC, CKC_SMALL>(s.ckc, [&](auto ckc) {
+            constexpr int CK = decltype(ckc)::value;
+            if (s.spec) int_dispatch<2, 3, 4>(s.spec, [&](auto nsc) { // (two tiles per round: 24.6 / 42.5 KB of LDS, six / three workgroups per CU; three and four: run_device_clong)
+                hipLaunchKernelGGL((cl_walk_spec_kernel<P16, CK, decltype(nsc)::value>), per_pair, dim3(64), 0, stream, a.plans, a.np, a.a, a.as, a.b, a.bs, a.kp, a.tp, rb, a.snap, a.hfin, a.score, a.nops, a.scr_off, a.scr, a.err);
+            });
+            else bool_dispatch(s.rebase, [&](auto rbc) { int_dispatch<1, 2, 4>(s.wnp, [&](auto npc) {
+                constexpr bool REBASE = decltype(rbc)::value;
+                constexpr int NP = decltype(npc)::value;
+                // (REBASE walks one pair per workgroup; padding the workgroups' LDS so that a launch smaller than the GPU spreads over all CUs changes nothing: the dispatcher already does)
+                if constexpr (!REBASE || NP == 1) walk(cl_walk_kernel<P16, NP, CK, REBASE>, dim3((unsigned)((a.np + NP - 1) / NP)), 64, rb);
+            }); });
+        });
+    });
+}
+
 // The walk of the 64-lane snapshot path as rounds of {re-fill the tiles ahead of the walk on many CUs, walk them} (farm64.hip.h).
 // d_st: np MegaStates the caller has prepared (zeroed for a whole pair; the panel's state for row panels).  Launches rounds until every
 // pair's walk is over (or has left its panel): the first batch sized by the path's length, no host round trip inside a batch.
@@ -756,59 +874,49 @@ int run_walk_farm(Ctx &c, bool affine, bool p16, int np, int nt, const PairPlan 
     const int ckr = affine ? kp.ckc : 0; // (the affine sweep's snapshot spacing of this call, w64_farm_ck; the constant-gap tiles are CKC64 steps)
     const int rw = affine ? t_w64_r : t_w64_rc; // rows per lane of the sweep that wrote the snapshots (w64_pick_rows)
     size_t tile_dw = 0;
-    if (affine) w64_rows_dispatch(rw, [&](auto rwc) { tile_dw = (size_t)FarmGeo<true, decltype(rwc)::value>(ckr).tile_dw(); });
-    else w64c_rows_dispatch(rw, [&](auto rwc) { tile_dw = (size_t)FarmGeo<false, decltype(rwc)::value>(0).tile_dw(); });
+    unsigned *d_planes = nullptr;
+    FarmCtl *d_ctl = nullptr;
+    const dim3 gf((unsigned)nt, (unsigned)np), gw((unsigned)np), gr((unsigned)nt + 1, (unsigned)np);
+    // every launch of the farm, and the size of a tile's planes, through the one (AFF, RW, P16) selection
+    enum FarmStep { TILE_DW, INIT, FILL, ROUND, WALK };
+    auto farm = [&](FarmStep step, int par = 0) {
+        rows_dispatch(affine, rw, [&](auto affc, auto rwc) {
+            constexpr bool AFF = decltype(affc)::value;
+            constexpr int RW = decltype(rwc)::value;
+            if (step == TILE_DW) tile_dw = (size_t)FarmGeo<AFF, RW>(ckr).tile_dw();
+            else if (step == INIT) hipLaunchKernelGGL((farm_init_kernel<AFF, RW>), dim3((unsigned)((np + 63) / 64)), dim3(64), 0, stream, dpl, np, tp, d_st, d_ctl, nt, ckr);
+            else if (step == WALK) hipLaunchKernelGGL((farm_walk_kernel<AFF, RW>), gw, dim3(256), 0, stream, dpl, tp, dhf, d_score, dn, d_so, d_scr, d_err, d_st, d_ctl, d_planes, nt, ckr);
+            else bool_dispatch(p16, [&](auto p16c) {
+                constexpr bool P16 = decltype(p16c)::value;
+                if constexpr (AFF) {
+                    const int2 *rows = reinterpret_cast<const int2 *>(drb);
+                    if (step == FILL) hipLaunchKernelGGL((al64_farm_fill_kernel<RW, P16>), gf, dim3(64), 0, stream, dpl, d_a, d_as, d_b, d_bs, kp, rows, dsn, d_err, dbs, d_ctl, d_planes, par);
+                    else hipLaunchKernelGGL((al64_farm_round_kernel<RW, P16>), gr, dim3(256), 0, stream, dpl, d_a, d_as, d_b, d_bs, kp, tp, rows, dsn, dhf, d_score, dn, d_so, d_scr, d_err, dbs, d_st, d_ctl, d_planes, nt, par);
+                } else {
+                    const int *rows = reinterpret_cast<const int *>(drb);
+                    if (step == FILL) hipLaunchKernelGGL((cl64_farm_fill_kernel<RW, P16>), gf, dim3(64), 0, stream, dpl, d_a, d_as, d_b, d_bs, kp, rows, dsn, d_err, dbs, d_ctl, d_planes, par);
+                    else hipLaunchKernelGGL((cl64_farm_round_kernel<RW, P16>), gr, dim3(256), 0, stream, dpl, d_a, d_as, d_b, d_bs, kp, tp, rows, dsn, dhf, d_score, dn, d_so, d_scr, d_err, dbs, d_st, d_ctl, d_planes, nt, par);
+                }
+            });
+        });
+    };
+    farm(TILE_DW);
     const size_t planes_bytes = (size_t)np * 2 * FARM_MAX * tile_dw * 4;
     if ((rc = c.farm.ensure(planes_bytes + (size_t)np * sizeof(FarmCtl)))) return rc;
-    unsigned *d_planes = reinterpret_cast<unsigned *>(c.farm.p);
-    FarmCtl *d_ctl = reinterpret_cast<FarmCtl *>(reinterpret_cast<char *>(c.farm.p) + planes_bytes);
+    d_planes = reinterpret_cast<unsigned *>(c.farm.p);
+    d_ctl = reinterpret_cast<FarmCtl *>(reinterpret_cast<char *>(c.farm.p) + planes_bytes);
     const bool pipe = !(getenv("GNX_W64_FARM_PIPE") && getenv("GNX_W64_FARM_PIPE")[0] == '0'); // overlapped rounds (one launch each); 0: {fill, walk} launches
-    if (affine) w64_rows_dispatch(rw, [&](auto rwc) { hipLaunchKernelGGL((farm_init_kernel<true, decltype(rwc)::value>), dim3((unsigned)((np + 63) / 64)), dim3(64), 0, stream, dpl, np, tp, d_st, d_ctl, nt, ckr); });
-    else w64c_rows_dispatch(rw, [&](auto rwc) { hipLaunchKernelGGL((farm_init_kernel<false, decltype(rwc)::value>), dim3((unsigned)((np + 63) / 64)), dim3(64), 0, stream, dpl, np, tp, d_st, d_ctl, nt, 0); });
-    const dim3 gf((unsigned)nt, (unsigned)np), gw((unsigned)np), gr((unsigned)nt + 1, (unsigned)np);
-    const int2 *drb2 = reinterpret_cast<const int2 *>(drb);
-    const int *drb1 = reinterpret_cast<const int *>(drb);
-    auto launch_fill = [&](int par) {
-        if (affine) {
-            w64_rows_dispatch(rw, [&](auto rwc) {
-                constexpr int RW = decltype(rwc)::value;
-                if (p16) hipLaunchKernelGGL((al64_farm_fill_kernel<RW, true>), gf, dim3(64), 0, stream, dpl, d_a, d_as, d_b, d_bs, kp, drb2, dsn, d_err, dbs, d_ctl, d_planes, par);
-                else hipLaunchKernelGGL((al64_farm_fill_kernel<RW, false>), gf, dim3(64), 0, stream, dpl, d_a, d_as, d_b, d_bs, kp, drb2, dsn, d_err, dbs, d_ctl, d_planes, par);
-            });
-        } else {
-            w64c_rows_dispatch(rw, [&](auto rwc) {
-                constexpr int RW = decltype(rwc)::value;
-                if (p16) hipLaunchKernelGGL((cl64_farm_fill_kernel<RW, true>), gf, dim3(64), 0, stream, dpl, d_a, d_as, d_b, d_bs, kp, drb1, dsn, d_err, dbs, d_ctl, d_planes, par);
-                else hipLaunchKernelGGL((cl64_farm_fill_kernel<RW, false>), gf, dim3(64), 0, stream, dpl, d_a, d_as, d_b, d_bs, kp, drb1, dsn, d_err, dbs, d_ctl, d_planes, par);
-            });
-        }
-    };
-    auto launch_round = [&](int par) {
-        if (affine) {
-            w64_rows_dispatch(rw, [&](auto rwc) {
-                constexpr int RW = decltype(rwc)::value;
-                if (p16) hipLaunchKernelGGL((al64_farm_round_kernel<RW, true>), gr, dim3(256), 0, stream, dpl, d_a, d_as, d_b, d_bs, kp, tp, drb2, dsn, dhf, d_score, dn, d_so, d_scr, d_err, dbs, d_st, d_ctl, d_planes, nt, par);
-                else hipLaunchKernelGGL((al64_farm_round_kernel<RW, false>), gr, dim3(256), 0, stream, dpl, d_a, d_as, d_b, d_bs, kp, tp, drb2, dsn, dhf, d_score, dn, d_so, d_scr, d_err, dbs, d_st, d_ctl, d_planes, nt, par);
-            });
-        } else {
-            w64c_rows_dispatch(rw, [&](auto rwc) {
-                constexpr int RW = decltype(rwc)::value;
-                if (p16) hipLaunchKernelGGL((cl64_farm_round_kernel<RW, true>), gr, dim3(256), 0, stream, dpl, d_a, d_as, d_b, d_bs, kp, tp, drb1, dsn, dhf, d_score, dn, d_so, d_scr, d_err, dbs, d_st, d_ctl, d_planes, nt, par);
-                else hipLaunchKernelGGL((cl64_farm_round_kernel<RW, false>), gr, dim3(256), 0, stream, dpl, d_a, d_as, d_b, d_bs, kp, tp, drb1, dsn, dhf, d_score, dn, d_so, d_scr, d_err, dbs, d_st, d_ctl, d_planes, nt, par);
-            });
-        }
-    };
+    farm(INIT);
     int64_t batch = path_cells / ((int64_t)(affine ? ckr * 3 / 4 : 100) * nt) + 8; // (a diagonal crosses ~0.9 of a tile's steps; a round that finds the walk over costs a few us)
     std::vector<FarmCtl> h_ctl((size_t)np);
     int64_t rounds = 0;
-    if (pipe) launch_fill(0);
+    if (pipe) farm(FILL, 0);
     while (true) {
         for (int64_t r = 0; r < batch; r++) {
-            if (pipe) launch_round((int)((rounds + r) & 1));
+            if (pipe) farm(ROUND, (int)((rounds + r) & 1));
             else {
-                launch_fill(0);
-                if (affine) w64_rows_dispatch(rw, [&](auto rwc) { hipLaunchKernelGGL((farm_walk_kernel<true, decltype(rwc)::value>), gw, dim3(256), 0, stream, dpl, tp, dhf, d_score, dn, d_so, d_scr, d_err, d_st, d_ctl, d_planes, nt, ckr); });
-                else w64c_rows_dispatch(rw, [&](auto rwc) { hipLaunchKernelGGL((farm_walk_kernel<false, decltype(rwc)::value>), gw, dim3(256), 0, stream, dpl, tp, dhf, d_score, dn, d_so, d_scr, d_err, d_st, d_ctl, d_planes, nt, 0); });
+                farm(FILL, 0);
+                farm(WALK);
             }
         }
         rounds += batch;
@@ -838,18 +946,19 @@ int run_device_clong(const gnx_params *prm, const KParams &kp, const TbParams &t
     int rc;
     if (w64 && !rebase) w64 = false;
     const int rw64 = (w64 && w64_farm_tiles() > 0) ? (affine ? t_w64_r : t_w64_rc) : R; // rows per lane of the 64-lane kernels (the one-workgroup walks: R)
-    const int64_t HS = w64 ? (int64_t)G64 * rw64 : H, GS = w64 ? G64 : G; // rows per strip, lanes per pair
+    SnapGeo geo(affine, w64, rw64, 0, rebase); // (the snapshot spacing: below)
     // snapshot spacing of the constant-gap form (const_long.hip.h): the wide tiles only when the walk will have the GPU full of long chains
     int64_t ckc = CKC_SMALL;
     {
         int64_t strips_sum = 0;
-        for (int64_t p = 0; p < n_pairs; p++) strips_sum += (h_alen[p] + HS - 1) / HS;
+        for (int64_t p = 0; p < n_pairs; p++) strips_sum += geo.strips(h_alen[p]);
         if (n_pairs > 1536 && strips_sum >= 64 * n_pairs) ckc = CKC;
         if (const char *e = getenv("GNX_CL_CKC")) { const int v = atoi(e); if (v == CKC || v == CKC_SMALL) ckc = v; }
         if (w64) ckc = CKC64;
     }
     // affine snapshot spacing: CKA; the 64-lane sweep under the walk farm: wider (farm64.hip.h) -- a quarter of the snapshots to allocate and to write
     const int64_t ck_aff = (w64 && affine && w64_farm_tiles() > 0) ? t_w64_ck : CKA;
+    geo.ck = affine ? ck_aff : ckc;
     std::vector<PairPlan> plans((size_t)n_pairs);
     std::vector<int64_t> so((size_t)n_pairs + 1, 0); // staging offsets (runs), chunk-relative; so[chunk end] is unused
     std::vector<int64_t> chunk_begin{0};
@@ -857,16 +966,14 @@ int run_device_clong(const gnx_params *prm, const KParams &kp, const TbParams &t
     {
         int64_t rb = 0, sn = 0, sc = 0, bs = 0;
         int64_t budget = c.ws_limit - c.ws_limit / 16;
-        const int64_t rbw = affine ? 8 : 4, ck = affine ? ck_aff : ckc, snw = affine ? (w64 ? al64_snapw(rw64) : AL_SNAPW) : (w64 ? cl64_snapw(rw64) : SNAPW); // row-buffer entry bytes, snapshot spacing / dwords
-        auto bytes_of = [&](int64_t rb2, int64_t sn2, int64_t sc2, int64_t bs2) { return rbw * rb2 + 4 * sn2 + (int64_t)sizeof(gnx_cigar) * sc2 + 8 * bs2; };
-        auto nq_of = [&](int64_t m) { return rebase ? (((m + GS + 14) & ~(int64_t)15) / ck + 2) : 0; }; // K-step blocks of a strip (REBASE: one int64 base each)
+        auto bytes_of = [&](int64_t rb2, int64_t sn2, int64_t sc2, int64_t bs2) { return geo.rbw * rb2 + 4 * sn2 + (int64_t)sizeof(gnx_cigar) * sc2 + 8 * bs2; };
         // One pair that needs more than the workspace limit (a 1 Mb x 1 Mb pair: 50 GB of bottom rows + 43 GB of snapshots) is given what
         // the device has free, plus what these buffers already hold: the limit is there to leave room for other contexts' batches, and such a
         // pair cannot run any other way (the stored matrix would be 750 GB).
         int64_t one_max = 0;
         for (int64_t p = 0; p < n_pairs; p++) {
-            const int64_t n = h_alen[p], m = h_blen[p], strips = (n + HS - 1) / HS;
-            one_max = std::max(one_max, bytes_of((strips - 1) * (m + 1), (m + GS - 1) / ck * strips * GS * snw, n + m + 2, strips * nq_of(m)));
+            const int64_t n = h_alen[p], m = h_blen[p], strips = geo.strips(n);
+            one_max = std::max(one_max, bytes_of(geo.row_entries(strips, m), geo.snap_dwords(strips, m), geo.scratch_runs(n, m), geo.base_words(strips, m)));
         }
         if (one_max > budget) {
             size_t fr = 0, tot = 0;
@@ -878,8 +985,8 @@ int run_device_clong(const gnx_params *prm, const KParams &kp, const TbParams &t
         }
         for (int64_t p = 0; p < n_pairs; p++) {
             const int64_t n = h_alen[p], m = h_blen[p];
-            const int64_t strips = (n + HS - 1) / HS, ncp = (m + GS - 1) / ck;
-            const int64_t prb = (strips - 1) * (m + 1), psn = ncp * strips * GS * snw, psc = n + m + 2, pbs = strips * nq_of(m);
+            const int64_t strips = geo.strips(n);
+            const int64_t prb = geo.row_entries(strips, m), psn = geo.snap_dwords(strips, m), psc = geo.scratch_runs(n, m), pbs = geo.base_words(strips, m);
             if (bytes_of(prb, psn, psc, pbs) > budget) return -1;
             if (bytes_of(rb + prb, sn + psn, sc + psc, bs + pbs) > budget) { // new chunk, 4-aligned so that waves stay whole
                 int64_t cb = p & ~(int64_t)3;
@@ -888,13 +995,13 @@ int run_device_clong(const gnx_params *prm, const KParams &kp, const TbParams &t
                 for (int64_t q2 = cb; q2 < p; q2++) {
                     PairPlan &pq = plans[(size_t)q2];
                     pq.rowbuf_off = rb; pq.ckpt_off = sn; so[(size_t)q2] = sc; pq.hcol_off = q2 - cb; pq.src = (int32_t)(q2 - cb); pq.rowi_off = bs;
-                    rb += (int64_t)(pq.strips - 1) * (pq.m + 1); sn += (int64_t)((pq.m + GS - 1) / ck) * pq.strips * GS * snw; sc += (int64_t)pq.n + pq.m + 2; bs += (int64_t)pq.strips * pq.s_pitch;
+                    rb += geo.row_entries(pq.strips, pq.m); sn += geo.snap_dwords(pq.strips, pq.m); sc += geo.scratch_runs(pq.n, pq.m); bs += geo.base_words(pq.strips, pq.m);
                 }
                 chunk_begin.push_back(cb);
             }
             PairPlan &pl = plans[(size_t)p];
             pl.n = (int32_t)n; pl.m = (int32_t)m; pl.words = 0; pl.strips = (int32_t)strips;
-            pl.trace_off = 0; pl.dcol_off = 0; pl.col_off = 0; pl.rowi_off = bs; pl.s_off = 0; pl.s_pitch = nq_of(m);
+            pl.trace_off = 0; pl.dcol_off = 0; pl.col_off = 0; pl.rowi_off = bs; pl.s_off = 0; pl.s_pitch = geo.base_blocks(m);
             pl.rowbuf_off = rb; pl.ckpt_off = sn; so[(size_t)p] = sc;
             pl.hcol_off = p - chunk_begin.back(); pl.src = (int32_t)(p - chunk_begin.back());
             rb += prb; sn += psn; sc += psc; bs += pbs;
@@ -905,7 +1012,7 @@ int run_device_clong(const gnx_params *prm, const KParams &kp, const TbParams &t
     }
     int64_t max_np = 1;
     for (size_t ch = 0; ch + 1 < chunk_begin.size(); ch++) max_np = std::max(max_np, chunk_begin[ch + 1] - chunk_begin[ch]);
-    if ((rc = c.rowbuf.ensure((size_t)max_rb * (affine ? 8 : 4)))) return rc;
+    if ((rc = c.rowbuf.ensure((size_t)max_rb * geo.rbw))) return rc;
     if ((rc = c.fp_ckpt.ensure((size_t)max_sn * 4))) return rc;
     if ((rc = c.tb_scr.ensure((size_t)max_sc * sizeof(gnx_cigar)))) return rc;
     if ((rc = c.tb_scr_off.ensure(((size_t)n_pairs + 1) * 8))) return rc;
@@ -921,9 +1028,8 @@ int run_device_clong(const gnx_params *prm, const KParams &kp, const TbParams &t
     HIPCHK(hipMemcpyAsync(c.plans.p, plans.data(), (size_t)n_pairs * sizeof(PairPlan), hipMemcpyHostToDevice, stream));
     HIPCHK(hipMemcpyAsync(c.tb_scr_off.p, so.data(), ((size_t)n_pairs + 1) * 8, hipMemcpyHostToDevice, stream));
     HIPCHK(hipStreamSynchronize(stream)); // plans / so are locals
-    // int16 profile when every entry 4*(s - 2g) + 1 fits (half the LDS reads per step); GNX_CL_P16=0/1 overrides for A/B runs
-    bool p16 = true;
-    for (int x = 0; x < 25; x++) { const int64_t v = 4 * (prm->scores[x] - 2 * (affine ? prm->gap_extend : prm->gap_open)) + 1; if (v > 32767 || v < -32768) p16 = false; }
+    // GNX_CL_P16=0/1 overrides the int16-profile rule for A/B runs
+    bool p16 = snap_profile_fits_int16(prm, affine);
     if (getenv("GNX_CL_P16")) p16 = p16 && atoi(getenv("GNX_CL_P16")) != 0;
     double fill_ms = 0, tb_ms = 0;
     int64_t trace_bytes = 0;
@@ -934,19 +1040,19 @@ int run_device_clong(const gnx_params *prm, const KParams &kp, const TbParams &t
         const int np = (int)(e - b);
         if (np <= 0) continue;
         const PairPlan *dpl = reinterpret_cast<const PairPlan *>(c.plans.p) + b;
-        int *drb = reinterpret_cast<int *>(c.rowbuf.p), *dsn = reinterpret_cast<int *>(c.fp_ckpt.p);
+        int *dsn = reinterpret_cast<int *>(c.fp_ckpt.p);
         int64_t *dhf = reinterpret_cast<int64_t *>(c.hcol.p);
         long long *dbs = rebase ? reinterpret_cast<long long *>(c.cl_bases.p) : nullptr;
         int64_t *dn = reinterpret_cast<int64_t *>(c.nops.p) + b;
         const int64_t *d_so = reinterpret_cast<const int64_t *>(c.tb_scr_off.p) + b;
         gnx_cigar *d_scr = reinterpret_cast<gnx_cigar *>(c.tb_scr.p);
-        bool multi = false;
+        int strips_max = 0;
         int64_t m_maxc = 0;
-        for (int64_t q2 = b; q2 < e; q2++) { if (plans[(size_t)q2].strips > 1) multi = true; m_maxc = std::max<int64_t>(m_maxc, plans[(size_t)q2].m); }
+        for (int64_t q2 = b; q2 < e; q2++) { strips_max = std::max(strips_max, (int)plans[(size_t)q2].strips); m_maxc = std::max<int64_t>(m_maxc, plans[(size_t)q2].m); }
+        const bool multi = strips_max > 1;
         int64_t n_blocks = (np + 3) / 4;
         const bool piped = w64 || (multi && n_blocks < 3072 && m_maxc >= 8 * RB_PUB && !no_pipe());
         // constant gap, int16 profile: several strips per workgroup, rows handed over through LDS (cl_sweep_wg_kernel; GNX_CL_WG=0: one strip per workgroup)
-        constexpr int CLW_NW = 4;
         const bool wg = piped && !affine && p16 && !rebase && !(getenv("GNX_CL_WG") && atoi(getenv("GNX_CL_WG")) == 0);
         const int per_item = wg ? CLW_NW : 1;
         const int2 *d_smap = nullptr;
@@ -981,50 +1087,21 @@ int run_device_clong(const gnx_params *prm, const KParams &kp, const TbParams &t
         if (w64) { g_last_w64_r = rw64; g_last_w64_ck = affine ? ck_aff : ckc; }
         kps.rb_pub = n_blocks * per_item >= (int64_t)40 * c.n_cu ? 16 : RB_PUB; // (twice the wave slots of the piped sweep: 20 per CU)
         if (const char *e = getenv("GNX_CL_PUB")) { const int v = atoi(e); if (v == 16 || v == 32 || v == 64 || v == 128) kps.rb_pub = v; }
-        int2 *drb2 = reinterpret_cast<int2 *>(c.rowbuf.p);
-        const dim3 gridS((unsigned)n_blocks);
-#define GNX_AL_SWEEP(P_, RBS_) hipLaunchKernelGGL((al_sweep_kernel<P_, RBS_>), gridS, dim3(64), 0, stream, dpl, np, d_a, d_as + b, d_b, d_bs + b, kp, drb2, dsn, dhf, d_err, d_smap, d_sprog, dbs)
-#define GNX_CL_SWEEP(P_, RBS_) hipLaunchKernelGGL((cl_sweep_kernel<P_, RBS_>), gridS, dim3(64), 0, stream, dpl, np, d_a, d_as + b, d_b, d_bs + b, kps, drb, dsn, dhf, d_err, d_smap, d_sprog, dbs)
-#define GNX_CL_FLAT(P_, RBS_) hipLaunchKernelGGL((cl_sweep_flat_kernel<P_, RBS_>), gridS, dim3(64), 0, stream, dpl, np, d_a, d_as + b, d_b, d_bs + b, kps, drb, dsn, dhf, d_err, dbs)
+        SnapSel sel{};
+        sel.affine = affine; sel.p16 = p16; sel.rebase = rebase; sel.w64 = w64; sel.piped = piped; sel.wg = wg; sel.rw = rw64; sel.ckc = (int)ckc; sel.wnp = 1;
+        // (the sweeps: the affine 16-lane one takes the call's parameters, the 64-lane one its snapshot spacing, the constant-gap ones theirs and the publish interval; every walk: the call's)
+        SnapArgs sa{dpl, np, d_a, d_as + b, d_b, d_bs + b, affine ? (w64 ? kpa : kp) : kps, tp, c.rowbuf.p, dsn, dhf, d_score + b, dn, d_scr, d_so, d_err, d_smap, d_sprog, dbs, nullptr};
         if (rebase && !w64) HIPCHK(hipMemsetAsync(dbs, 0, (size_t)max_bs * 8, stream));
         if (w64) { // the 64-lane sweeps hand rows over without a progress word (affine_long64.hip.h, W64_SENT): row buffer and bases start as "not written yet", block 0 of every strip's bases as 0
             int64_t rb_used = 0, bs_used = 0;
-            for (int64_t q2 = b; q2 < e; q2++) { const PairPlan &pq = plans[(size_t)q2]; rb_used = std::max(rb_used, pq.rowbuf_off + (int64_t)(pq.strips - 1) * (pq.m + 1)); bs_used = std::max(bs_used, pq.rowi_off + (int64_t)pq.strips * pq.s_pitch); }
-            if (rb_used > 0) HIPCHK(hipMemsetAsync(c.rowbuf.p, 0x80, (size_t)rb_used * (affine ? 8 : 4), stream));
+            for (int64_t q2 = b; q2 < e; q2++) { const PairPlan &pq = plans[(size_t)q2]; rb_used = std::max(rb_used, pq.rowbuf_off + geo.row_entries(pq.strips, pq.m)); bs_used = std::max(bs_used, pq.rowi_off + geo.base_words(pq.strips, pq.m)); }
+            if (rb_used > 0) HIPCHK(hipMemsetAsync(c.rowbuf.p, 0x80, (size_t)rb_used * geo.rbw, stream));
             if (bs_used > 0) HIPCHK(hipMemsetAsync(dbs, 0x80, (size_t)bs_used * 8, stream));
             for (int64_t q2 = b; q2 < e; q2++) { const PairPlan &pq = plans[(size_t)q2]; HIPCHK(hipMemset2DAsync(dbs + pq.rowi_off, (size_t)pq.s_pitch * 8, 0, 8, (size_t)pq.strips, stream)); }
         }
-        if (w64 && !affine) {
-            w64c_rows_dispatch(rw64, [&](auto rwc) {
-                constexpr int RW = decltype(rwc)::value;
-                if (p16) hipLaunchKernelGGL((cl64_sweep_kernel<RW, true>), gridS, dim3(64), 0, stream, dpl, np, d_a, d_as + b, d_b, d_bs + b, kps, drb, dsn, dhf, d_err, d_smap, d_sprog, dbs);
-                else hipLaunchKernelGGL((cl64_sweep_kernel<RW, false>), gridS, dim3(64), 0, stream, dpl, np, d_a, d_as + b, d_b, d_bs + b, kps, drb, dsn, dhf, d_err, d_smap, d_sprog, dbs);
-            });
-        } else if (w64) {
-            w64_rows_dispatch(rw64, [&](auto rwc) {
-                constexpr int RW = decltype(rwc)::value;
-                if (p16) hipLaunchKernelGGL((al64_sweep_kernel<RW, true>), gridS, dim3(64), 0, stream, dpl, np, d_a, d_as + b, d_b, d_bs + b, kpa, drb2, dsn, dhf, d_err, d_smap, d_sprog, dbs);
-                else hipLaunchKernelGGL((al64_sweep_kernel<RW, false>), gridS, dim3(64), 0, stream, dpl, np, d_a, d_as + b, d_b, d_bs + b, kpa, drb2, dsn, dhf, d_err, d_smap, d_sprog, dbs);
-            });
-        } else if (affine) { if (rebase) { if (p16) GNX_AL_SWEEP(true, true); else GNX_AL_SWEEP(false, true); } else { if (p16) GNX_AL_SWEEP(true, false); else GNX_AL_SWEEP(false, false); } }
-        else if (wg) {
-            if (GNX_CLW_SENT) { // the item boundaries' rows start as "not written yet" (const_long_wg.hip.h)
-                int smax_all = 0;
-                for (int64_t q2 = b; q2 < e; q2++) smax_all = std::max(smax_all, (int)plans[(size_t)q2].strips);
-                const dim3 gfs((unsigned)std::max((smax_all + CLW_NW - 1) / CLW_NW, 1), (unsigned)np);
-                hipLaunchKernelGGL(clw_fill_sentinel_kernel, gfs, dim3(256), 0, stream, dpl, np, CLW_NW, drb);
-            }
-            hipLaunchKernelGGL(cl_sweep_wg_kernel<CLW_NW>, gridS, dim3(64 * CLW_NW), 0, stream, dpl, np, d_a, d_as + b, d_b, d_bs + b, kps, drb, dsn, dhf, d_err, d_smap, d_sprog);
-        }
-        else if (piped) { if (rebase) { if (p16) GNX_CL_SWEEP(true, true); else GNX_CL_SWEEP(false, true); } else { if (p16) GNX_CL_SWEEP(true, false); else GNX_CL_SWEEP(false, false); } }
-        else { if (rebase) { if (p16) GNX_CL_FLAT(true, true); else GNX_CL_FLAT(false, true); } else { if (p16) GNX_CL_FLAT(true, false); else GNX_CL_FLAT(false, false); } }
-#undef GNX_AL_SWEEP
-#undef GNX_CL_SWEEP
-#undef GNX_CL_FLAT
+        launch_snap_sweep(sel, sa, (unsigned)n_blocks, strips_max, stream);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(c.ev[2], stream));
-        const dim3 gridW((unsigned)((np + 3) / 4));
-#define GNX_AL_WALK(P_, RBS_) hipLaunchKernelGGL((al_walk_kernel<P_, RBS_>), gridW, dim3(64), 0, stream, dpl, np, d_a, d_as + b, d_b, d_bs + b, kp, tp, drb2, dsn, dhf, d_score + b, dn, d_so, d_scr, d_err, dbs, (MegaState *)nullptr)
         const int farm_nt = w64 ? w64_farm_tiles(affine, np) : 0;
         if (farm_nt > 0) { // the walk as rounds of tiles re-filled ahead of it on many CUs (farm64.hip.h)
             int64_t path = 0;
@@ -1032,70 +1109,23 @@ int run_device_clong(const gnx_params *prm, const KParams &kp, const TbParams &t
             if ((rc = c.mega_state.ensure(256 + (size_t)np * sizeof(MegaState)))) return rc;
             MegaState *d_fst = reinterpret_cast<MegaState *>(reinterpret_cast<char *>(c.mega_state.p) + 256);
             HIPCHK(hipMemsetAsync(d_fst, 0, (size_t)np * sizeof(MegaState), stream));
-            if ((rc = run_walk_farm(c, affine, p16, (int)np, farm_nt, dpl, d_a, d_as + b, d_b, d_bs + b, kpa, tp, affine ? (const void *)drb2 : (const void *)drb, dsn, dhf, d_score + b, dn, d_so, d_scr, d_err, dbs, d_fst, path / 2, stream))) return rc;
-        } else if (w64 && !affine) { // one pair per workgroup
-            const dim3 gw((unsigned)np);
-            if (w64_two_waves()) {
-                if (p16) hipLaunchKernelGGL((cl64_walk2_kernel<true>), gw, dim3(128), 0, stream, dpl, np, d_a, d_as + b, d_b, d_bs + b, kp, tp, drb, dsn, dhf, d_score + b, dn, d_so, d_scr, d_err, dbs, (MegaState *)nullptr);
-                else hipLaunchKernelGGL((cl64_walk2_kernel<false>), gw, dim3(128), 0, stream, dpl, np, d_a, d_as + b, d_b, d_bs + b, kp, tp, drb, dsn, dhf, d_score + b, dn, d_so, d_scr, d_err, dbs, (MegaState *)nullptr);
-            }
-            else if (p16) hipLaunchKernelGGL((cl64_walk_kernel<true>), gw, dim3(64), 0, stream, dpl, np, d_a, d_as + b, d_b, d_bs + b, kp, tp, drb, dsn, dhf, d_score + b, dn, d_so, d_scr, d_err, dbs, (MegaState *)nullptr);
-            else hipLaunchKernelGGL((cl64_walk_kernel<false>), gw, dim3(64), 0, stream, dpl, np, d_a, d_as + b, d_b, d_bs + b, kp, tp, drb, dsn, dhf, d_score + b, dn, d_so, d_scr, d_err, dbs, (MegaState *)nullptr);
-        } else if (w64) {
-            const dim3 gw((unsigned)np);
-            if (w64_two_waves()) { // (the tile to the left re-filled by a second wave while the first re-fills the walk's: GNX_W64_SPEC=0 switches it off)
-                if (p16) hipLaunchKernelGGL((al64_walk2_kernel<true>), gw, dim3(128), 0, stream, dpl, np, d_a, d_as + b, d_b, d_bs + b, kp, tp, drb2, dsn, dhf, d_score + b, dn, d_so, d_scr, d_err, dbs, (MegaState *)nullptr);
-                else hipLaunchKernelGGL((al64_walk2_kernel<false>), gw, dim3(128), 0, stream, dpl, np, d_a, d_as + b, d_b, d_bs + b, kp, tp, drb2, dsn, dhf, d_score + b, dn, d_so, d_scr, d_err, dbs, (MegaState *)nullptr);
-            }
-            else if (p16) hipLaunchKernelGGL((al64_walk_kernel<true>), gw, dim3(64), 0, stream, dpl, np, d_a, d_as + b, d_b, d_bs + b, kp, tp, drb2, dsn, dhf, d_score + b, dn, d_so, d_scr, d_err, dbs, (MegaState *)nullptr);
-            else hipLaunchKernelGGL((al64_walk_kernel<false>), gw, dim3(64), 0, stream, dpl, np, d_a, d_as + b, d_b, d_bs + b, kp, tp, drb2, dsn, dhf, d_score + b, dn, d_so, d_scr, d_err, dbs, (MegaState *)nullptr);
-        } else if (affine) { if (rebase) { if (p16) GNX_AL_WALK(true, true); else GNX_AL_WALK(false, true); } else { if (p16) GNX_AL_WALK(true, false); else GNX_AL_WALK(false, false); } }
-#undef GNX_AL_WALK
-        else if (rebase) { // (one pair per workgroup, plain walk)
-            const dim3 gw((unsigned)np);
-#define GNX_CL_WALKR(P_, CK_) hipLaunchKernelGGL((cl_walk_kernel<P_, 1, CK_, true>), gw, dim3(64), 0, stream, dpl, np, d_a, d_as + b, d_b, d_bs + b, kp, tp, drb, dsn, dhf, d_score + b, dn, d_so, d_scr, d_err, dbs, (MegaState *)nullptr)
-            if (ckc == CKC) { if (p16) GNX_CL_WALKR(true, CKC); else GNX_CL_WALKR(false, CKC); }
-            else { if (p16) GNX_CL_WALKR(true, CKC_SMALL); else GNX_CL_WALKR(false, CKC_SMALL); }
-#undef GNX_CL_WALKR
+            if ((rc = run_walk_farm(c, affine, p16, (int)np, farm_nt, dpl, d_a, d_as + b, d_b, d_bs + b, kpa, tp, c.rowbuf.p, dsn, dhf, d_score + b, dn, d_so, d_scr, d_err, dbs, d_fst, path / 2, stream))) return rc;
         } else {
-            // pairs per walk workgroup: GNX_CL_WALK_NP = 1 / 2 / 4 (default 1, see cl_walk_kernel)
-            const char *npe = getenv("GNX_CL_WALK_NP");
-            const int wnp = (npe && (npe[0] == '2' || npe[0] == '4')) ? npe[0] - '0' : 1;
-            const dim3 gw((unsigned)((np + wnp - 1) / wnp));
-            // (padding the workgroups' LDS so that a launch smaller than the GPU spreads over all CUs changes nothing: the dispatcher already does)
-            auto launch_walk = [&](auto kern) {
-                hipLaunchKernelGGL(kern, gw, dim3(64), 0, stream, dpl, np, d_a, d_as + b, d_b, d_bs + b, kp, tp, drb, dsn, dhf, d_score + b, dn, d_so, d_scr, d_err, (const long long *)nullptr, (MegaState *)nullptr);
-            };
-            const bool wide = ckc == CKC;
-            // speculative re-fills of the next tiles by the wave's other lane groups (cl_walk_spec_kernel): GNX_CL_WALK_SPEC = 0 / 3 / 4 tiles per round
-            // Three tiles per round while every pair of the launch is resident at once (33.6 KB of LDS: four workgroups per CU) and the walk is a
-            // latency chain: 1024 pairs of C5 37.9 -> 28.6 ms.  With more pairs than that the plain walk's eight workgroups per CU win
-            // (2048 pairs, 448-step tiles: 42 ms plain, 111 ms speculative), and four tiles per round (three workgroups per CU) never pay.
-            int spec = (np <= 4 * c.n_cu && !wide) ? 3 : 0;
-            if (const char *se = getenv("GNX_CL_WALK_SPEC")) { const int v = atoi(se); spec = (v == 2 || v == 3 || v == 4) ? v : 0; }
-            if (npe) spec = 0; // (an explicit GNX_CL_WALK_NP asks for the plain walk)
-            const dim3 gs((unsigned)np);
-            auto launch_spec = [&](auto kern) {
-                hipLaunchKernelGGL(kern, gs, dim3(64), 0, stream, dpl, np, d_a, d_as + b, d_b, d_bs + b, kp, tp, drb, dsn, dhf, d_score + b, dn, d_so, d_scr, d_err);
-            };
-            if (spec == 2) { // two tiles per round: 24.6 / 42.5 KB of LDS, six / three workgroups per CU
-                if (p16) { if (wide) launch_spec(cl_walk_spec_kernel<true, CKC, 2>); else launch_spec(cl_walk_spec_kernel<true, CKC_SMALL, 2>); }
-                else { if (wide) launch_spec(cl_walk_spec_kernel<false, CKC, 2>); else launch_spec(cl_walk_spec_kernel<false, CKC_SMALL, 2>); }
-            } else if (spec && p16) {
-                if (spec == 3) { if (wide) launch_spec(cl_walk_spec_kernel<true, CKC, 3>); else launch_spec(cl_walk_spec_kernel<true, CKC_SMALL, 3>); }
-                else { if (wide) launch_spec(cl_walk_spec_kernel<true, CKC, 4>); else launch_spec(cl_walk_spec_kernel<true, CKC_SMALL, 4>); }
-            } else if (spec) {
-                if (spec == 3) { if (wide) launch_spec(cl_walk_spec_kernel<false, CKC, 3>); else launch_spec(cl_walk_spec_kernel<false, CKC_SMALL, 3>); }
-                else { if (wide) launch_spec(cl_walk_spec_kernel<false, CKC, 4>); else launch_spec(cl_walk_spec_kernel<false, CKC_SMALL, 4>); }
-            } else if (p16) {
-                if (wnp == 1) { if (wide) launch_walk(cl_walk_kernel<true, 1, CKC>); else launch_walk(cl_walk_kernel<true, 1, CKC_SMALL>); }
-                else if (wnp == 2) { if (wide) launch_walk(cl_walk_kernel<true, 2, CKC>); else launch_walk(cl_walk_kernel<true, 2, CKC_SMALL>); }
-                else { if (wide) launch_walk(cl_walk_kernel<true, 4, CKC>); else launch_walk(cl_walk_kernel<true, 4, CKC_SMALL>); }
-            } else {
-                if (wnp == 1) { if (wide) launch_walk(cl_walk_kernel<false, 1, CKC>); else launch_walk(cl_walk_kernel<false, 1, CKC_SMALL>); }
-                else if (wnp == 2) { if (wide) launch_walk(cl_walk_kernel<false, 2, CKC>); else launch_walk(cl_walk_kernel<false, 2, CKC_SMALL>); }
-                else { if (wide) launch_walk(cl_walk_kernel<false, 4, CKC>); else launch_walk(cl_walk_kernel<false, 4, CKC_SMALL>); }
+            sa.kp = kp;
+            if (w64) sel.two_waves = w64_two_waves();
+            else if (!affine && !rebase) { // (REBASE: one pair per workgroup, plain walk)
+                // pairs per walk workgroup: GNX_CL_WALK_NP = 1 / 2 / 4 (default 1, see cl_walk_kernel)
+                const char *npe = getenv("GNX_CL_WALK_NP");
+                sel.wnp = (npe && (npe[0] == '2' || npe[0] == '4')) ? npe[0] - '0' : 1;
+                // speculative re-fills of the next tiles by the wave's other lane groups (cl_walk_spec_kernel): GNX_CL_WALK_SPEC = 0 / 3 / 4 tiles per round
+                // Three tiles per round while every pair of the launch is resident at once (33.6 KB of LDS: four workgroups per CU) and the walk is a
+                // latency chain: 1024 pairs of C5 37.9 -> 28.6 ms.  With more pairs than that the plain walk's eight workgroups per CU win
+                // (2048 pairs, 448-step tiles: 42 ms plain, 111 ms speculative), and four tiles per round (three workgroups per CU) never pay.
+                sel.spec = (np <= 4 * c.n_cu && ckc != CKC) ? 3 : 0;
+                if (const char *se = getenv("GNX_CL_WALK_SPEC")) { const int v = atoi(se); sel.spec = (v == 2 || v == 3 || v == 4) ? v : 0; }
+                if (npe) sel.spec = 0; // (an explicit GNX_CL_WALK_NP asks for the plain walk)
             }
+            launch_snap_walk(sel, sa, stream);
         }
         HIPCHK(hipGetLastError());
         if ((rc = launch_scan(dn, np, d_ops_off + b, d_carry, stream))) return rc;
@@ -1109,23 +1139,21 @@ int run_device_clong(const gnx_params *prm, const KParams &kp, const TbParams &t
         fill_ms += f1; tb_ms += f2;
         for (int64_t p = b; p < e; p++) {
             const PairPlan &pl = plans[(size_t)p];
-            trace_bytes += (affine ? 8 : 4) * (int64_t)(pl.strips - 1) * (pl.m + 1) + 4 * (int64_t)((pl.m + GS - 1) / (affine ? ck_aff : ckc)) * pl.strips * GS * (affine ? (w64 ? al64_snapw(rw64) : AL_SNAPW) : (w64 ? cl64_snapw(rw64) : SNAPW));
+            trace_bytes += geo.rbw * geo.row_entries(pl.strips, pl.m) + 4 * geo.snap_dwords(pl.strips, pl.m);
         }
     }
     HIPCHK(hipEventRecord(c.ev[2], stream));
     int h_misc[16];
-    HIPCHK(hipMemcpyAsync(h_misc, c.misc.p, 64, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
+    int64_t total;
+    if ((rc = read_call_flags(c, stream, h_misc, total))) return rc;
     float tot = 0;
     HIPCHK(hipEventElapsedTime(&tot, c.ev[0], c.ev[2]));
     c.timing.fill_ms = fill_ms; c.timing.traceback_ms = tb_ms; c.timing.total_ms = tot;
     c.timing.cells = cells; c.timing.n_launches = (int64_t)nchunks; c.timing.trace_bytes = trace_bytes;
     c.timing.dominant_ms = fill_ms; c.timing.dominant_launches = (int64_t)nchunks; c.timing.fast_path = w64 ? 6 : 2;
-    int64_t total;
-    memcpy(&total, reinterpret_cast<char *>(h_misc) + 16, 8);
     if (out_total) *out_total = total;
     const int ef = h_misc[0];
-    if (ef & 1) { set_err("a base >= 5 was found: the reference would panic (index out of range)%s", ""); return GNX_EBASE; }
+    if (ef & 1) return flag_error(1, total);
     if (ef & 16) {
         if (t_no_pipe) { set_err("a strip waited more than 5 s for the strip above it%s", ""); return GNX_EDEVICE; }
         if (getenv("GNX_DEBUG")) fprintf(stderr, "[gnx] a pipelined strip timed out: the call runs again with sequential strips\n");
@@ -1134,9 +1162,7 @@ int run_device_clong(const gnx_params *prm, const KParams &kp, const TbParams &t
         t_no_pipe = false;
         return rc;
     }
-    if (ef & 2) { set_err("unexpected traceback%s", ""); return GNX_ETRACE; }
-    if (ef & 4) { set_err("CIGAR buffer too small: need %s%lld elements", "", (long long)total); return GNX_ECAPACITY; }
-    return GNX_OK;
+    return flag_error(ef & 6, total);
 }
 
 // Pairs whose snapshot working set (bottom rows of all strips + snapshots: 20 B per column and strip for AffineGap) exceeds the workspace:
@@ -1153,7 +1179,6 @@ int run_device_mega(const gnx_params *prm, const KParams &kp, const TbParams &tp
     Ctx &c = g_ctx;
     int rc;
     const int rw64 = (w64 && w64_farm_tiles() > 0) ? (affine ? t_w64_r : t_w64_rc) : R; // rows per lane of the 64-lane kernels (the one-workgroup walks: R)
-    const int64_t HS = w64 ? (int64_t)G64 * rw64 : H, GS = w64 ? G64 : G; // rows per strip, lanes per pair (w64: affine_long64.hip.h / const_long64.hip.h)
     const int np = (int)n_pairs;
     // Snapshot spacing of the affine 64-lane sweep in row panels: what a backward panel holds per strip is its bottom row (8 B per column) + its snapshots
     // (4 (2 RW + 2) / K B per column and lane), and the strips that fit the budget are the waves that sweep: 5 Mb x 5 Mb at RW = 16, K = 512: 814 strips a
@@ -1166,9 +1191,12 @@ int run_device_mega(const gnx_params *prm, const KParams &kp, const TbParams &tp
         if (const char *e = getenv("GNX_W64_CK_MEGA")) { const int v = atoi(e); if (v == 128 || v == 256 || v == 512 || v == 1024 || v == 2048) want = v; }
         for (int v = want; v >= CKA; v >>= 1) if ((int64_t)((int64_t)G64 * rw64 + G64 + v + 64) * step4 < ((int64_t)1 << 28)) { ck_mega = v; break; }
     }
-    const int64_t ck = affine ? ((w64 && w64_farm_tiles() > 0) ? ck_mega : CKA) : CKC_SMALL, snw = affine ? (w64 ? al64_snapw(rw64) : AL_SNAPW) : (w64 ? cl64_snapw(rw64) : SNAPW), rbw = affine ? 8 : 4;
-    bool p16 = true;
-    for (int x = 0; x < 25; x++) { const int64_t v = 4 * (prm->scores[x] - 2 * (affine ? prm->gap_extend : prm->gap_open)) + 1; if (v > 32767 || v < -32768) p16 = false; }
+    const int64_t ck = affine ? ((w64 && w64_farm_tiles() > 0) ? ck_mega : CKA) : CKC_SMALL;
+    const SnapGeo geo(affine, w64, rw64, ck, true);
+    const int64_t HS = geo.HS, rbw = geo.rbw; // rows per strip (w64: affine_long64.hip.h / const_long64.hip.h), row-buffer entry bytes
+    const bool p16 = snap_profile_fits_int16(prm, affine); // (GNX_CL_P16, run_device_clong's A/B override of this rule, is not read here: row panels always take the rule's answer)
+    SnapSel sel{}; // the REBASE kernels, piped strips; constant gap: the narrow tiles, one pair per walk workgroup
+    sel.affine = affine; sel.p16 = p16; sel.rebase = true; sel.w64 = w64; sel.piped = true; sel.rw = rw64; sel.ckc = CKC_SMALL; sel.wnp = 1;
     std::vector<int64_t> so((size_t)np + 1, 0), h_start((size_t)np * 2);
     int64_t m_hi = 1;
     for (int64_t p = 0; p < n_pairs; p++) {
@@ -1176,9 +1204,9 @@ int run_device_mega(const gnx_params *prm, const KParams &kp, const TbParams &tp
         so[(size_t)p + 1] = so[(size_t)p] + h_alen[p] + h_blen[p] + 2;
         m_hi = std::max(m_hi, h_blen[p]);
     }
-    const int64_t nq_hi = ((m_hi + GS + 14) & ~(int64_t)15) / ck + 2;
-    const int64_t strip_fwd_hi = (m_hi + 1) * rbw + nq_hi * 8;                                   // forward pass: bottom row + bases
-    const int64_t strip_bwd_hi = strip_fwd_hi + ((m_hi + GS - 1) / ck) * GS * snw * 4;                 // backward pass: + snapshots
+    const int64_t nq_hi = geo.base_blocks(m_hi);
+    const int64_t strip_fwd_hi = (m_hi + 1) * rbw + nq_hi * 8;                // forward pass: bottom row + bases
+    const int64_t strip_bwd_hi = strip_fwd_hi + geo.snap_dwords(1, m_hi) * 4; // backward pass: + snapshots
     const int64_t scr_b = so[(size_t)np] * (int64_t)sizeof(gnx_cigar);
     // such a pair cannot run any other way: it is given what the device has free (plus what these buffers hold already), not the workspace
     // limit that leaves room for other contexts' batches -- strips in flight are what keeps the device busy (400 strips: a quarter of it)
@@ -1200,7 +1228,7 @@ int run_device_mega(const gnx_params *prm, const KParams &kp, const TbParams &tp
     {
         int64_t n_hi = 1;
         for (int64_t p = 0; p < n_pairs; p++) n_hi = std::max(n_hi, h_alen[p]);
-        const int64_t strips_hi = (n_hi + HS - 1) / HS, top_hi = (m_hi + 1) * rbw + nq_hi * 8;
+        const int64_t strips_hi = geo.strips(n_hi), top_hi = (m_hi + 1) * rbw + nq_hi * 8;
         int64_t tops = 16 * top_hi;
         for (int pass = 0; pass < 3; pass++) {
             const int64_t b2 = budget - tops - tops / 8;
@@ -1248,7 +1276,7 @@ int run_device_mega(const gnx_params *prm, const KParams &kp, const TbParams &tp
         // 0.5 s faster and take 1.4 s longer to allocate in a process's first call)
         // ... unless whole rounds of the SIMDs fit: a launch is paced by the SIMD that holds most strips (one wave each), so 2 048 strips cost what 1 628 do -- panels of
         // k x 1 024 strips and one remainder panel (5 Mb x 5 Mb at 1 024-row strips: 2 048 + 2 048 + 787 instead of 3 x 1 628), when the remainder is not a sliver
-        const int64_t total_strips = (n + HS - 1) / HS, simds = 4 * (int64_t)c.n_cu;
+        const int64_t total_strips = geo.strips(n), simds = 4 * (int64_t)c.n_cu;
         int64_t n_bwd = (total_strips + Sb_max - 1) / Sb_max, Sb_pick = (total_strips + n_bwd - 1) / n_bwd;
         if (w64 && Sb_max >= simds && total_strips > Sb_max) {
             const int64_t Sq = Sb_max / simds * simds, rem = total_strips % Sq;
@@ -1257,7 +1285,7 @@ int run_device_mega(const gnx_params *prm, const KParams &kp, const TbParams &tp
         const int64_t Sb = forced_panels ? Sb_max : Sb_pick;
         if (forced_panels) n_bwd = (total_strips + Sb_max - 1) / Sb_max;
         const int64_t Sf = forced_panels ? Sf_max : std::max(Sb, std::min<int64_t>(Sf_max, std::max<int64_t>(Sb, 9 * c.n_cu)) / Sb * Sb);
-        const int64_t nq = ((m + GS + 14) & ~(int64_t)15) / ck + 2; // K-step blocks of a strip: the pitch of the bases, the same in every panel
+        const int64_t nq = geo.base_blocks(m); // K-step blocks of a strip: the pitch of the bases, the same in every panel
         const int64_t top_b = (m + 1) * rbw + nq * 8;           // one saved boundary: the row + its bases
         if ((rc = c.mega_rows.ensure((size_t)(n_bwd * top_b)))) return rc;
         char *tops = reinterpret_cast<char *>(c.mega_rows.p); // tops[b]: the row above backward panel b (b >= 1)
@@ -1272,7 +1300,7 @@ int run_device_mega(const gnx_params *prm, const KParams &kp, const TbParams &tp
             pl.n = (int32_t)(rows + virt); pl.m = (int32_t)mcols; pl.words = 0; pl.strips = (int32_t)planned;
             pl.trace_off = 0; pl.dcol_off = 0; pl.col_off = 0; pl.s_off = 0; pl.rowbuf_off = 0; pl.ckpt_off = 0;
             pl.hcol_off = (forward && last) ? 0 : 1; pl.src = 0; pl.rowi_off = 0; pl.s_pitch = nq;
-            const int64_t rb_e = (planned - 1) * (mcols + 1), sn_e = forward ? 0 : ((mcols + GS - 1) / ck) * planned * GS * snw, bs_e = planned * nq;
+            const int64_t rb_e = geo.row_entries(planned, mcols), sn_e = forward ? 0 : geo.snap_dwords(planned, mcols), bs_e = planned * nq;
             int r2;
             if (getenv("GNX_DEBUG")) {
                 size_t fr = 0, tot = 0;
@@ -1319,31 +1347,9 @@ int run_device_mega(const gnx_params *prm, const KParams &kp, const TbParams &tp
             KParams kps = kp;
             kps.ckc = (int)ck; kps.rb_pub = RB_PUB;
             if (w64) { g_last_w64_r = rw64; g_last_w64_ck = ck; }
-            const dim3 gridS((unsigned)local);
             HIPCHK(hipEventRecord(c.ev[1], stream));
-            if (w64 && !affine) {
-                int *drb = reinterpret_cast<int *>(ar_rows);
-                w64c_rows_dispatch(rw64, [&](auto rwc) {
-                    constexpr int RW = decltype(rwc)::value;
-                    if (p16) hipLaunchKernelGGL((cl64_sweep_kernel<RW, true>), gridS, dim3(64), 0, stream, dpl, 1, d_a, d_starts, d_b, d_starts + 1, kps, drb, dsn, dhf, d_err, d_smap, d_sprog, dbs);
-                    else hipLaunchKernelGGL((cl64_sweep_kernel<RW, false>), gridS, dim3(64), 0, stream, dpl, 1, d_a, d_starts, d_b, d_starts + 1, kps, drb, dsn, dhf, d_err, d_smap, d_sprog, dbs);
-                });
-            } else if (w64) {
-                int2 *drb2 = reinterpret_cast<int2 *>(ar_rows);
-                w64_rows_dispatch(rw64, [&](auto rwc) {
-                    constexpr int RW = decltype(rwc)::value;
-                    if (p16) hipLaunchKernelGGL((al64_sweep_kernel<RW, true>), gridS, dim3(64), 0, stream, dpl, 1, d_a, d_starts, d_b, d_starts + 1, kps, drb2, dsn, dhf, d_err, d_smap, d_sprog, dbs);
-                    else hipLaunchKernelGGL((al64_sweep_kernel<RW, false>), gridS, dim3(64), 0, stream, dpl, 1, d_a, d_starts, d_b, d_starts + 1, kps, drb2, dsn, dhf, d_err, d_smap, d_sprog, dbs);
-                });
-            } else if (affine) {
-                int2 *drb2 = reinterpret_cast<int2 *>(ar_rows);
-                if (p16) hipLaunchKernelGGL((al_sweep_kernel<true, true>), gridS, dim3(64), 0, stream, dpl, 1, d_a, d_starts, d_b, d_starts + 1, kps, drb2, dsn, dhf, d_err, d_smap, d_sprog, dbs);
-                else hipLaunchKernelGGL((al_sweep_kernel<false, true>), gridS, dim3(64), 0, stream, dpl, 1, d_a, d_starts, d_b, d_starts + 1, kps, drb2, dsn, dhf, d_err, d_smap, d_sprog, dbs);
-            } else {
-                int *drb = reinterpret_cast<int *>(ar_rows);
-                if (p16) hipLaunchKernelGGL((cl_sweep_kernel<true, true>), gridS, dim3(64), 0, stream, dpl, 1, d_a, d_starts, d_b, d_starts + 1, kps, drb, dsn, dhf, d_err, d_smap, d_sprog, dbs);
-                else hipLaunchKernelGGL((cl_sweep_kernel<false, true>), gridS, dim3(64), 0, stream, dpl, 1, d_a, d_starts, d_b, d_starts + 1, kps, drb, dsn, dhf, d_err, d_smap, d_sprog, dbs);
-            }
+            const SnapArgs sa{dpl, 1, d_a, d_starts, d_b, d_starts + 1, kps, tp, ar_rows, dsn, dhf, nullptr, nullptr, nullptr, nullptr, d_err, d_smap, d_sprog, dbs, nullptr}; // (a sweep: nothing of the walk's)
+            launch_snap_sweep(sel, sa, (unsigned)local, 0, stream);
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(c.ev[2], stream));
             launches++;
@@ -1364,7 +1370,7 @@ int run_device_mega(const gnx_params *prm, const KParams &kp, const TbParams &tp
         };
         { // the arena: the biggest launch of the forward pass (rows + bases of Sf + 2 strips) or of the backward pass (+ snapshots, Sb + 2 strips)
             const int64_t lf = std::min(Sf, total_strips) + 2, lb = std::min(Sb, total_strips) + 2;
-            const int64_t need_f = lf * (m + 1) * rbw + lf * nq * 8 + 1024, need_b = lb * (m + 1) * rbw + lb * nq * 8 + ((m + GS - 1) / ck) * lb * GS * snw * 4 + 1024;
+            const int64_t need_f = lf * (m + 1) * rbw + lf * nq * 8 + 1024, need_b = lb * (m + 1) * rbw + lb * nq * 8 + geo.snap_dwords(lb, m) * 4 + 1024;
             if ((rc = c.mega_arena.ensure((size_t)std::max(need_f, need_b)))) return rc;
         }
         for (int64_t s0 = 0; s0 < total_strips; s0 += Sf) if ((rc = sweep_rows(s0, std::min(Sf, total_strips - s0), m, true))) return rc; // forward
@@ -1385,8 +1391,8 @@ int run_device_mega(const gnx_params *prm, const KParams &kp, const TbParams &tp
             if (st.resume) { st.wi = pl.n; st.wj = (int32_t)jcur; }
             HIPCHK(hipMemcpyAsync(d_st, &st, sizeof(st), hipMemcpyHostToDevice, stream));
             const PairPlan *dpl = reinterpret_cast<const PairPlan *>(c.plans.p);
-            const long long *dbs = reinterpret_cast<const long long *>(ar_bases);
-            const int *dsn = reinterpret_cast<const int *>(ar_snap);
+            long long *dbs = reinterpret_cast<long long *>(ar_bases);
+            int *dsn = reinterpret_cast<int *>(ar_snap);
             int64_t *d_tmp_score = dhf + 2; // (the walk writes hfin[pl.hcol_off] here when it ends: not the pair's score, see above)
             HIPCHK(hipEventRecord(c.ev[1], stream));
             const int farm_nt = w64 ? w64_farm_tiles(affine, 1) : 0;
@@ -1395,30 +1401,10 @@ int run_device_mega(const gnx_params *prm, const KParams &kp, const TbParams &tp
                 kpf.ckc = (int)ck;
                 if ((rc = run_walk_farm(c, affine, p16, 1, farm_nt, dpl, d_a, d_starts, d_b, d_starts + 1, kpf, tp, ar_rows, dsn, dhf, d_tmp_score, dn + p, d_so + p, d_scr, d_err, dbs, d_st,
                                         std::min<int64_t>((int64_t)pl.n + jcur, 2 * (int64_t)pl.n) / 2, stream))) return rc;
-            } else if (w64 && !affine) {
-                const int *drb = reinterpret_cast<const int *>(ar_rows);
-                if (w64_two_waves()) {
-                    if (p16) hipLaunchKernelGGL((cl64_walk2_kernel<true>), dim3(1), dim3(128), 0, stream, dpl, 1, d_a, d_starts, d_b, d_starts + 1, kp, tp, drb, dsn, dhf, d_tmp_score, dn + p, d_so + p, d_scr, d_err, dbs, d_st);
-                    else hipLaunchKernelGGL((cl64_walk2_kernel<false>), dim3(1), dim3(128), 0, stream, dpl, 1, d_a, d_starts, d_b, d_starts + 1, kp, tp, drb, dsn, dhf, d_tmp_score, dn + p, d_so + p, d_scr, d_err, dbs, d_st);
-                }
-                else if (p16) hipLaunchKernelGGL((cl64_walk_kernel<true>), dim3(1), dim3(64), 0, stream, dpl, 1, d_a, d_starts, d_b, d_starts + 1, kp, tp, drb, dsn, dhf, d_tmp_score, dn + p, d_so + p, d_scr, d_err, dbs, d_st);
-                else hipLaunchKernelGGL((cl64_walk_kernel<false>), dim3(1), dim3(64), 0, stream, dpl, 1, d_a, d_starts, d_b, d_starts + 1, kp, tp, drb, dsn, dhf, d_tmp_score, dn + p, d_so + p, d_scr, d_err, dbs, d_st);
-            } else if (w64) {
-                const int2 *drb2 = reinterpret_cast<const int2 *>(ar_rows);
-                if (w64_two_waves()) {
-                    if (p16) hipLaunchKernelGGL((al64_walk2_kernel<true>), dim3(1), dim3(128), 0, stream, dpl, 1, d_a, d_starts, d_b, d_starts + 1, kp, tp, drb2, dsn, dhf, d_tmp_score, dn + p, d_so + p, d_scr, d_err, dbs, d_st);
-                    else hipLaunchKernelGGL((al64_walk2_kernel<false>), dim3(1), dim3(128), 0, stream, dpl, 1, d_a, d_starts, d_b, d_starts + 1, kp, tp, drb2, dsn, dhf, d_tmp_score, dn + p, d_so + p, d_scr, d_err, dbs, d_st);
-                }
-                else if (p16) hipLaunchKernelGGL((al64_walk_kernel<true>), dim3(1), dim3(64), 0, stream, dpl, 1, d_a, d_starts, d_b, d_starts + 1, kp, tp, drb2, dsn, dhf, d_tmp_score, dn + p, d_so + p, d_scr, d_err, dbs, d_st);
-                else hipLaunchKernelGGL((al64_walk_kernel<false>), dim3(1), dim3(64), 0, stream, dpl, 1, d_a, d_starts, d_b, d_starts + 1, kp, tp, drb2, dsn, dhf, d_tmp_score, dn + p, d_so + p, d_scr, d_err, dbs, d_st);
-            } else if (affine) {
-                const int2 *drb2 = reinterpret_cast<const int2 *>(ar_rows);
-                if (p16) hipLaunchKernelGGL((al_walk_kernel<true, true>), dim3(1), dim3(64), 0, stream, dpl, 1, d_a, d_starts, d_b, d_starts + 1, kp, tp, drb2, dsn, dhf, d_tmp_score, dn + p, d_so + p, d_scr, d_err, dbs, d_st);
-                else hipLaunchKernelGGL((al_walk_kernel<false, true>), dim3(1), dim3(64), 0, stream, dpl, 1, d_a, d_starts, d_b, d_starts + 1, kp, tp, drb2, dsn, dhf, d_tmp_score, dn + p, d_so + p, d_scr, d_err, dbs, d_st);
             } else {
-                const int *drb = reinterpret_cast<const int *>(ar_rows);
-                if (p16) hipLaunchKernelGGL((cl_walk_kernel<true, 1, CKC_SMALL, true>), dim3(1), dim3(64), 0, stream, dpl, 1, d_a, d_starts, d_b, d_starts + 1, kp, tp, drb, dsn, dhf, d_tmp_score, dn + p, d_so + p, d_scr, d_err, dbs, d_st);
-                else hipLaunchKernelGGL((cl_walk_kernel<false, 1, CKC_SMALL, true>), dim3(1), dim3(64), 0, stream, dpl, 1, d_a, d_starts, d_b, d_starts + 1, kp, tp, drb, dsn, dhf, d_tmp_score, dn + p, d_so + p, d_scr, d_err, dbs, d_st);
+                if (w64) sel.two_waves = w64_two_waves();
+                const SnapArgs sa{dpl, 1, d_a, d_starts, d_b, d_starts + 1, kp, tp, ar_rows, dsn, dhf, d_tmp_score, dn + p, d_scr, d_so + p, d_err, nullptr, nullptr, dbs, d_st};
+                launch_snap_walk(sel, sa, stream);
             }
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(c.ev[2], stream));
@@ -1446,20 +1432,16 @@ int run_device_mega(const gnx_params *prm, const KParams &kp, const TbParams &tp
         HIPCHK(hipStreamSynchronize(stream)); // (pls is a local)
     }
     int h_misc[16];
-    HIPCHK(hipMemcpyAsync(h_misc, c.misc.p, 64, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
+    int64_t total;
+    if ((rc = read_call_flags(c, stream, h_misc, total))) return rc;
     c.timing.fill_ms = fill_ms; c.timing.traceback_ms = tb_ms; c.timing.total_ms = fill_ms + tb_ms;
     c.timing.cells = cells; c.timing.n_launches = launches; c.timing.trace_bytes = ws_bytes;
     c.timing.dominant_ms = fill_ms; c.timing.dominant_launches = launches; c.timing.fast_path = 5;
-    int64_t total;
-    memcpy(&total, reinterpret_cast<char *>(h_misc) + 16, 8);
     if (out_total) *out_total = total;
     const int ef = h_misc[0];
-    if (ef & 1) { set_err("a base >= 5 was found: the reference would panic (index out of range)%s", ""); return GNX_EBASE; }
+    if (ef & 1) return flag_error(1, total);
     if (ef & 16) { set_err("a strip waited more than 5 s for the strip above it%s", ""); return GNX_EDEVICE; }
-    if (ef & 2) { set_err("unexpected traceback%s", ""); return GNX_ETRACE; }
-    if (ef & 4) { set_err("CIGAR buffer too small: need %s%lld elements", "", (long long)total); return GNX_ECAPACITY; }
-    return GNX_OK;
+    return flag_error(ef & 6, total);
 }
 
 // The latency geometry (lat_fill.hip.h): one pair per wave, 64 lanes x 2 rows, the strips of a pair as piped workgroups; one wave per pair
@@ -1572,23 +1554,19 @@ int run_device_lat(const gnx_params *prm, const KParams &kp, const TbParams &tp,
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c.ev[2], stream));
     int h_misc[16];
-    HIPCHK(hipMemcpyAsync(h_misc, c.misc.p, 64, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
+    int64_t total;
+    if ((rc = read_call_flags(c, stream, h_misc, total))) return rc;
     float f1 = 0, f2 = 0;
     HIPCHK(hipEventElapsedTime(&f1, c.ev[0], c.ev[1]));
     HIPCHK(hipEventElapsedTime(&f2, c.ev[1], c.ev[2]));
     c.timing.fill_ms = f1; c.timing.traceback_ms = f2; c.timing.total_ms = f1 + f2;
     c.timing.cells = cells; c.timing.n_launches = 1; c.timing.trace_bytes = toff * 16;
     c.timing.dominant_ms = f1; c.timing.dominant_launches = 1; c.timing.fast_path = wide ? 4 : 3;
-    int64_t total;
-    memcpy(&total, reinterpret_cast<char *>(h_misc) + 16, 8);
     if (out_total) *out_total = total;
     const int ef = h_misc[0];
-    if (ef & 1) { set_err("a base >= 5 was found: the reference would panic (index out of range)%s", ""); return GNX_EBASE; }
+    if (ef & 1) return flag_error(1, total);
     if (ef & 16) { if (getenv("GNX_DEBUG")) fprintf(stderr, "[gnx] a strip of the latency geometry timed out: the call runs again on the general path\n"); return -2; }
-    if (ef & 2) { set_err("unexpected traceback%s", ""); return GNX_ETRACE; }
-    if (ef & 4) { set_err("CIGAR buffer too small: need %s%lld elements", "", (long long)total); return GNX_ECAPACITY; }
-    return GNX_OK;
+    return flag_error(ef & 6, total);
 }
 
 // The device flow shared by all entry points.  All pointers are device pointers except h_*.
@@ -2142,18 +2120,16 @@ int run_device(const gnx_params *prm, int64_t n_pairs,
     }
     HIPCHK(hipEventRecord(c.ev[2], stream));
     int h_misc[16];
-    HIPCHK(hipMemcpyAsync(h_misc, c.misc.p, 64, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
+    int64_t total;
+    if ((rc = read_call_flags(c, stream, h_misc, total))) return rc;
     float tot = 0;
     HIPCHK(hipEventElapsedTime(&tot, c.ev[0], c.ev[2]));
     c.timing.fill_ms = fill_ms; c.timing.traceback_ms = tb_ms; c.timing.total_ms = tot;
     c.timing.cells = cells; c.timing.n_launches = (int64_t)nchunks; c.timing.trace_bytes = trace_bytes;
     c.timing.dominant_ms = fill_ms; c.timing.dominant_launches = (int64_t)nchunks; c.timing.fast_path = 0;
-    int64_t total;
-    memcpy(&total, reinterpret_cast<char *>(h_misc) + 16, 8);
     if (out_total) *out_total = total;
     const int ef = h_misc[0];
-    if (ef & 1) { set_err("a base >= 5 was found: the reference would panic (index out of range)%s", ""); return GNX_EBASE; }
+    if (ef & 1) return flag_error(1, total);
     if (ef & 16) {
         if (t_no_pipe) { set_err("a strip waited more than 5 s for the strip above it%s", ""); return GNX_EDEVICE; }
         if (getenv("GNX_DEBUG")) fprintf(stderr, "[gnx] a pipelined strip timed out: the call runs again with sequential strips\n");
@@ -2162,9 +2138,7 @@ int run_device(const gnx_params *prm, int64_t n_pairs,
         t_no_pipe = false;
         return rc;
     }
-    if (ef & 2) { set_err("unexpected traceback%s", ""); return GNX_ETRACE; }
-    if (ef & 4) { set_err("CIGAR buffer too small: need %s%lld elements", "", (long long)total); return GNX_ECAPACITY; }
-    return GNX_OK;
+    return flag_error(ef & 6, total);
 }
 
 // ---- score-only chunk / multiple-alignment calls: the sweep with explicit cell scores (n1_sweep.hip.h) -------
