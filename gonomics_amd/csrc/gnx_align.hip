@@ -1898,11 +1898,16 @@ int run_device(const gnx_params *prm, int64_t n_pairs,
     }
     // ---- plan ----
     const auto t_plan0 = std::chrono::steady_clock::now();
-    bool p16 = true; // 4*score fits a signed 16-bit profile entry
-    for (int x = 0; x < 25; x++) { const int64_t v = 4 * (prm->scores[x] - 2 * (affine ? prm->gap_extend : 0)); if (v > 32767 || v < -32768) p16 = false; }
-    if (!getenv("GNX_FORCE_P16")) p16 = false; // int32 profile: plain 2-cycle VGPR add instead of a 4-cycle SDWA add
     bool hform = affine && prm->gap_open <= 0;
     if (getenv("GNX_NO_HFORM")) hform = false;
+    // what the fill keeps of a score fits a signed 16-bit profile entry: 4 * (s - 2e) in the h-form, 4 * s in the plain one (which never
+    // stores 4 * (s - 2e): asking it of the plain form too only keeps this rule from admitting a table it refused before)
+    bool p16 = true;
+    for (int x = 0; x < 25; x++) {
+        const int64_t v = 4 * (prm->scores[x] - 2 * (affine ? prm->gap_extend : 0)), w = 4 * prm->scores[x];
+        if (v > 32767 || v < -32768 || (!hform && (w > 32767 || w < -32768))) p16 = false;
+    }
+    if (!getenv("GNX_FORCE_P16")) p16 = false; // int32 profile: plain 2-cycle VGPR add instead of a 4-cycle SDWA add
     const int Q = affine ? QA : QC;
     // the plans are built in pinned host memory kept by the context: a fresh std::vector of 96 B per pair costs a page fault per 42 pairs
     // and an upload from pageable memory -- 400 000 pairs of 150 x 216: 16 of the call's 24 ms (round 3)
