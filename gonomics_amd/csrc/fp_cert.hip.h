@@ -14,16 +14,33 @@ namespace {
 //      16 384-bit prefilter beside it;
 //   2. the window is streamed 16 columns per lane and round (one 16-byte load, or one dword of the packed reference): a lane packs
 //      its columns into a 32-bit code word, takes the word of the lane before it (__shfl_up) and looks up the 16 16-mers that START in
-//      that earlier word's last 15 columns or at its own first one (v_alignbit).  Bytes that are not A C G T count as their two low bits:
-//      a false hit can only refuse a pair, the decision below re-scores from the real bytes;
+//      that earlier word's last 15 columns or at its own first one (v_alignbit): sixteen prefilter tests without a branch, then one
+//      loop over the bits that are set.  Bytes that are not A C G T count as their two low bits: a false hit can only refuse a pair,
+//      the decision below re-scores from the real bytes;
 //   3. all hits must share one diagonal c (wave-wide min == max); a read that holds a 16-mer twice puts two hits on two diagonals;
-//   4. the bases under the read on diagonal c, at the window's start and at its end are staged in LDS, and lane 0 runs the
-//      decision arithmetic the host shares (gnx_cert_decide).
+//   4. the decision (fp_cert_decide.h, the pieces gnx_cert_decide is made of) runs across the wave: a lane takes ceil(n / 64) consecutive
+//      rows -- the read's base from LDS, the window's bases on diagonal c, on its first and on its last columns from memory -- and the
+//      lanes' sums are combined in int64 by wave sums and prefix scans (__shfl on the two halves): the deficit and the score by sums,
+//      "no prefix of f above 0" by a scan of f, d* by a scan of g and a wave-wide (least prefix, first row), the edge rule's four
+//      sums by masked sums once the deficit has fixed T1 and T2.  The call's matrix comes as a kernel argument (built once on the host).
 // Windows of the packed reference that hold an exception (N, byte >= 5) are not certified; bytes >= 5 raise the sweep's error flag.
 // ------------------------------------------------------------------------------------------------------
 constexpr int CERT_K = 16;
 constexpr int CERT_SLOTS = 512;  // table slots (at most 145 keys); the prefilter has 32 bits per slot word
 constexpr int CERT_NMAX = 160;   // one row block
+constexpr int CERT_CHUNK = (CERT_NMAX + 63) / 64; // rows per lane, at most
+
+// wave operations of the decision (tests/cpp/cert_wave_test.cpp restates them on the host, in this order)
+__device__ __forceinline__ int64_t cert_wave_sum(int64_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+__device__ __forceinline__ int64_t cert_wave_scan(int64_t v, int lane) { // inclusive prefix sums
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const int64_t t = __shfl_up(v, d, 64); if (lane >= d) v += t; }
+    return v;
+}
 
 __device__ __forceinline__ unsigned cert_hash(unsigned code) { return code * 0x9E3779B1u; } // slot = top 9 bits, filter bit = top 14 bits
 // 2-bit codes of four dna.Base bytes -> 8 bits (byte k at bits 2k)
@@ -37,16 +54,14 @@ template <bool PK>
 __global__ __launch_bounds__(64) void fp_cert_kernel(const PairPlan *__restrict__ plans, int n_pairs,
                                                      const uint8_t *__restrict__ a_buf, const int64_t *__restrict__ a_start,
                                                      const uint8_t *__restrict__ b_buf, const int64_t *__restrict__ b_start,
-                                                     KParams kp, TbParams tp, gnx_cigar *__restrict__ stage, int cap,
+                                                     KParams kp, TbParams tp, GnxCertMatrix mx, gnx_cigar *__restrict__ stage, int cap,
                                                      int64_t *__restrict__ score_out, int64_t *__restrict__ nops,
                                                      int64_t *__restrict__ live, int *__restrict__ err) {
     __shared__ unsigned keys[CERT_SLOTS];
     __shared__ int qv[CERT_SLOTS];
     __shared__ unsigned filt[CERT_SLOTS];
-    __shared__ uint8_t sa[CERT_NMAX], sd[CERT_NMAX], sf[CERT_NMAX], sl[CERT_NMAX];
-    __shared__ int64_t sc64[25];
-    __shared__ GnxCertMatrix smx;
-    __shared__ int64_t res[3];
+    __shared__ uint8_t sa[CERT_NMAX];
+    __shared__ int64_t sw[32]; // w(x, y) at 8 x + y (the host built mx with mx.ok set, or did not launch)
     const int p = (int)blockIdx.x;
     if (p >= n_pairs) return;
     const int lane = threadIdx.x;
@@ -66,13 +81,8 @@ __global__ __launch_bounds__(64) void fp_cert_kernel(const PairPlan *__restrict_
     bool read_ok = true;
     for (int i = lane; i < n; i += 64) { const uint8_t v = ap[i]; sa[i] = v; if (v >= 4) read_ok = false; }
     if (__any(!read_ok)) { if (lane == 0) live[p] = 1; return; } // (N in the read: no certificate; a byte >= 5: the sweep flags it)
-    if (lane == 0) { // the call's matrix, rebased (kp holds 4 x the scores)
-#pragma unroll
-        for (int x = 0; x < 25; x++) sc64[x] = (int64_t)(kp.sc4[x] >> 2);
-        gnx_cert_matrix_init(&smx, sc64, (int64_t)(kp.o4 >> 2), (int64_t)(kp.e4 >> 2));
-    }
-    __syncthreads();
-    if (!smx.ok) { if (lane == 0) live[p] = 1; return; }
+    if (lane < 32) sw[lane] = gnx_cert_table8_entry(&mx, lane);
+    __syncthreads(); // (sa and the empty table, before the 16-mers are read and inserted)
     for (int q = lane; q + CERT_K <= n; q += 64) {
         unsigned code = 0;
 #pragma unroll
@@ -117,19 +127,24 @@ __global__ __launch_bounds__(64) void fp_cert_kernel(const PairPlan *__restrict_
         if (lane == 0) prev = carry;
         carry = __shfl(cw, 63, 64);
         const int s0 = 16 * (g0 + lane) - sh - 16; // window column (0-based) of the earlier word's first base
+        unsigned hits = 0; // bit t - 1: the prefilter has the 16-mer that starts t bases into `prev` -- sixteen tests without a branch
 #pragma unroll
         for (int t = 1; t <= 16; t++) {
-            const unsigned code = t < 16 ? __builtin_amdgcn_alignbit(cw, prev, 2 * t) : cw;
+            const unsigned h = cert_hash(t < 16 ? __builtin_amdgcn_alignbit(cw, prev, 2 * t) : cw);
+            hits |= ((filt[h >> 23] >> ((h >> 18) & 31u)) & 1u) << (t - 1);
+        }
+        while (hits) { // (one branch per round; about one lookup in a hundred gets here, and the read's own locus)
+            const int t = __ffs(hits);
+            hits &= hits - 1;
+            const unsigned code = (unsigned)((((unsigned long long)cw << 32) | prev) >> (2 * t));
             const unsigned h = cert_hash(code);
-            if ((filt[h >> 23] >> ((h >> 18) & 31u)) & 1u) {
-                const int s = s0 + t;
-                if (s >= 0 && s + CERT_K <= m) {
-                    unsigned slot = h >> 23;
-                    int q;
-                    while ((q = qv[slot]) != -1 && dmin >= dmax) {
-                        if (keys[slot] == code) { dmin = min(dmin, s - q); dmax = max(dmax, s - q); }
-                        slot = (slot + 1) & (CERT_SLOTS - 1);
-                    }
+            const int s = s0 + t;
+            if (s >= 0 && s + CERT_K <= m) {
+                unsigned slot = h >> 23;
+                int q;
+                while ((q = qv[slot]) != -1 && dmin >= dmax) {
+                    if (keys[slot] == code) { dmin = min(dmin, s - q); dmax = max(dmax, s - q); }
+                    slot = (slot + 1) & (CERT_SLOTS - 1);
                 }
             }
         }
@@ -141,23 +156,43 @@ __global__ __launch_bounds__(64) void fp_cert_kernel(const PairPlan *__restrict_
     const int c = dmin;
     if (dmin != dmax || c <= 0 || c >= m - n) { if (lane == 0) live[p] = 1; return; } // (no hit at all: dmin > dmax)
 
-    // ---- 3. the real bases under the read on diagonal c, on the window's first and last columns; the decision ----
-    for (int i = lane; i < n; i += 64) {
-        sd[i] = (uint8_t)bp.at(c + i);
-        sf[i] = (uint8_t)bp.at(i);
-        sl[i] = (uint8_t)bp.at(m - n + i);
+    // ---- 3. the decision across the wave: the real bases under a lane's rows on diagonal c, on the window's first and last columns ----
+    const int chunk = (n + 63) >> 6, i0 = lane * chunk;
+    GnxCertLane ln;
+    gnx_cert_lane_init(&ln);
+    int64_t loss[CERT_CHUNK];
+#pragma unroll
+    for (int k = 0; k < CERT_CHUNK; k++) {
+        const int i = i0 + k;
+        loss[k] = 0;
+        if (k < chunk && i < n) loss[k] = gnx_cert_lane_row<8>(&ln, sw, i, sa[i], (unsigned)bp.at(c + i), (unsigned)bp.at(i), (unsigned)bp.at(m - n + i));
     }
-    __syncthreads();
-    if (lane == 0) {
-        int64_t ds = 0, sc = 0;
-        const int ok = gnx_cert_decide(&smx, sa, n, sd, sf, sl, m, c, CERT_K, tp.ci, tp.cj, &ds, &sc);
-        res[0] = ok; res[1] = ds; res[2] = sc;
+    if (__any(!ln.ok)) { if (lane == 0) live[p] = 1; return; } // a byte >= 5 under the read
+    const int64_t D = cert_wave_sum(ln.loss), mid_sum = cert_wave_sum(ln.mid);
+    const int64_t Fi = cert_wave_scan(ln.f, lane), Gi = cert_wave_scan(ln.g, lane);
+    const int f_pos = __any(ln.rows > 0 && Fi - ln.f + ln.f_top > 0); // some F_alpha > 0
+    int64_t g_low = ln.rows > 0 ? Gi - ln.g + ln.g_low : INT64_MAX;
+    int g_row = ln.rows > 0 ? ln.g_row : n;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) gnx_cert_low_min(&g_low, &g_row, __shfl_xor(g_low, d, 64), __shfl_xor(g_row, d, 64));
+    const GnxCertBounds t = gnx_cert_bounds(mx.lambda, mx.o, n, CERT_K, D); // (uniform from here on)
+    int64_t h1 = 0, h2 = 0, t1 = 0, t2 = 0;
+    if (t.edge) { // the loss of the first / last T1 and T2 rows
+#pragma unroll
+        for (int k = 0; k < CERT_CHUNK; k++) {
+            const int i = i0 + k;
+            if (i < t.T1) h1 += loss[k];
+            if (i < t.T2) h2 += loss[k];
+            if (i >= n - t.T1) t1 += loss[k];
+            if (i >= n - t.T2) t2 += loss[k];
+        }
+        h1 = cert_wave_sum(h1); h2 = cert_wave_sum(h2); t1 = cert_wave_sum(t1); t2 = cert_wave_sum(t2);
     }
-    __syncthreads();
-    if (!res[0]) { if (lane == 0) live[p] = 1; return; }
+    int64_t best, ds, sc;
+    gnx_cert_tail(__shfl(Gi, 63, 64), g_low, g_row, n, &best, &ds);
+    if (!gnx_cert_finish(&t, mx.o, mx.e, n, m, f_pos, mid_sum, h1, h2, t1, t2, best, ds, &ds, &sc)) { if (lane == 0) live[p] = 1; return; }
     if (lane == 0) {
         // the runs in traceback order, as fp_walk_kernel stages them: [d* M] [m - n - c I] [n - d* M] [c I]
-        const int64_t ds = res[1];
         gnx_cigar *stg = stage + (int64_t)p * cap;
         int cnt = 0;
         auto put = [&](int op, int64_t run) { gnx_cigar g; g.run_length = run; g.op = (uint8_t)op; for (int z = 0; z < 7; z++) g._pad[z] = 0; stg[cnt++] = g; };
@@ -166,7 +201,7 @@ __global__ __launch_bounds__(64) void fp_cert_kernel(const PairPlan *__restrict_
         put(0, (int64_t)n - ds);
         put(1, c);
         nops[p] = cnt;
-        score_out[p] = res[2];
+        score_out[p] = sc;
         live[p] = 0;
     }
 }

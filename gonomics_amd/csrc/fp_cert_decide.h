@@ -1,6 +1,8 @@
 // fp_cert_decide.h -- the gapless-read certificate's decision arithmetic, plain C++: no HIP header needed.
-// Shared by fp_cert_kernel (fp_cert.hip.h, one lane per pair runs it on staged bases) and by the host-only debug entry
-// gnx_debug_gapless_certificate (the CPU tests).  Everything here is exact integer arithmetic in int64.
+// The pieces -- a row's terms, a lane's chunk of rows, the thresholds, the tail rule, the finishing arithmetic -- are shared by
+// fp_cert_kernel (fp_cert.hip.h: 64 lanes with a chunk of rows each, combined by wave sums and scans) and by gnx_cert_decide, their serial
+// composition, which the host-only debug entry gnx_debug_gapless_certificate runs (the CPU tests; tests/cpp/cert_wave_test.cpp
+// evaluates the pieces the kernel's way on the host and requires gnx_cert_decide's results).  Exact integer arithmetic in int64.
 #pragma once
 #include <stdint.h>
 
@@ -38,55 +40,143 @@ GNX_CERT_HD inline void gnx_cert_matrix_init(GnxCertMatrix *mx, const int64_t *s
     mx->ok = (ok && lam > 0) ? 1 : 0;
 }
 
+// Entry k = 8 x + y of the table with row stride 8 (the kernel's copy in LDS: an index without a multiply); y = 5 .. 7 is padding.
+GNX_CERT_HD inline int64_t gnx_cert_table8_entry(const GnxCertMatrix *mx, int k) { return (k & 7) < 5 ? mx->w[(k >> 3) * 5 + (k & 7)] : 0; }
+
+// ---- a row ----
+// Read base a against the window's bases on diagonal c (bd), on its first n columns (bf) and on its last n columns (bl):
+// mid = w(a, bd), the row's loss on the diagonal R_a - mid, and what the row gains on the first / last columns instead.
+// w = the table with row stride STRIDE (5: GnxCertMatrix::w, 8: gnx_cert_table8_entry).  Returns 0 for an N in the read or a byte >= 5.
+struct GnxCertRow {
+    int64_t mid, loss, f, g;
+};
+template <int STRIDE>
+GNX_CERT_HD inline int gnx_cert_row(const int64_t *w, unsigned a, unsigned bd, unsigned bf, unsigned bl, GnxCertRow *r) {
+    if (a >= 4 || bd >= 5 || bf >= 5 || bl >= 5) return 0;
+    const int64_t *wa = w + a * STRIDE;
+    const int64_t mid = wa[bd];
+    r->mid = mid; r->loss = wa[a] - mid; r->f = wa[bf] - mid; r->g = wa[bl] - mid;
+    return 1;
+}
+
+// ---- a lane's chunk of consecutive rows, taken in ascending order ----
+// Sums of the four terms; f_top = the largest of the chunk's own prefix sums of f (item 6: the prefix before the chunk + f_top <= 0);
+// g_low = the least sum of g over the chunk's rows BEFORE a row and g_row = the first row that attains it (the suffix sum G from
+// that row on is the chunk's largest, and of equal ones the longest).
+struct GnxCertLane {
+    int64_t loss, mid, f, g, f_top, g_low;
+    int32_t g_row, rows, ok;
+};
+GNX_CERT_HD inline void gnx_cert_lane_init(GnxCertLane *l) {
+    l->loss = l->mid = l->f = l->g = l->f_top = l->g_low = 0;
+    l->g_row = 0; l->rows = 0; l->ok = 1;
+}
+// row i joins the chunk; returns its loss (the edge rule's sums)
+template <int STRIDE>
+GNX_CERT_HD inline int64_t gnx_cert_lane_row(GnxCertLane *l, const int64_t *w, int i, unsigned a, unsigned bd, unsigned bf, unsigned bl) {
+    GnxCertRow r;
+    if (!gnx_cert_row<STRIDE>(w, a, bd, bf, bl, &r)) { l->ok = 0; return 0; }
+    if (l->rows == 0 || l->g < l->g_low) { l->g_low = l->g; l->g_row = i; }
+    l->loss += r.loss; l->mid += r.mid; l->f += r.f; l->g += r.g;
+    if (l->rows == 0 || l->f > l->f_top) l->f_top = l->f;
+    l->rows++;
+    return r.loss;
+}
+// (least prefix, first row) of two chunks
+GNX_CERT_HD inline void gnx_cert_low_min(int64_t *low, int *row, int64_t other_low, int other_row) {
+    if (other_low < *low || (other_low == *low && other_row < *row)) { *low = other_low; *row = other_row; }
+}
+
+// ---- the thresholds: items 4 and 5 from the deficit D ----
+// ok = 0: refused.  edge = 1: -o < D < -2o, the edge rule decides: the loss of the first / last T1 and T2 rows (T1 + T2 < n).
+struct GnxCertBounds {
+    int64_t T1, T2;
+    int32_t ok, edge;
+};
+// x / y for x >= 0 < y; values below 2^32, as every call of the kernel has them, take a 32-bit division
+GNX_CERT_HD inline int64_t gnx_cert_div(int64_t x, int64_t y) {
+    if ((((uint64_t)x | (uint64_t)y) >> 32) == 0) return (int64_t)((uint32_t)x / (uint32_t)y);
+    return x / y;
+}
+GNX_CERT_HD inline GnxCertBounds gnx_cert_bounds(int64_t lambda, int64_t o, int64_t n, int64_t K, int64_t D) {
+    GnxCertBounds t = {0, 0, 0, 0};
+    const int64_t O = -o;
+    if (K > n) return t; // (every ceiling below is at most n)
+    if (D == O || D >= 2 * O) return t; // (deficit == -o: a perfect path with three gap runs ties; refused, not argued)
+    const int64_t J = gnx_cert_div(D, lambda), J1 = gnx_cert_div(D + O, lambda);
+    if (n - J <= 0 || n - J1 <= 0) return t;
+    // K <= ceil(x / y)  <=>  (K - 1) y < x
+    if ((K - 1) * (3 + J) >= n - J || (K - 1) * (2 + J1) >= n - J1) return t;
+    if (D > O) {
+        // -o < deficit < -2o: paths with three gap runs.  Off diagonal c they need an exact run of K rows (the third inequality); with a
+        // segment on diagonal c they have to save -o or more on the rows outside it: at most T1 rows at one end and T2 at the other.
+        const int64_t J3 = gnx_cert_div(D - O, lambda);
+        if ((K - 1) * (4 + J3) >= n - J3) return t;
+        t.T1 = (1 + J3) * (K - 1) + J3; t.T2 = (2 + J3) * (K - 1) + J3;
+        if (t.T1 + t.T2 >= n) return t; // (every row is an edge row: E = deficit)
+        t.edge = 1;
+    }
+    t.ok = 1;
+    return t;
+}
+
+// ---- the tail: G_d = the sum of g over the last d rows, G_0 = 0; the LARGEST d that attains the maximum ----
+// g_tot = the sum of g over all rows, (g_low, g_row) = the least sum of g over the rows before a row and the first row that attains it.
+GNX_CERT_HD inline void gnx_cert_tail(int64_t g_tot, int64_t g_low, int64_t g_row, int64_t n, int64_t *best, int64_t *d_star) {
+    const int64_t G = g_tot - g_low;
+    if (G >= 0) { *best = G; *d_star = n - g_row; } else { *best = 0; *d_star = 0; }
+}
+
+// ---- the finishing arithmetic: items 4 (the edge rule's corners), 6 and the score ----
+// f_pos: some F_alpha > 0; h1, h2 / t1, t2 = the loss of the first / last T1 and T2 rows (read only when t->edge).
+GNX_CERT_HD inline int gnx_cert_finish(const GnxCertBounds *t, int64_t o, int64_t e, int64_t n, int64_t m, int f_pos, int64_t mid_sum, int64_t h1,
+                                       int64_t h2, int64_t t1, int64_t t2, int64_t best, int64_t ds, int64_t *d_star, int64_t *score) {
+    if (!t->ok || f_pos) return 0;
+    if (t->edge && (h1 + t2 >= -o || h2 + t1 >= -o)) return 0;
+    if (ds >= n) return 0;
+    *d_star = ds;
+    *score = mid_sum + best + 2 * o + e * (n + m);
+    return 1;
+}
+
 // Items 1 (shape and checkerboard), 2 (no N in the read), 4, 5 and 6 of the certificate for a pair whose exact K-mer matches all lie on
 // diagonal c (item 3, the caller's scan).  a[0..n) = the read; bd / bf / bl[0..n) = the window's bases under the read on diagonal c, on
 // the window's first n columns and on its last n columns (b + c, b, b + m - n).  Item 4 has two branches: deficit < -o, or
 // -o < deficit < -2o with the edge rule (a second pass over at most T2 rows from each end, running sums only).  Returns 1 and the
 // closed form -- d* = the trailing read bases that sit on the window's last columns, the score -- or 0: the pair goes through the sweep.
+// The serial composition of the pieces above.
 GNX_CERT_HD inline int gnx_cert_decide(const GnxCertMatrix *mx, const uint8_t *a, int64_t n, const uint8_t *bd, const uint8_t *bf, const uint8_t *bl,
                                        int64_t m, int64_t c, int64_t K, int64_t ci, int64_t cj, int64_t *d_star, int64_t *score) {
     if (!mx->ok || n < 1 || K < 1 || m < n + 2 || c <= 0 || c >= m - n) return 0;
     if (ci < n || cj < m) return 0; // a checkerboard edge inside the matrix: quirks Q1 / Q2 are the walk's business
+    GnxCertRow r, r2;
     int64_t deficit = 0, mid_sum = 0, F = 0;
     for (int64_t i = 0; i < n; i++) {
-        const int x = a[i];
-        if (x >= 4 || bd[i] >= 5 || bf[i] >= 5 || bl[i] >= 5) return 0;
-        const int64_t mid = mx->w[x * 5 + bd[i]];
-        deficit += mx->R[x] - mid;
-        mid_sum += mid;
-        F += mx->w[x * 5 + bf[i]] - mid; // the first i + 1 rows on the window's first columns instead (ties stay on the diagonal)
+        if (!gnx_cert_row<5>(mx->w, a[i], bd[i], bf[i], bl[i], &r)) return 0;
+        deficit += r.loss;
+        mid_sum += r.mid;
+        F += r.f; // the first i + 1 rows on the window's first columns instead (ties stay on the diagonal)
         if (F > 0) return 0;
     }
-    const int64_t O = -mx->o;
-    if (deficit == O || deficit >= 2 * O) return 0; // (deficit == -o: a perfect path with three gap runs ties; refused, not argued)
-    const int64_t J = deficit / mx->lambda, J1 = (deficit + O) / mx->lambda;
-    if (n - J <= 0 || n - J1 <= 0) return 0;
-    if (K > (n - J + (3 + J) - 1) / (3 + J) || K > (n - J1 + (2 + J1) - 1) / (2 + J1)) return 0;
-    if (deficit > O) {
-        // -o < deficit < -2o: paths with three gap runs.  Off diagonal c they need an exact run of K rows (the third inequality); with a
-        // segment on diagonal c they have to save -o or more on the rows outside it: at most T1 rows at one end and T2 at the other.
-        const int64_t J3 = (deficit - O) / mx->lambda;
-        if (K > (n - J3 + (4 + J3) - 1) / (4 + J3)) return 0;
-        const int64_t T1 = (1 + J3) * (K - 1) + J3, T2 = (2 + J3) * (K - 1) + J3;
-        if (T1 + T2 >= n) return 0; // (every row is an edge row: E = deficit)
-        int64_t h1 = 0, h2 = 0, t1 = 0, t2 = 0; // the loss of the first / last T1 and T2 rows
-        for (int64_t i = 0; i < T2; i++) {
-            const int64_t lh = mx->R[a[i]] - mx->w[a[i] * 5 + bd[i]], lt = mx->R[a[n - 1 - i]] - mx->w[a[n - 1 - i] * 5 + bd[n - 1 - i]];
-            h2 += lh; t2 += lt;
-            if (i < T1) { h1 += lh; t1 += lt; }
+    const GnxCertBounds t = gnx_cert_bounds(mx->lambda, mx->o, n, K, deficit);
+    if (!t.ok) return 0;
+    int64_t h1 = 0, h2 = 0, t1 = 0, t2 = 0; // the loss of the first / last T1 and T2 rows
+    if (t.edge)
+        for (int64_t i = 0; i < t.T2; i++) {
+            const int64_t j = n - 1 - i;
+            gnx_cert_row<5>(mx->w, a[i], bd[i], bf[i], bl[i], &r);
+            gnx_cert_row<5>(mx->w, a[j], bd[j], bf[j], bl[j], &r2);
+            h2 += r.loss; t2 += r2.loss;
+            if (i < t.T1) { h1 += r.loss; t1 += r2.loss; }
         }
-        if (h1 + t2 >= O || h2 + t1 >= O) return 0;
-    }
     int64_t G = 0, best = 0, ds = 0;
     for (int64_t d = 1; d <= n; d++) { // the last d rows on the window's last columns instead: the LARGEST d that attains the maximum
         const int64_t i = n - d;
-        G += mx->w[a[i] * 5 + bl[i]] - mx->w[a[i] * 5 + bd[i]];
+        gnx_cert_row<5>(mx->w, a[i], bd[i], bf[i], bl[i], &r);
+        G += r.g;
         if (G >= best) { best = G; ds = d; }
     }
-    if (ds >= n) return 0;
-    *d_star = ds;
-    *score = mid_sum + best + 2 * mx->o + mx->e * (n + m);
-    return 1;
+    return gnx_cert_finish(&t, mx->o, mx->e, n, m, 0, mid_sum, h1, h2, t1, t2, best, ds, d_star, score);
 }
 
 // Item 3 the naive way (host: the debug entry).  Exact K-mer matches of read positions q .. q + K - 1 and window positions j .. j + K - 1 over

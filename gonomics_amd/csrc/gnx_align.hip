@@ -432,6 +432,7 @@ int run_device_fp(const gnx_params *prm, const KParams &kp, const TbParams &tp, 
     int64_t *d_cflag = nullptr, *d_coff = nullptr;
     int *d_live = nullptr;
     PairPlan *d_gpl = nullptr;
+    bool gathered = false; // the certificate ran: d_gpl / d_live hold the live pairs
     if (cert) {
         if ((rc = c.fp_cflag.ensure((size_t)(2 * np + 2) * 8))) return rc;
         if ((rc = c.fp_live.ensure((size_t)np * 4))) return rc;
@@ -441,9 +442,15 @@ int run_device_fp(const gnx_params *prm, const KParams &kp, const TbParams &tp, 
         d_gpl = reinterpret_cast<PairPlan *>(c.fp_gplans.p);
     }
     auto certify = [&](hipStream_t st) -> int {
+        GnxCertMatrix mx; // the call's matrix, rebased, from the scores the kernels see (kp holds 4 x the scores): once per call
+        int64_t sc64[25];
+        for (int x = 0; x < 25; x++) sc64[x] = (int64_t)(kp.sc4[x] >> 2);
+        gnx_cert_matrix_init(&mx, sc64, (int64_t)(kp.o4 >> 2), (int64_t)(kp.e4 >> 2));
+        g_cert_offered += np;
+        if (!mx.ok) return GNX_OK; // no certificate under this matrix: everyone through the sweep (n_live = np), nothing launched
         HIPCHK(hipMemsetAsync(d_cflag + np, 0, 8, st));
         auto kc = kp.b2 ? fp_cert_kernel<true> : fp_cert_kernel<false>;
-        hipLaunchKernelGGL(kc, dim3((unsigned)np), dim3(64), 0, st, dpl, np, d_a, d_as, d_b, d_bs, kp, tp, d_stage, CAP, d_score, d_nops, d_cflag, d_err);
+        hipLaunchKernelGGL(kc, dim3((unsigned)np), dim3(64), 0, st, dpl, np, d_a, d_as, d_b, d_bs, kp, tp, mx, d_stage, CAP, d_score, d_nops, d_cflag, d_err);
         HIPCHK(hipGetLastError());
         if ((rc = launch_scan(d_cflag, np, d_coff, d_cflag + np, st))) return rc;
         hipLaunchKernelGGL(fp_cert_gather_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, np, d_cflag, d_coff, dpl, d_live, d_gpl);
@@ -452,7 +459,8 @@ int run_device_fp(const gnx_params *prm, const KParams &kp, const TbParams &tp, 
         HIPCHK(hipMemcpyAsync(&nl, d_coff + np, 8, hipMemcpyDeviceToHost, st)); // the sweep's grid
         HIPCHK(hipStreamSynchronize(st));
         n_live = (int)nl;
-        g_cert_offered += np; g_cert_ok += np - n_live;
+        gathered = true;
+        g_cert_ok += np - n_live;
         if (getenv("GNX_DEBUG")) fprintf(stderr, "[gnx fp] gapless certificate: %d of %d pairs certified, %d go through the sweep\n", np - n_live, np, n_live);
         return GNX_OK;
     };
@@ -620,9 +628,9 @@ int run_device_fp(const gnx_params *prm, const KParams &kp, const TbParams &tp, 
 
     HIPCHK(hipEventRecord(c.ev[0], stream));
     if (cert && (rc = certify(stream))) return rc; // (inside the bracket: fill_ms and dominant_ms include it)
-    if ((rc = forward(cert ? d_gpl : dpl, n_live, stream))) return rc;
+    if ((rc = forward(gathered ? d_gpl : dpl, n_live, stream))) return rc;
     HIPCHK(hipEventRecord(c.ev[1], stream));
-    if ((rc = post(0, np, stream, d_cnt, c.ev[4], c.ev[5], cert ? d_live : nullptr, n_live))) return rc;
+    if ((rc = post(0, np, stream, d_cnt, c.ev[4], c.ev[5], gathered ? d_live : nullptr, n_live))) return rc;
     if ((rc = launch_scan(d_nops, np, d_ops_off, d_carry, stream))) return rc;
     hipLaunchKernelGGL(fp_compact_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, stream, np, d_st, d_stage, d_nops, d_ops_off, d_ops, ops_capacity, d_err, CAP);
     HIPCHK(hipGetLastError());
