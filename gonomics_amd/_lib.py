@@ -25,7 +25,8 @@ EXPORTS = ["gnx_device_count", "gnx_init", "gnx_shutdown", "gnx_last_error", "gn
            "gnx_affine_gap_chunk_score_batch", "gnx_multiple_affine_gap_score_batch",
            "gnx_best_of_by_offset", "gnx_best_of_windows", "gnx_best_pair_by_offset", "gnx_best_pair_windows",
            "gnx_reference_index_build", "gnx_reference_index_info", "gnx_reference_index_get", "gnx_seed_candidates",
-           "gnx_summarize_batch", "gnx_summarize_batch_windows", "gnx_summarize_batch_by_offset"]
+           "gnx_summarize_batch", "gnx_summarize_batch_windows", "gnx_summarize_batch_by_offset",
+           "gnx_md_batch", "gnx_md_batch_windows", "gnx_md_batch_by_offset", "gnx_mapq_batch"]
 GNX_XCOL_EQ, GNX_XCOL_X = 3, 4
 
 
@@ -173,6 +174,15 @@ def lib():
             L.gnx_summarize_batch_windows.restype = ctypes.c_int
             L.gnx_summarize_batch_by_offset.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_p)]
             L.gnx_summarize_batch_by_offset.restype = ctypes.c_int
+        if hasattr(L, "gnx_md_batch"):
+            L.gnx_md_batch.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_p)]
+            L.gnx_md_batch.restype = ctypes.c_int
+            L.gnx_md_batch_windows.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, i64, c_p, c_p, c_p, i64, c_p, c_p, c_p, c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_p)]
+            L.gnx_md_batch_windows.restype = ctypes.c_int
+            L.gnx_md_batch_by_offset.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_p)]
+            L.gnx_md_batch_by_offset.restype = ctypes.c_int
+            L.gnx_mapq_batch.argtypes = [i64, c_p, c_p, c_p]
+            L.gnx_mapq_batch.restype = ctypes.c_int
         L.gnx_seed_index_build.argtypes = [c_p, c_p, i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(i64)]
         L.gnx_seed_index_build.restype = ctypes.c_int
         L.gnx_seed_index_set.argtypes = [c_p, c_p, i64, c_p, c_p, i64, ctypes.c_int]
@@ -697,6 +707,59 @@ def summarize_batch_by_offset(params, read_cat, read_off, ref_start, ref_len, op
     n, ops = int(ref_start.shape[0]), _ops_array(ops)
     return _summarize(lambda o, xp, xo: L.gnx_summarize_batch_by_offset(ctypes.byref(params), n, read_cat.ctypes.data, read_off.ctypes.data, ref_start.ctypes.data, ref_len.ctypes.data,
                                                                         ops.ctypes.data, ops_off.ctypes.data, o, xp, xo), n, xcigar, out)
+
+
+# ---- MD strings (gnx_md_*) and the MAPQ rule (gnx_mapq_batch) ----
+def _md(call, n):
+    """call(md_ref, off_ref) -> rc.  Returns (bytes uint8[off[n]], off int64[n + 1]): pair k's string is bytes[off[k] : off[k + 1]]."""
+    md_p, off_p = ctypes.c_void_p(), ctypes.c_void_p()
+    check(call(ctypes.byref(md_p), ctypes.byref(off_p)))
+    off = _take_array(off_p, n + 1, ctypes.c_int64, np.int64)
+    return _take_array(md_p, int(off[-1]), ctypes.c_uint8, np.uint8), off
+
+
+def md_batch_windows(params, a_buf, a_start, a_len, b_buf, b_start, b_len, ops, ops_off):
+    """gnx_md_batch_windows: the MD strings of the CIGARs ops[ops_off[p] : ops_off[p + 1]] against windows of two buffers (alpha is described)."""
+    L = lib()
+    a_buf, b_buf = _u8(a_buf), _u8(b_buf)
+    a_start, a_len, b_start, b_len, ops_off = _i64(a_start), _i64(a_len), _i64(b_start), _i64(b_len), _i64(ops_off)
+    n, ops = int(a_start.shape[0]), _ops_array(ops)
+    return _md(lambda mp, op: L.gnx_md_batch_windows(ctypes.byref(params), n, a_buf.ctypes.data, a_buf.shape[0], a_start.ctypes.data, a_len.ctypes.data,
+                                                     b_buf.ctypes.data, b_buf.shape[0], b_start.ctypes.data, b_len.ctypes.data, ops.ctypes.data, ops_off.ctypes.data, mp, op), n)
+
+
+def md_batch(params, alphas, betas, ops, ops_off):
+    """gnx_md_batch on lists of uint8 arrays."""
+    L = lib()
+    a_cat, a_off = _cat(list(alphas))
+    b_cat, b_off = _cat(list(betas))
+    n, ops, ops_off = len(alphas), _ops_array(ops), _i64(ops_off)
+    return _md(lambda mp, op: L.gnx_md_batch(ctypes.byref(params), n, a_cat.ctypes.data, a_off.ctypes.data, b_cat.ctypes.data, b_off.ctypes.data,
+                                             ops.ctypes.data, ops_off.ctypes.data, mp, op), n)
+
+
+def md_batch_by_offset(params, read_cat, read_off, ref_start, ref_len, ops, ops_off):
+    """gnx_md_batch_by_offset: reads (the queries) against windows of the resident reference (described); GNX_AFFINE_GAP_LOCAL only."""
+    L = lib()
+    read_cat, read_off, ref_start, ref_len, ops_off = _u8(read_cat), _i64(read_off), _i64(ref_start), _i64(ref_len), _i64(ops_off)
+    n, ops = int(ref_start.shape[0]), _ops_array(ops)
+    return _md(lambda mp, op: L.gnx_md_batch_by_offset(ctypes.byref(params), n, read_cat.ctypes.data, read_off.ctypes.data, ref_start.ctypes.data, ref_len.ctypes.data,
+                                                       ops.ctypes.data, ops_off.ctypes.data, mp, op), n)
+
+
+def md_strings(md, off):
+    """the strings of an (md, off) pair"""
+    raw = md.tobytes()
+    return [raw[int(off[k]):int(off[k + 1])].decode("ascii") for k in range(off.shape[0] - 1)]
+
+
+def mapq_batch(scores, second_scores):
+    """gnx_mapq_batch: uint8 MAPQs from scores and second scores (INT64_MIN: no other candidate).  Host arithmetic: no device, no init."""
+    scores, second_scores = _i64(scores), _i64(second_scores)
+    n = int(scores.shape[0])
+    out = np.zeros(max(n, 1), dtype=np.uint8)
+    check(lib().gnx_mapq_batch(n, scores.ctypes.data, second_scores.ctypes.data, out.ctypes.data))
+    return out[:n]
 
 
 def _chunk_pairs(alphas, betas):

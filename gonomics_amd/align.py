@@ -418,11 +418,57 @@ def FormatXCigar(route):
     return "".join("%d%s" % (c[0], runes[c[1]]) for c in route) or "*"
 
 
-def _report(params, reads, placed, extra):
-    """placed[r] = (best, strand, score, window (start, len) or None, route): one SummarizeByOffset call on the reads that have a winner"""
+def MDTags(params, alphas, betas, routes):
+    """The MD string of every alignment (gnx_md_batch): routes[k] is the CIGAR of alphas[k] against betas[k], and alphas[k] is the
+    DESCRIBED side -- the reference of SAM's MD:Z tag -- whose letters stand under every substitution and deletion, e.g. "3T2^G3".
+    include/gnx_align.h defines the string; in GNX_AFFINE_GAP_LOCAL the free end gaps are outside it."""
+    if not routes:
+        return []
+    ops, off = _routes_to_ops(routes)
+    try:
+        md, md_off = _lib.md_batch(params, alphas, betas, ops, off)
+    except _lib.GnxError as e:
+        _raise(e)
+    return _lib.md_strings(md, md_off)
+
+
+def MDTagsByOffset(params, reads, windows, routes):
+    """MDTags against the resident reference (gnx_md_batch_by_offset): windows[k] = (start, len) is the described side, reads[k] the
+    query in the orientation it was aligned in.  GNX_AFFINE_GAP_LOCAL only: in the global modes the window is beta."""
+    if not routes:
+        return []
+    ops, off = _routes_to_ops(routes)
+    r_cat, r_off = _lib._cat(list(reads))
+    try:
+        md, md_off = _lib.md_batch_by_offset(params, r_cat, r_off, [w[0] for w in windows], [w[1] for w in windows], ops, off)
+    except _lib.GnxError as e:
+        _raise(e)
+    return _lib.md_strings(md, md_off)
+
+
+def Mapq(scores, second_scores):
+    """gnx_mapq_batch: the library's MAPQ (0 .. 60) of placements from their scores and the best score among each one's other
+    candidates; None = there is no other candidate."""
+    if not len(scores):
+        return []
+    none = np.iinfo(np.int64).min
+    try:
+        out = _lib.mapq_batch([int(x) for x in scores], [none if x is None else int(x) for x in second_scores])
+    except _lib.GnxError as e:
+        _raise(e)
+    return [int(x) for x in out]
+
+
+def _report(params, reads, placed, extra, tags=False):
+    """placed[r] = (best, strand, score, window (start, len) or None, route): one SummarizeByOffset call on the reads that have a winner;
+    tags: one MDTagsByOffset call on the same reads behind it ("md"), and "mapq" from score and extra[r]["second_score"]"""
     idx = [r for r, p in enumerate(placed) if p[0] >= 0]
     oriented = [dna.ReverseComplement(np.array(reads[r], dtype=np.uint8)) if placed[r][1] else reads[r] for r in idx]  # (it works in place: on a copy)
     sums = SummarizeByOffset(params, oriented, [placed[r][3] for r in idx], [placed[r][4] for r in idx], xcigar=True)
+    if tags:
+        mds = dict(zip(idx, MDTagsByOffset(params, oriented, [placed[r][3] for r in idx], [placed[r][4] for r in idx])))
+        mapq = Mapq([p[2] for p in placed], [e["second_score"] for e in extra])
+        extra = [dict(e, md=mds.get(r), mapq=mapq[r]) for r, e in enumerate(extra)]
     at = dict(zip(idx, sums))
     rep = []
     for r, (best, strand, score, win, route) in enumerate(placed):
@@ -442,18 +488,20 @@ def _local_only(params, name):
         raise ValueError("%s: the mode must be GNX_AFFINE_GAP_LOCAL (positions are defined nowhere else)" % name)
 
 
-def MapReadsReport(params, reads, **vote_opts):
+def MapReadsReport(params, reads, tags=False, **vote_opts):
     """MapReads (GNX_AFFINE_GAP_LOCAL) plus what is in each placement: the seed and best-of calls run unchanged, then ONE
     SummarizeByOffset call on the winners (strand-1 winners as their reverse complements).  Returns one dict per read: best, strand,
     score, window_start, pos (0-based reference position of the first aligned base = window_start + alpha_start), end, route, xcigar
-    and the summary fields; a read without a candidate has best -1, pos None and zero counts."""
+    and the summary fields; a read without a candidate has best -1, pos None and zero counts.  With tags=True one MDTagsByOffset call
+    on the winners follows, and every dict also has md (None for an unplaced read), second_score (the highest score among the read's
+    other candidates, None with a single one) and mapq (Mapq of score and second_score)."""
     _local_only(params, "MapReadsReport")
     if not reads:
         return []
     r_cat, r_off = _lib._cat(list(reads))
     try:
         c_off, start, ln, strand, _ = _lib.seed_candidates(r_cat, r_off, **_vote_opts(vote_opts))
-        best, scores, _, _, ops, off = _lib.best_of_by_offset(params, r_cat, r_off, c_off, start, ln, strand, cigar=True)
+        best, scores, _, cand, ops, off = _lib.best_of_by_offset(params, r_cat, r_off, c_off, start, ln, strand, cigar=True)
     except _lib.GnxError as e:
         _raise(e)
     placed = []
@@ -461,12 +509,18 @@ def MapReadsReport(params, reads, **vote_opts):
         b = int(best[r])
         c = int(c_off[r]) + b
         placed.append((b, int(strand[c]) if b >= 0 else 0, int(scores[r]), (int(start[c]), int(ln[c])) if b >= 0 else None, _to_route(ops[off[r]:off[r + 1]])))
-    return _report(params, reads, placed, [{} for _ in reads])
+    if not tags:
+        return _report(params, reads, placed, [{} for _ in reads])
+    extra = []
+    for r in range(len(reads)):
+        others = [int(x) for k, x in enumerate(cand[c_off[r]:c_off[r + 1]]) if k != int(best[r])]
+        extra.append({"second_score": max(others) if others else None})
+    return _report(params, reads, placed, extra, tags=True)
 
 
-def MapReadPairsReport(params, reads, min_insert, max_insert, unpaired_penalty=0, **vote_opts):
+def MapReadPairsReport(params, reads, min_insert, max_insert, unpaired_penalty=0, tags=False, **vote_opts):
     """MapReadPairs plus what is in each placement (see MapReadsReport); every dict also has second_score (None without another
-    candidate) and its pair's proper / tlen."""
+    candidate) and its pair's proper / tlen, and with tags=True md and mapq."""
     _local_only(params, "MapReadPairsReport")
     if len(reads) % 2:
         raise ValueError("MapReadPairsReport: reads come in mate pairs (an even number)")
@@ -486,7 +540,7 @@ def MapReadPairsReport(params, reads, min_insert, max_insert, unpaired_penalty=0
                        _to_route(out["ops"][out["off"][r]:out["off"][r + 1]])))
         second = int(out["second_score"][r])
         extra.append({"second_score": second if second != np.iinfo(np.int64).min else None, "proper": bool(out["proper"][r // 2]), "tlen": int(out["tlen"][r // 2])})
-    return _report(params, reads, placed, extra)
+    return _report(params, reads, placed, extra, tags=tags)
 
 
 def AffineGapChunk(alpha, beta, scores, gapOpen, gapExtend, chunkSize):

@@ -57,6 +57,7 @@
 #include "span_origin.hip.h"
 #include "ref_seeds.hip.h"
 #include "aln_summary.hip.h"
+#include "aln_md.hip.h"
 
 namespace {
 
@@ -144,7 +145,7 @@ struct Ctx {
     DevBuf ss_len, res_end, gat_end; // gnx_locate_*: target lengths for the end read off a CIGAR, the ends of a host job, their gather on device 0
     DevBuf ss_plans, ss_rowbuf, ss_prog, ss_err, ss_off; // the score-only sweep (score_sweep.hip.h): plans, hand-over rows, progress / claim words, error flags; offsets of a dropped CIGAR
     DevBuf sd_keys, sd_locs, sd_nodes, sd_node_off, sd_word_off, sd_words, sd_tmp[8];
-    DevBuf sm[14]; // gnx_summarize_* (gnx_host.hip.h, SM_*): sequences, window tables, CIGAR runs and offsets, the score matrix, summaries, the extended CIGAR's counts / offsets / runs
+    DevBuf sm[14]; // gnx_summarize_* and gnx_md_* (gnx_host.hip.h, SM_*): sequences, window tables, CIGAR runs and offsets, the score matrix, summaries, the extended CIGAR's counts / offsets / runs (gnx_md_*: the strings' byte counts / offsets / bytes)
     DevBuf bo[19]; // gnx_best_of_* / gnx_best_pair_* (gnx_host.hip.h, BO_*): reads + reverse complements, candidate tables and scores, per-read winners, the winners' tables
     int64_t sd_n = -1, sd_nodes_n = 0; int sd_seed_len = 0;
     // k-mer index of the resident reference (gnx_reference_index_build; context 0 only) and the scratch of gnx_seed_candidates (RS_*)
@@ -3087,6 +3088,38 @@ int gnx_summarize_batch_by_offset(const gnx_params *p, int64_t n_pairs, const ui
     const SeqSide reads = cat_side(read_cat, read_off, n_pairs, rl), wins = ref_side(ref_start, ref_len);
     const bool local = p->mode == GNX_AFFINE_GAP_LOCAL; // the roles of gnx_best_of_by_offset: the window is the target (alpha) of the mapping mode, beta everywhere else
     return run_summarize(p, n_pairs, local ? wins : reads, local ? reads : wins, ops, ops_off, out, out_xops, out_xops_off);
+}
+
+/* ---- MD strings: the same walk with the reference letters under every substitution and deletion (gnx_align.h) ---- */
+int gnx_md_batch_windows(const gnx_params *p, int64_t n_pairs,
+                         const uint8_t *alpha_buf, int64_t alpha_buf_len, const int64_t *alpha_start, const int64_t *alpha_len,
+                         const uint8_t *beta_buf, int64_t beta_buf_len, const int64_t *beta_start, const int64_t *beta_len,
+                         const gnx_cigar *ops, const int64_t *ops_off, char **out_md, int64_t **out_md_off) {
+    ApiCall api;
+    const SeqSide sa{alpha_buf, alpha_buf_len, alpha_start, alpha_len, false}, sb{beta_buf, beta_buf_len, beta_start, beta_len, false};
+    return run_md(p, n_pairs, sa, sb, ops, ops_off, out_md, out_md_off);
+}
+
+int gnx_md_batch(const gnx_params *p, int64_t n_pairs, const uint8_t *alpha_cat, const int64_t *alpha_off, const uint8_t *beta_cat, const int64_t *beta_off,
+                 const gnx_cigar *ops, const int64_t *ops_off, char **out_md, int64_t **out_md_off) {
+    if (n_pairs < 0 || !alpha_off || !beta_off) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    const std::vector<int64_t> al = lengths_of(alpha_off, n_pairs), bl = lengths_of(beta_off, n_pairs);
+    return gnx_md_batch_windows(p, n_pairs, alpha_cat, alpha_off[n_pairs], alpha_off, al.data(), beta_cat, beta_off[n_pairs], beta_off, bl.data(), ops, ops_off, out_md, out_md_off);
+}
+
+int gnx_md_batch_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *read_cat, const int64_t *read_off, const int64_t *ref_start, const int64_t *ref_len,
+                           const gnx_cigar *ops, const int64_t *ops_off, char **out_md, int64_t **out_md_off) {
+    ApiCall api;
+    if (!p || n_pairs < 0 || !read_off || !ref_start || !ref_len) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (p->mode != GNX_AFFINE_GAP_LOCAL) { set_err("gnx_md_batch_by_offset takes GNX_AFFINE_GAP_LOCAL only (the window is the described side there), not mode %s%lld", "", (long long)p->mode); return GNX_EINVAL; }
+    const std::vector<int64_t> rl = lengths_of(read_off, n_pairs);
+    return run_md(p, n_pairs, ref_side(ref_start, ref_len), cat_side(read_cat, read_off, n_pairs, rl), ops, ops_off, out_md, out_md_off);
+}
+
+int gnx_mapq_batch(int64_t n, const int64_t *score, const int64_t *second_score, uint8_t *out_mapq) {
+    if (n < 0 || (n > 0 && (!score || !second_score || !out_mapq))) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    for (int64_t r = 0; r < n; r++) out_mapq[r] = mapq_of(score[r], second_score[r]);
+    return GNX_OK;
 }
 
 int gnx_score_batch_device(const gnx_params *p, int64_t n_pairs,

@@ -1084,14 +1084,13 @@ int run_best_of(const gnx_params *prm, int64_t n_reads, const uint8_t *read_cat,
 // caller's outputs before every kernel has succeeded.
 enum { SM_A, SM_B, SM_AS, SM_AL, SM_BS, SM_BL, SM_OPS, SM_OFF, SM_SC, SM_OUT, SM_NX, SM_XOFF, SM_XOPS, SM_MISC, SM_COUNT };
 static_assert(SM_COUNT == sizeof(Ctx::sm) / sizeof(DevBuf), "Ctx::sm holds one buffer per SM_* index");
-int run_summarize(const gnx_params *prm, int64_t n_pairs, const SeqSide &sa, const SeqSide &sb, const gnx_cigar *ops, const int64_t *ops_off,
-                  gnx_aln_summary *out, gnx_cigar **out_xops, int64_t **out_xops_off) {
-    const auto t_entry = std::chrono::steady_clock::now();
-    // ---- argument checks: everything that needs no device ----
-    if (!prm || n_pairs < 0 || !ops_off || !out || !sa.start || !sa.len || !sb.start || !sb.len || sa.buf_len < 0 || sb.buf_len < 0) { set_err("bad argument%s", ""); return GNX_EINVAL; }
-    if ((out_xops == nullptr) != (out_xops_off == nullptr)) { set_err("out_xops and out_xops_off must be given together%s", ""); return GNX_EINVAL; }
+// The argument checks gnx_summarize_* and gnx_md_* share: everything that needs no device.  outs_given: the entry's required outputs are
+// there; xops_paired: gnx_summarize_*'s optional pair of outputs comes together or not at all.  cells = the columns of all CIGARs.
+int check_cigar_call(const gnx_params *prm, int64_t n_pairs, const SeqSide &sa, const SeqSide &sb, const gnx_cigar *ops, const int64_t *ops_off,
+                     bool outs_given, bool xops_paired, int64_t &cells) {
+    if (!prm || n_pairs < 0 || !ops_off || !outs_given || !sa.start || !sa.len || !sb.start || !sb.len || sa.buf_len < 0 || sb.buf_len < 0) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (!xops_paired) { set_err("out_xops and out_xops_off must be given together%s", ""); return GNX_EINVAL; }
     if (prm->mode < GNX_AFFINE_GAP || prm->mode > GNX_CONST_GAP_HIGHMEM) { set_err("unknown mode %s%lld", "", (long long)prm->mode); return GNX_EINVAL; }
-    const bool local = prm->mode == GNX_AFFINE_GAP_LOCAL, affine = local || prm->mode == GNX_AFFINE_GAP || prm->mode == GNX_AFFINE_GAP_HIGHMEM, xc = out_xops != nullptr;
     if (ops_off[0] != 0) { set_err("ops_off must start at 0%s", ""); return GNX_EINVAL; }
     for (int64_t q = 0; q < n_pairs; q++)
         if (ops_off[q + 1] < ops_off[q]) { set_err("decreasing ops_off at pair %s%lld", "", (long long)q); return GNX_EINVAL; }
@@ -1103,7 +1102,7 @@ int run_summarize(const gnx_params *prm, int64_t n_pairs, const SeqSide &sa, con
             if (!s->resident && s->len[q] > 0 && !s->buf) { set_err("null sequence buffer%s", ""); return GNX_EINVAL; }
             if (s->len[q] >= ((int64_t)1 << 30)) { set_err("a sequence of 2^30 bases or more at pair %s%lld (the limit of the align entries)", "", (long long)q); return GNX_EINVAL; }
         }
-    int64_t cells = 0;
+    cells = 0;
     for (int64_t q = 0; q < n_pairs; q++) {
         int64_t fa = sa.len[q], fb = sb.len[q]; // what is left of either sequence
         for (int64_t x = ops_off[q]; x < ops_off[q + 1]; x++) {
@@ -1117,17 +1116,83 @@ int run_summarize(const gnx_params *prm, int64_t n_pairs, const SeqSide &sa, con
             cells += len;
         }
     }
-    Ctx &c = ctx_at(0);
-    CtxScope scope(c);
-    int rc;
-    if ((rc = ensure_init())) return rc;
-    g_transport = 0; g_bcast_ms = 0;
+    return GNX_OK;
+}
+// ... and the one that needs the context: the windows of a resident side lie inside the reference
+int check_resident_windows(const Ctx &c, int64_t n_pairs, const SeqSide &sa, const SeqSide &sb) {
     if (sa.resident || sb.resident) {
         if (c.ref_len < 0) { set_err("no resident reference: call gnx_set_reference first%s", ""); return GNX_EINVAL; }
         const SeqSide &s = sa.resident ? sa : sb;
         for (int64_t q = 0; q < n_pairs; q++)
             if (s.len[q] > c.ref_len - s.start[q]) { set_err("window out of bounds at pair %s%lld", "", (long long)q); return GNX_EINVAL; }
     }
+    return GNX_OK;
+}
+
+// What both families send up once per call (n_pairs > 0): sequences, window tables, CIGAR runs and offsets, the score matrix, the zeroed
+// flag and carry words; `a` gets every field that does not depend on the sub-batch.  Returns which side the kernels read packed in pk.
+int sum_upload(Ctx &c, hipStream_t st, const gnx_params *prm, int64_t n_pairs, const SeqSide &sa, const SeqSide &sb, const gnx_cigar *ops, const int64_t *ops_off,
+               SumArgs &a, int &pk) {
+    DevBuf *sm = c.sm;
+    const size_t np = (size_t)n_pairs;
+    const int64_t n_runs = ops_off[n_pairs];
+    int rc;
+    if ((rc = sm[SM_AS].ensure(np * 8)) || (rc = sm[SM_AL].ensure(np * 8)) || (rc = sm[SM_BS].ensure(np * 8)) || (rc = sm[SM_BL].ensure(np * 8)) ||
+        (rc = sm[SM_OPS].ensure((size_t)std::max<int64_t>(n_runs, 1) * sizeof(gnx_cigar))) || (rc = sm[SM_OFF].ensure((np + 1) * 8)) || (rc = sm[SM_SC].ensure(25 * 8)) ||
+        (rc = sm[SM_NX].ensure(np * 8)) || (rc = sm[SM_XOFF].ensure((np + 1) * 8)) || (rc = sm[SM_MISC].ensure(64)) ||
+        (!sa.resident && (rc = sm[SM_A].ensure((size_t)sa.buf_len + 16))) || (!sb.resident && (rc = sm[SM_B].ensure((size_t)sb.buf_len + 16)))) return rc;
+    memset(&a, 0, sizeof(a));
+    for (int side = 0; side < 2; side++) {
+        const SeqSide &s = side ? sb : sa;
+        KParams &k = a.kp;
+        if (s.resident) { k.b2 = (const unsigned *)c.ref.p; k.bflag = (const unsigned long long *)c.ref_flag.p; k.brank = (const unsigned *)c.ref_rank.p; k.bexc = (const unsigned long long *)c.ref_exc.p; }
+        else if (s.buf_len > 0) HIPCHK(hipMemcpyAsync(sm[side ? SM_B : SM_A].p, s.buf, (size_t)s.buf_len, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(sm[side ? SM_BS : SM_AS].p, s.start, np * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(sm[side ? SM_BL : SM_AL].p, s.len, np * 8, hipMemcpyHostToDevice, st));
+    }
+    if (n_runs > 0) HIPCHK(hipMemcpyAsync(sm[SM_OPS].p, ops, (size_t)n_runs * sizeof(gnx_cigar), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sm[SM_OFF].p, ops_off, (np + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sm[SM_SC].p, prm->scores, 25 * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(sm[SM_MISC].p, 0, 64, st)); // [0] the error flags (int), [8 ..) the scan's carry (int64)
+    a.a_buf = sa.resident ? nullptr : (const uint8_t *)sm[SM_A].p; a.b_buf = sb.resident ? nullptr : (const uint8_t *)sm[SM_B].p;
+    a.ops = (const gnx_cigar *)sm[SM_OPS].p; a.scores = (const int64_t *)sm[SM_SC].p;
+    a.local = prm->mode == GNX_AFFINE_GAP_LOCAL;
+    a.err = (int *)sm[SM_MISC].p;
+    pk = sa.resident ? 1 : sb.resident ? 2 : 0;
+    return GNX_OK;
+}
+// `a` for the sub-batch of cnt pairs from pair b: its slices of the per-pair tables
+SumArgs sum_sub_args(const SumArgs &a, DevBuf *sm, int64_t b, int64_t cnt) {
+    SumArgs s = a;
+    s.a_start = (const int64_t *)sm[SM_AS].p + b; s.a_len = (const int64_t *)sm[SM_AL].p + b; s.b_start = (const int64_t *)sm[SM_BS].p + b; s.b_len = (const int64_t *)sm[SM_BL].p + b;
+    s.ops_off = (const int64_t *)sm[SM_OFF].p + b; s.out = (gnx_aln_summary *)sm[SM_OUT].p + b; s.nx = (int64_t *)sm[SM_NX].p + b; s.xoff = (const int64_t *)sm[SM_XOFF].p + b;
+    s.n_pairs = cnt;
+    return s;
+}
+// GNX_EBASE's check of that sub-batch (aln_summary_bases_kernel): one workgroup per pair, or several that share a pair when the launch is a few long pairs
+void launch_sum_bases(SumArgs s, int pk, const SeqSide &sa, const SeqSide &sb, int64_t b, int64_t cnt, hipStream_t st) {
+    int64_t longest = 0;
+    for (int64_t q = b; q < b + cnt; q++) longest = std::max(longest, std::max(sa.len[q], sb.len[q]));
+    const int chunks = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(longest / 8192, 256), ((int64_t)1 << 16) / cnt));
+    const dim3 bgrid((unsigned)std::min<int64_t>(cnt, 1 << 20), (unsigned)chunks);
+    s.slice = (int)((((longest + chunks - 1) / chunks) + 255) & ~(int64_t)255) + 256;
+    if (pk == 1) hipLaunchKernelGGL(aln_summary_bases_kernel<1>, bgrid, dim3(256), 0, st, s);
+    else if (pk == 2) hipLaunchKernelGGL(aln_summary_bases_kernel<2>, bgrid, dim3(256), 0, st, s);
+    else hipLaunchKernelGGL(aln_summary_bases_kernel<0>, bgrid, dim3(256), 0, st, s);
+}
+
+int run_summarize(const gnx_params *prm, int64_t n_pairs, const SeqSide &sa, const SeqSide &sb, const gnx_cigar *ops, const int64_t *ops_off,
+                  gnx_aln_summary *out, gnx_cigar **out_xops, int64_t **out_xops_off) {
+    const auto t_entry = std::chrono::steady_clock::now();
+    int rc;
+    int64_t cells = 0;
+    if ((rc = check_cigar_call(prm, n_pairs, sa, sb, ops, ops_off, out != nullptr, (out_xops == nullptr) == (out_xops_off == nullptr), cells))) return rc;
+    const bool local = prm->mode == GNX_AFFINE_GAP_LOCAL, affine = local || prm->mode == GNX_AFFINE_GAP || prm->mode == GNX_AFFINE_GAP_HIGHMEM, xc = out_xops != nullptr;
+    Ctx &c = ctx_at(0);
+    CtxScope scope(c);
+    if ((rc = ensure_init())) return rc;
+    g_transport = 0; g_bcast_ms = 0;
+    if ((rc = check_resident_windows(c, n_pairs, sa, sb))) return rc;
     hipStream_t st = c.own_stream;
     gnx_cigar *xops = nullptr;
     int64_t *xoff = nullptr;
@@ -1148,58 +1213,27 @@ int run_summarize(const gnx_params *prm, int64_t n_pairs, const SeqSide &sa, con
         if (const char *e = getenv("GNX_SUMMARY_FORM")) cut = e[0] == '0' ? 1 : e[0] == '1' ? 0x7fffffff : 64;
         DevBuf *sm = c.sm;
         const size_t np = (size_t)n_pairs;
-        if ((rc = sm[SM_AS].ensure(np * 8)) || (rc = sm[SM_AL].ensure(np * 8)) || (rc = sm[SM_BS].ensure(np * 8)) || (rc = sm[SM_BL].ensure(np * 8)) ||
-            (rc = sm[SM_OPS].ensure((size_t)std::max<int64_t>(n_runs, 1) * sizeof(gnx_cigar))) || (rc = sm[SM_OFF].ensure((np + 1) * 8)) || (rc = sm[SM_SC].ensure(25 * 8)) ||
-            (rc = sm[SM_OUT].ensure(np * sizeof(gnx_aln_summary))) || (rc = sm[SM_NX].ensure(np * 8)) || (rc = sm[SM_XOFF].ensure((np + 1) * 8)) || (rc = sm[SM_MISC].ensure(64)) ||
-            (!sa.resident && (rc = sm[SM_A].ensure((size_t)sa.buf_len + 16))) || (!sb.resident && (rc = sm[SM_B].ensure((size_t)sb.buf_len + 16)))) return fail(rc);
+        if ((rc = sm[SM_OUT].ensure(np * sizeof(gnx_aln_summary)))) return fail(rc);
         auto run = [&]() -> int {
             SumArgs a;
-            memset(&a, 0, sizeof(a));
-            for (int side = 0; side < 2; side++) {
-                const SeqSide &s = side ? sb : sa;
-                KParams &k = a.kp;
-                if (s.resident) { k.b2 = (const unsigned *)c.ref.p; k.bflag = (const unsigned long long *)c.ref_flag.p; k.brank = (const unsigned *)c.ref_rank.p; k.bexc = (const unsigned long long *)c.ref_exc.p; }
-                else if (s.buf_len > 0) HIPCHK(hipMemcpyAsync(sm[side ? SM_B : SM_A].p, s.buf, (size_t)s.buf_len, hipMemcpyHostToDevice, st));
-                HIPCHK(hipMemcpyAsync(sm[side ? SM_BS : SM_AS].p, s.start, np * 8, hipMemcpyHostToDevice, st));
-                HIPCHK(hipMemcpyAsync(sm[side ? SM_BL : SM_AL].p, s.len, np * 8, hipMemcpyHostToDevice, st));
-            }
-            if (n_runs > 0) HIPCHK(hipMemcpyAsync(sm[SM_OPS].p, ops, (size_t)n_runs * sizeof(gnx_cigar), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(sm[SM_OFF].p, ops_off, (np + 1) * 8, hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(sm[SM_SC].p, prm->scores, 25 * 8, hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemsetAsync(sm[SM_MISC].p, 0, 64, st)); // [0] the error flags (int), [8 ..) the scan's carry (int64)
-            a.a_buf = sa.resident ? nullptr : (const uint8_t *)sm[SM_A].p; a.b_buf = sb.resident ? nullptr : (const uint8_t *)sm[SM_B].p;
-            a.ops = (const gnx_cigar *)sm[SM_OPS].p; a.scores = (const int64_t *)sm[SM_SC].p;
-            a.gap_open = prm->gap_open; a.gap_extend = prm->gap_extend; a.cut = cut; a.affine = affine; a.local = local;
-            a.err = (int *)sm[SM_MISC].p; a.xops = nullptr;
+            int pk, r; // pk: which side the kernels read packed
+            if ((r = sum_upload(c, st, prm, n_pairs, sa, sb, ops, ops_off, a, pk))) return r;
+            a.gap_open = prm->gap_open; a.gap_extend = prm->gap_extend; a.cut = cut; a.affine = affine;
             int64_t *d_carry = (int64_t *)sm[SM_MISC].p + 1;
-            const int pk = sa.resident ? 1 : sb.resident ? 2 : 0; // which side the kernels read packed
             auto launch = [&](bool write) -> int {
                 for (int64_t b = 0; b < n_pairs; b += sub) {
                     const int64_t cnt = std::min(sub, n_pairs - b);
-                    SumArgs s = a;
-                    s.a_start = (const int64_t *)sm[SM_AS].p + b; s.a_len = (const int64_t *)sm[SM_AL].p + b; s.b_start = (const int64_t *)sm[SM_BS].p + b; s.b_len = (const int64_t *)sm[SM_BL].p + b;
-                    s.ops_off = (const int64_t *)sm[SM_OFF].p + b; s.out = (gnx_aln_summary *)sm[SM_OUT].p + b; s.nx = (int64_t *)sm[SM_NX].p + b; s.xoff = (const int64_t *)sm[SM_XOFF].p + b;
-                    s.n_pairs = cnt;
+                    const SumArgs s = sum_sub_args(a, sm, b, cnt);
                     const dim3 grid((unsigned)std::min<int64_t>((cnt + 3) / 4, 1 << 20));
-                    // the base check: one workgroup per pair, or several that share a pair when the launch is a few long pairs
-                    int64_t longest = 0;
-                    for (int64_t q = b; q < b + cnt; q++) longest = std::max(longest, std::max(sa.len[q], sb.len[q]));
-                    const int chunks = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(longest / 8192, 256), ((int64_t)1 << 16) / cnt));
-                    const dim3 bgrid((unsigned)std::min<int64_t>(cnt, 1 << 20), (unsigned)chunks);
-                    s.slice = (int)((((longest + chunks - 1) / chunks) + 255) & ~(int64_t)255) + 256;
                     if (write) {
                         if (pk == 1) hipLaunchKernelGGL((aln_summary_kernel<true, 1>), grid, dim3(256), 0, st, s);
                         else if (pk == 2) hipLaunchKernelGGL((aln_summary_kernel<true, 2>), grid, dim3(256), 0, st, s);
                         else hipLaunchKernelGGL((aln_summary_kernel<true, 0>), grid, dim3(256), 0, st, s);
-                    } else if (pk == 1) {
-                        hipLaunchKernelGGL(aln_summary_bases_kernel<1>, bgrid, dim3(256), 0, st, s);
-                        hipLaunchKernelGGL((aln_summary_kernel<false, 1>), grid, dim3(256), 0, st, s);
-                    } else if (pk == 2) {
-                        hipLaunchKernelGGL(aln_summary_bases_kernel<2>, bgrid, dim3(256), 0, st, s);
-                        hipLaunchKernelGGL((aln_summary_kernel<false, 2>), grid, dim3(256), 0, st, s);
                     } else {
-                        hipLaunchKernelGGL(aln_summary_bases_kernel<0>, bgrid, dim3(256), 0, st, s);
-                        hipLaunchKernelGGL((aln_summary_kernel<false, 0>), grid, dim3(256), 0, st, s);
+                        launch_sum_bases(s, pk, sa, sb, b, cnt, st);
+                        if (pk == 1) hipLaunchKernelGGL((aln_summary_kernel<false, 1>), grid, dim3(256), 0, st, s);
+                        else if (pk == 2) hipLaunchKernelGGL((aln_summary_kernel<false, 2>), grid, dim3(256), 0, st, s);
+                        else hipLaunchKernelGGL((aln_summary_kernel<false, 0>), grid, dim3(256), 0, st, s);
                     }
                     HIPCHK(hipGetLastError());
                     int r;
@@ -1208,7 +1242,6 @@ int run_summarize(const gnx_params *prm, int64_t n_pairs, const SeqSide &sa, con
                 }
                 return GNX_OK;
             };
-            int r;
             HIPCHK(hipEventRecord(c.ev[0], st));
             if ((r = launch(false))) return r;
             HIPCHK(hipEventRecord(c.ev[1], st));
@@ -1250,6 +1283,110 @@ int run_summarize(const gnx_params *prm, int64_t n_pairs, const SeqSide &sa, con
     t.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count();
     c.timing = t;
     return GNX_OK;
+}
+
+// ---- gnx_md_*: the MD strings of CIGARs walked against their sequences (aln_md.hip.h; contract: gnx_align.h) ----------------------
+// gnx_summarize_*'s host flow with bytes where it has extended runs: the same checks, the same uploads into the same buffers (the
+// bytes go where the extended runs go), the base check, aln_md_kernel<false> and the scan per sub-batch of GNX_HOST_SUB pairs
+// (GNX_MD_SUB=<pairs> overrides the cut), one read-back of the flags and offsets that sizes the output, aln_md_kernel<true>.
+int run_md(const gnx_params *prm, int64_t n_pairs, const SeqSide &sa, const SeqSide &sb, const gnx_cigar *ops, const int64_t *ops_off, char **out_md, int64_t **out_md_off) {
+    const auto t_entry = std::chrono::steady_clock::now();
+    int rc;
+    int64_t cells = 0;
+    if ((rc = check_cigar_call(prm, n_pairs, sa, sb, ops, ops_off, out_md && out_md_off, true, cells))) return rc;
+    Ctx &c = ctx_at(0);
+    CtxScope scope(c);
+    if ((rc = ensure_init())) return rc;
+    g_transport = 0; g_bcast_ms = 0;
+    if ((rc = check_resident_windows(c, n_pairs, sa, sb))) return rc;
+    hipStream_t st = c.own_stream;
+    char *md = nullptr;
+    int64_t *off = (int64_t *)g_pool.get((size_t)(n_pairs + 1) * 8);
+    if (!off) { set_err("pinned host allocation failed%s", ""); return GNX_ENOMEM; }
+    off[0] = 0;
+    auto fail = [&](int r) { g_pool.put(off); if (md) g_pool.put(md); return r; };
+    gnx_timing t = {};
+    t.fast_path = 13; t.cells = cells; t.n_contexts = 1;
+    if (n_pairs > 0) {
+        int64_t sub = gnx_host_sub(getenv("GNX_HOST_SUB"));
+        if (const char *e = getenv("GNX_MD_SUB")) sub = std::max<int64_t>(atoll(e), 1);
+        int cut = 64;
+        if (const char *e = getenv("GNX_MD_FORM")) cut = e[0] == '0' ? 1 : e[0] == '1' ? 0x7fffffff : 64;
+        DevBuf *sm = c.sm;
+        const size_t np = (size_t)n_pairs;
+        auto run = [&]() -> int {
+            MdArgs a;
+            a.md = nullptr;
+            int pk, r;
+            if ((r = sum_upload(c, st, prm, n_pairs, sa, sb, ops, ops_off, a.s, pk))) return r;
+            a.s.cut = cut;
+            int64_t *d_carry = (int64_t *)sm[SM_MISC].p + 1;
+            auto launch = [&](bool write) -> int {
+                for (int64_t b = 0; b < n_pairs; b += sub) {
+                    const int64_t cnt = std::min(sub, n_pairs - b);
+                    MdArgs s = a;
+                    s.s = sum_sub_args(a.s, sm, b, cnt);
+                    const dim3 grid((unsigned)std::min<int64_t>((cnt + 3) / 4, 1 << 20));
+                    if (write) {
+                        if (pk == 1) hipLaunchKernelGGL((aln_md_kernel<true, 1>), grid, dim3(256), 0, st, s);
+                        else if (pk == 2) hipLaunchKernelGGL((aln_md_kernel<true, 2>), grid, dim3(256), 0, st, s);
+                        else hipLaunchKernelGGL((aln_md_kernel<true, 0>), grid, dim3(256), 0, st, s);
+                    } else {
+                        launch_sum_bases(s.s, pk, sa, sb, b, cnt, st);
+                        if (pk == 1) hipLaunchKernelGGL((aln_md_kernel<false, 1>), grid, dim3(256), 0, st, s);
+                        else if (pk == 2) hipLaunchKernelGGL((aln_md_kernel<false, 2>), grid, dim3(256), 0, st, s);
+                        else hipLaunchKernelGGL((aln_md_kernel<false, 0>), grid, dim3(256), 0, st, s);
+                    }
+                    HIPCHK(hipGetLastError());
+                    if (!write && (r = launch_scan(s.s.nx, (int)cnt, (int64_t *)sm[SM_XOFF].p + b, d_carry, st))) return r;
+                    t.n_launches++;
+                }
+                return GNX_OK;
+            };
+            HIPCHK(hipEventRecord(c.ev[0], st));
+            if ((r = launch(false))) return r;
+            HIPCHK(hipEventRecord(c.ev[1], st));
+            int ef = 0;
+            HIPCHK(hipMemcpyAsync(&ef, sm[SM_MISC].p, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(off, sm[SM_XOFF].p, (np + 1) * 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st)); // (also: the sources are pageable memory of the caller -- no return while a copy may still read them)
+            if (ef & 1) { set_err("a base >= 5 was found: the reference would panic (index out of range)%s", ""); return GNX_EBASE; }
+            float ms = 0;
+            HIPCHK(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+            t.fill_ms = ms;
+            const int64_t n_md = off[n_pairs]; // (at least one byte per pair)
+            md = (char *)g_pool.get((size_t)n_md);
+            if (!md) { set_err("pinned host allocation failed%s", ""); return GNX_ENOMEM; }
+            if ((r = sm[SM_XOPS].ensure((size_t)n_md + 64))) return r;
+            a.md = (char *)sm[SM_XOPS].p;
+            HIPCHK(hipEventRecord(c.ev[2], st));
+            if ((r = launch(true))) return r;
+            HIPCHK(hipEventRecord(c.ev[3], st));
+            HIPCHK(hipMemcpyAsync(md, sm[SM_XOPS].p, (size_t)n_md, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            HIPCHK(hipEventElapsedTime(&ms, c.ev[2], c.ev[3]));
+            t.fill_ms += ms;
+            return GNX_OK;
+        };
+        if ((rc = run())) { (void)hipStreamSynchronize(st); return fail(rc); }
+    } else {
+        md = (char *)g_pool.get(1);
+        if (!md) { set_err("pinned host allocation failed%s", ""); return fail(GNX_ENOMEM); }
+    }
+    *out_md = md; *out_md_off = off;
+    t.dominant_ms = t.total_ms = t.fill_ms; t.dominant_launches = t.n_launches;
+    t.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count();
+    c.timing = t;
+    return GNX_OK;
+}
+
+// gnx_mapq_batch's rule for one read (gnx_align.h): the share of the score that the best other candidate does not reach, on a scale of 60
+uint8_t mapq_of(int64_t score, int64_t second) {
+    if (score <= 0) return 0;
+    const int64_t s2 = second < 0 ? 0 : second; // (INT64_MIN, "no other candidate", is negative too)
+    if (s2 >= score) return 0;
+    const unsigned __int128 q = (unsigned __int128)60 * (uint64_t)(score - s2) / (uint64_t)score; // (60 * 2^63 does not fit 64 bits)
+    return (uint8_t)std::min<uint64_t>(60, (uint64_t)q);
 }
 
 } // namespace

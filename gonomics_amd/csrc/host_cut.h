@@ -1,5 +1,5 @@
 // host_cut.h -- how the host flows cut a batch into sub-batches (gnx_host.hip.h), plain C++: no HIP header needed.
-// Shared by run_host_job, run_best_of and run_summarize, and by tests/cpp/host_cut_test.cpp on the CPU.
+// Shared by run_host_job, run_best_of, run_summarize and run_md, and by tests/cpp/host_cut_test.cpp on the CPU.
 #pragma once
 #include <stdint.h>
 #include <stdlib.h>

@@ -1,8 +1,10 @@
 """SAM lines from the reports of align.MapReadsReport / align.MapReadPairsReport.
 
-Lines() is text formatting only: every number in a line comes out of the report (the alignment summaries of gnx_summarize_*), none
-is computed here from bases.  The MD tag is not written: it needs the target's bases on the host, and the resident reference lives
-on the device.  MAPQ is 255 ("not available"): the library defines no MAPQ formula (second_score is its raw ingredient, written as XS).
+Lines() is text formatting only: every number and letter in a line comes out of the report (the alignment summaries of
+gnx_summarize_*, the MD strings of gnx_md_* and the MAPQs of gnx_mapq_batch), none is computed here from bases.  A report made with
+tags=True carries md and mapq: the MD string is written on the device, where the resident reference lives, and MAPQ follows the
+library's rule (include/gnx_align.h; second_score, its other input, is written as XS).  A report without them gives MAPQ 255 ("not
+available") and no MD tag.
 """
 import numpy as np
 
@@ -35,9 +37,10 @@ def _seq(read, reverse):
 
 
 def Lines(names, reads, report, ref_name, quals=None, paired=False):
-    """One SAM line (the eleven mandatory fields and the tags AS, NM, XS) per read.  report[r] is the dict of read r; with paired=True
+    """One SAM line (the eleven mandatory fields and the tags AS, NM, MD, XS) per read.  report[r] is the dict of read r; with paired=True
     reads 2k and 2k + 1 are mates.  POS = pos + 1; SEQ and QUAL are in reference orientation (reverse-complemented / reversed on
-    strand 1); TLEN is signed, positive on the leftmost mate of a proper pair; NM = n_mismatch + ins_bases + del_bases; XS only where
+    strand 1); TLEN is signed, positive on the leftmost mate of a proper pair; NM = n_mismatch + ins_bases + del_bases; MAPQ = the
+    report's mapq where a mapped read's dict has one, else 255; MD directly behind NM where the dict has a string under md; XS only where
     the report has a second_score.  An unmapped read has RNAME *, POS 0, MAPQ 255, CIGAR * and no tags."""
     out = []
     for r, rep in enumerate(report):
@@ -60,10 +63,12 @@ def Lines(names, reads, report, ref_name, quals=None, paired=False):
         qual = "*"
         if quals is not None:
             qual = quals[r][::-1] if reverse else quals[r]
-        fields = [names[r], str(flag), ref_name if ok else "*", str(rep["pos"] + 1 if ok else 0), "255", _cigar(rep["xcigar"]) if ok else "*",
+        fields = [names[r], str(flag), ref_name if ok else "*", str(rep["pos"] + 1 if ok else 0), str(rep["mapq"]) if ok and "mapq" in rep else "255", _cigar(rep["xcigar"]) if ok else "*",
                   rnext, str(pnext), str(tlen), _seq(reads[r], reverse), qual]
         if ok:
             fields += ["AS:i:%d" % rep["score"], "NM:i:%d" % (rep["n_mismatch"] + rep["ins_bases"] + rep["del_bases"])]
+            if rep.get("md") is not None:
+                fields.append("MD:Z:%s" % rep["md"])
             if rep.get("second_score") is not None:
                 fields.append("XS:i:%d" % rep["second_score"])
         out.append("\t".join(fields))

@@ -106,6 +106,7 @@ typedef struct gnx_timing {
                             11: gnx_seed_candidates ran (ref_seeds.hip.h): fill_ms = lookup + vote kernels, dominant_ms = the vote kernels, cells = seed
                             hits that voted, n_launches = vote sub-batches.
                             12: gnx_summarize_* ran (aln_summary.hip.h): fill_ms = dominant_ms = the summary kernels, cells = columns walked.
+                            13: gnx_md_* ran (aln_md.hip.h): fill_ms = dominant_ms = the count and the write kernels, cells = columns walked.
                             Multi-context score calls report the maximum over contexts. */
     int32_t _pad;
     /* host-buffer entry points only (wall clock inside the library): */
@@ -352,8 +353,8 @@ typedef struct gnx_pair_opts {
  *                        combination exists and P >= U: the mates get that combination, out_proper[k] = 1, out_tlen[k] = E(v) - A(f).
  *                        Otherwise each mate gets its own first maximum, out_proper[k] = 0, out_tlen[k] = 0.  A mate without candidates
  *                        gets -1 / 0 / 0 / 0 and an empty CIGAR, and its partner is placed alone: not an error.
- *   out_second_score[r]  the highest score among read r's candidates other than the chosen one, INT64_MIN when there is none: the raw
- *                        ingredient of a MAPQ (the library defines no MAPQ formula).
+ *   out_second_score[r]  the highest score among read r's candidates other than the chosen one, INT64_MIN when there is none: with
+ *                        out_score[r] the input of gnx_mapq_batch.
  *   out_score[r], CIGAR  what gnx_align_batch_windows returns for the chosen pair under gnx_best_of_*'s local roles, quirks included,
  *                        checkersize_* honoured; without a CIGAR stage out_score[r] is the chosen candidate's score.
  *   out_target_start / _end[r]  the chosen candidate's span values, relative to its window: the CIGAR's leading GNX_COL_D run and the
@@ -483,6 +484,56 @@ int gnx_summarize_batch_by_offset(const gnx_params *p, int64_t n_pairs, const ui
                                   const int64_t *ref_start, const int64_t *ref_len,
                                   const gnx_cigar *ops, const int64_t *ops_off,
                                   gnx_aln_summary *out, gnx_cigar **out_xops, int64_t **out_xops_off);
+
+/* ---- MD strings: the reference letters of a finished alignment (an extension; SAM's MD:Z tag) -------------------------------------- */
+/* The MD string of every pair of a batch, written on the device: the resident reference exists there only (2 bits per base), so
+ * nothing else can name the reference base under a substitution or a deletion.  Sequences, ops and ops_off as in the gnx_summarize_*
+ * twin.  Outputs, both required, malloc'd (gnx_free): *out_md = the strings' bytes one behind the other, no terminators;
+ * (*out_md_off)[n_pairs + 1], starting at 0: pair k's string is (*out_md)[off[k] .. off[k + 1]).
+ * Contract.  Everything is a function of the pair's column sequence as gnx_summarize_* defines it (runs of length 0 vanish, adjacent equal
+ * ops are one run, anchored at (0, 0)).  ALPHA IS THE DESCRIBED (REFERENCE) SIDE: M and D consume it.  Letters are "ACGTN"[code]; equality is
+ * equality of bytes, so N against N is equal, exactly as n_equal counts.
+ *   Range   GNX_AFFINE_GAP_LOCAL: the leading maximal D run and the trailing maximal D run are outside (the free end gaps, the columns
+ *           the summary un-charges); a sequence that is one D run has nothing inside.  Every other mode: all columns are inside.
+ *   Walk    the inside columns in order with a counter run = 0:
+ *             M, equal bytes       run += 1
+ *             M, different bytes   emit dec(run), the alpha letter; run = 0
+ *             I                    nothing: the counter runs on across it
+ *             D whose previous COLUMN (an I column counts) is not an inside D column    emit dec(run), '^', the alpha letter; run = 0
+ *             D directly behind an inside D column                                      emit the alpha letter only
+ *           and at the end emit dec(run).
+ * Every string matches [0-9]+(([A-Z]|\^[A-Z]+)[0-9]+)*; an alignment with nothing inside gives "0".  The numbers sum to the summary's
+ * n_equal, the letters outside ^ groups number n_mismatch, the letters inside ^ groups number del_bases.
+ * E.g. alpha ACGTACGTAC, beta ACGAACTAC, 6M 1D 3M: "3T2^G3"; beta TTTACG, 3D 2I 4M 3D: "4" in GNX_AFFINE_GAP_LOCAL, "0^ACG4^TAC0" elsewhere.
+ * gnx_md_batch and _windows take all five modes.  _by_offset takes GNX_AFFINE_GAP_LOCAL only: there the window of the resident reference
+ * is alpha, while in the global modes _by_offset makes the read alpha and the string would spell the read; any other mode is GNX_EINVAL
+ * (gnx_best_pair_*'s rule).
+ * Return codes are the summary twin's, all before any output is written: GNX_EINVAL for a null required pointer (out_md and out_md_off
+ * included), a negative count, an unknown mode, ops_off not starting at 0 or decreasing, an op > 2, a negative run length, a CIGAR that
+ * consumes more than its alpha or beta holds, a window outside its buffer or the reference, a sequence of 2^30 bases or more; GNX_EBASE
+ * exactly where the align twin reports it (a byte >= 5 anywhere in either sequence); GNX_EDEVICE without a device, after the argument
+ * checks (no CPU fallback); n_pairs == 0: GNX_OK with off = {0}; never GNX_ERANGE.
+ * Runs on context 0.  aln_md_kernel (aln_md.hip.h) has aln_summary_kernel's geometry; a first instantiation counts each pair's bytes, the
+ * scan family turns the counts into offsets, a second one writes.  Calls are cut into launches of GNX_HOST_SUB pairs.  Switches, read per
+ * call: GNX_MD_SUB=<pairs> overrides that cut; GNX_MD_FORM=0 / 1 walks every M and D run a lane per column / a lane per run (same bytes).
+ * gnx_get_timing afterwards: fast_path 13. */
+int gnx_md_batch(const gnx_params *p, int64_t n_pairs,
+                 const uint8_t *alpha_cat, const int64_t *alpha_off, const uint8_t *beta_cat, const int64_t *beta_off,
+                 const gnx_cigar *ops, const int64_t *ops_off, char **out_md, int64_t **out_md_off);
+int gnx_md_batch_windows(const gnx_params *p, int64_t n_pairs,
+                         const uint8_t *alpha_buf, int64_t alpha_buf_len, const int64_t *alpha_start, const int64_t *alpha_len,
+                         const uint8_t *beta_buf, int64_t beta_buf_len, const int64_t *beta_start, const int64_t *beta_len,
+                         const gnx_cigar *ops, const int64_t *ops_off, char **out_md, int64_t **out_md_off);
+int gnx_md_batch_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *read_cat, const int64_t *read_off,
+                           const int64_t *ref_start, const int64_t *ref_len,
+                           const gnx_cigar *ops, const int64_t *ops_off, char **out_md, int64_t **out_md_off);
+/* The MAPQ of n placements from each one's score S = score[r] and the best score among its other candidates, second_score[r] (INT64_MIN:
+ * there is none -- gnx_best_pair_*'s out_second_score as it comes).  This is THIS LIBRARY's rule, not BWA's and not Bowtie's:
+ *   S <= 0: 0;   s2 = second_score[r] < 0 ? 0 : second_score[r] (INT64_MIN included);   s2 >= S: 0;
+ *   otherwise min(60, floor(60 * (S - s2) / S)), exact for every int64 S (the product is taken 128 bits wide).
+ * E.g. (400, none) 60, (400, 200) 30, (400, 399) 0, (400, 1) 59, (61, 1) 59, (2^62, 2^61) 30.
+ * Pure host arithmetic: no device, no gnx_init.  n < 0, or a null pointer with n > 0: GNX_EINVAL. */
+int gnx_mapq_batch(int64_t n, const int64_t *score, const int64_t *second_score, uint8_t *out_mapq);
 
 int gnx_get_timing(gnx_timing *out);
 /* Diagnostics (tests only; nothing in the reference corresponds to it): launch n_workgroups workgroups that each hold one CU's whole

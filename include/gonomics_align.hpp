@@ -446,6 +446,54 @@ inline std::string FormatXCigar(const std::vector<Cigar> &route) { // e.g. "12=1
     return s.empty() ? "*" : s;
 }
 
+// ---- MD strings (gnx_md_*, an extension) and the library's MAPQ rule (gnx_mapq_batch).  alphas[k] is the DESCRIBED side: the reference of
+// SAM's MD:Z tag, whose letters stand under every substitution and deletion ("3T2^G3").  gnx_align.h defines both.
+namespace detail {
+// by_offset: alphas = the reads (the queries), betas unused, windows = (start, len) of the resident reference (the described side)
+inline std::vector<std::string> md_tags(const gnx_params &p, const std::vector<std::vector<dna::Base>> &alphas, const std::vector<std::vector<dna::Base>> *betas,
+                                        const std::vector<std::pair<int64_t, int64_t>> *windows, const std::vector<std::vector<Cigar>> &routes) {
+    const int64_t n = (int64_t)routes.size();
+    std::vector<dna::Base> acat, bcat;
+    std::vector<int64_t> aoff, boff, ooff((size_t)n + 1, 0), ws, wl;
+    std::vector<gnx_cigar> ops;
+    flatten(alphas, acat, aoff);
+    if (betas) flatten(*betas, bcat, boff);
+    else for (const auto &w : *windows) { ws.push_back(w.first); wl.push_back(w.second); }
+    ws.push_back(0); wl.push_back(0);
+    for (int64_t k = 0; k < n; k++) {
+        for (const Cigar &c : routes[(size_t)k]) { gnx_cigar g{}; g.run_length = c.RunLength; g.op = c.Op; ops.push_back(g); }
+        ooff[(size_t)k + 1] = (int64_t)ops.size();
+    }
+    ops.push_back(gnx_cigar{});
+    char *md = nullptr;
+    int64_t *off = nullptr;
+    const int rc = betas ? gnx_md_batch(&p, n, acat.data(), aoff.data(), bcat.data(), boff.data(), ops.data(), ooff.data(), &md, &off)
+                         : gnx_md_batch_by_offset(&p, n, acat.data(), aoff.data(), ws.data(), wl.data(), ops.data(), ooff.data(), &md, &off);
+    if (rc) raise(rc);
+    std::vector<std::string> res((size_t)n);
+    for (int64_t k = 0; k < n; k++) res[(size_t)k].assign(md + off[k], md + off[k + 1]);
+    gnx_free(md); gnx_free(off);
+    return res;
+}
+} // namespace detail
+inline std::vector<std::string> MDTags(int mode, const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, const std::vector<std::vector<dna::Base>> &alphas,
+                                       const std::vector<std::vector<dna::Base>> &betas, const std::vector<std::vector<Cigar>> &routes) {
+    return detail::md_tags(detail::params(mode, scores, gapOpen, gapExtend, 10000, 10000), alphas, &betas, nullptr, routes);
+}
+// reads (queries, in the orientation they were aligned in) against windows (start, len) of the resident reference; GNX_AFFINE_GAP_LOCAL
+inline std::vector<std::string> MDTagsByOffset(const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, const std::vector<std::vector<dna::Base>> &reads,
+                                               const std::vector<std::pair<int64_t, int64_t>> &windows, const std::vector<std::vector<Cigar>> &routes) {
+    return detail::md_tags(detail::params(GNX_AFFINE_GAP_LOCAL, scores, gapOpen, gapExtend, 10000, 10000), reads, nullptr, &windows, routes);
+}
+// secondScores[r] = INT64_MIN: read r has no other candidate
+inline std::vector<int> Mapq(const std::vector<int64_t> &scores, const std::vector<int64_t> &secondScores) {
+    if (scores.size() != secondScores.size()) detail::raise(GNX_EINVAL);
+    std::vector<uint8_t> q(scores.size() + 1);
+    const int rc = gnx_mapq_batch((int64_t)scores.size(), scores.data(), secondScores.data(), q.data());
+    if (rc) detail::raise(rc);
+    return std::vector<int>(q.begin(), q.end() - 1);
+}
+
 inline void AffineGapLocalEngine(const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, std::vector<TargetQueryPair> &pairs) {
     std::vector<std::vector<dna::Base>> t, q;
     for (auto &p : pairs) { t.push_back(p.Target); q.push_back(p.Query); }
