@@ -26,7 +26,8 @@ EXPORTS = ["gnx_device_count", "gnx_init", "gnx_shutdown", "gnx_last_error", "gn
            "gnx_best_of_by_offset", "gnx_best_of_windows", "gnx_best_pair_by_offset", "gnx_best_pair_windows",
            "gnx_reference_index_build", "gnx_reference_index_info", "gnx_reference_index_get", "gnx_seed_candidates",
            "gnx_summarize_batch", "gnx_summarize_batch_windows", "gnx_summarize_batch_by_offset",
-           "gnx_md_batch", "gnx_md_batch_windows", "gnx_md_batch_by_offset", "gnx_mapq_batch"]
+           "gnx_md_batch", "gnx_md_batch_windows", "gnx_md_batch_by_offset", "gnx_mapq_batch",
+           "gnx_pileup_open", "gnx_pileup_info", "gnx_pileup_add_by_offset", "gnx_pileup_get", "gnx_pileup_calls", "gnx_pileup_close"]
 GNX_XCOL_EQ, GNX_XCOL_X = 3, 4
 
 
@@ -68,6 +69,18 @@ class GnxAlnSummary(ctypes.Structure):
 
 
 SUMMARY_DTYPE = np.dtype([(f, np.int64) for f in SUMMARY_FIELDS] + [("_reserved", np.int64)])
+
+
+class GnxPileCallOpts(ctypes.Structure):
+    _fields_ = [("min_depth", ctypes.c_int32), ("min_alt", ctypes.c_int32), ("frac_num", ctypes.c_int32), ("frac_den", ctypes.c_int32),
+                ("both_strands", ctypes.c_int32), ("_reserved", ctypes.c_int32)]
+
+
+# gnx_pile: one reference position, 64 bytes; gnx_pile_call: one call, 24 bytes
+PILE_DTYPE = np.dtype([("base", np.int32, (2, 5)), ("del", np.int32, (2,)), ("ins", np.int32, (2,)), ("_reserved", np.int32, (2,))])
+PILE_CALL_DTYPE = np.dtype({"names": ["pos", "depth", "count", "count_fwd", "kind", "ref", "alt", "_pad"],
+                            "formats": [np.int64, np.int32, np.int32, np.int32, np.uint8, np.uint8, np.uint8, np.uint8],
+                            "offsets": [0, 8, 12, 16, 20, 21, 22, 23], "itemsize": 24})
 
 
 class GnxError(RuntimeError):
@@ -183,6 +196,19 @@ def lib():
             L.gnx_md_batch_by_offset.restype = ctypes.c_int
             L.gnx_mapq_batch.argtypes = [i64, c_p, c_p, c_p]
             L.gnx_mapq_batch.restype = ctypes.c_int
+        if hasattr(L, "gnx_pileup_open"):
+            L.gnx_pileup_open.argtypes = [i64, i64]
+            L.gnx_pileup_open.restype = ctypes.c_int
+            L.gnx_pileup_info.argtypes = [c_p, c_p, c_p, c_p]
+            L.gnx_pileup_info.restype = ctypes.c_int
+            L.gnx_pileup_add_by_offset.argtypes = [ctypes.POINTER(GnxParams), i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]
+            L.gnx_pileup_add_by_offset.restype = ctypes.c_int
+            L.gnx_pileup_get.argtypes = [i64, i64, c_p]
+            L.gnx_pileup_get.restype = ctypes.c_int
+            L.gnx_pileup_calls.argtypes = [ctypes.POINTER(GnxPileCallOpts), ctypes.POINTER(c_p), ctypes.POINTER(i64)]
+            L.gnx_pileup_calls.restype = ctypes.c_int
+            L.gnx_pileup_close.argtypes = []
+            L.gnx_pileup_close.restype = ctypes.c_int
         L.gnx_seed_index_build.argtypes = [c_p, c_p, i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(i64)]
         L.gnx_seed_index_build.restype = ctypes.c_int
         L.gnx_seed_index_set.argtypes = [c_p, c_p, i64, c_p, c_p, i64, ctypes.c_int]
@@ -760,6 +786,57 @@ def mapq_batch(scores, second_scores):
     out = np.zeros(max(n, 1), dtype=np.uint8)
     check(lib().gnx_mapq_batch(n, scores.ctypes.data, second_scores.ctypes.data, out.ctypes.data))
     return out[:n]
+
+
+# ---- the pile of the resident reference (gnx_pileup_*) ----
+def pileup_open(start, length):
+    """gnx_pileup_open: a zeroed pile over [start, start + length) of the resident reference; an open one is replaced."""
+    check(lib().gnx_pileup_open(int(start), int(length)))
+
+
+def pileup_close():
+    check(lib().gnx_pileup_close())
+
+
+def pileup_info():
+    """gnx_pileup_info -> {"start", "len", "reads_added", "device_bytes"}"""
+    v = np.zeros(4, dtype=np.int64)
+    check(lib().gnx_pileup_info(v.ctypes.data, v.ctypes.data + 8, v.ctypes.data + 16, v.ctypes.data + 24))
+    return {"start": int(v[0]), "len": int(v[1]), "reads_added": int(v[2]), "device_bytes": int(v[3])}
+
+
+def pileup_add_by_offset(params, read_cat, read_off, ref_start, ref_len, strand, ops, ops_off, use=None):
+    """gnx_pileup_add_by_offset: reads (oriented as aligned) against windows of the resident reference, added to the open pile."""
+    read_cat, read_off, ref_start, ref_len, ops_off, strand = _u8(read_cat), _i64(read_off), _i64(ref_start), _i64(ref_len), _i64(ops_off), _u8(strand)
+    n, ops = int(ref_start.shape[0]), _ops_array(ops)
+    if strand.shape[0] != n or (use is not None and len(use) != n):
+        raise ValueError("pileup_add_by_offset: one strand byte (and one use byte) per pair")
+    use = None if use is None else _u8(use)
+    check(lib().gnx_pileup_add_by_offset(ctypes.byref(params), n, read_cat.ctypes.data, read_off.ctypes.data, ref_start.ctypes.data, ref_len.ctypes.data,
+                                         strand.ctypes.data if n else None, ops.ctypes.data, ops_off.ctypes.data, None if use is None else use.ctypes.data))
+
+
+def pileup_get(first=0, count=None):
+    """gnx_pileup_get: rows first .. first + count of the open pile (count None: to the end of the region) as PILE_DTYPE."""
+    if count is None:
+        count = pileup_info()["len"] - int(first)
+    out = np.zeros(max(int(count), 1), dtype=PILE_DTYPE)
+    check(lib().gnx_pileup_get(int(first), int(count), out.ctypes.data))
+    return out[:max(int(count), 0)]
+
+
+def pileup_calls(min_depth, min_alt, frac_num, frac_den, both_strands=0):
+    """gnx_pileup_calls -> PILE_CALL_DTYPE array, ordered by position"""
+    o = GnxPileCallOpts(int(min_depth), int(min_alt), int(frac_num), int(frac_den), int(both_strands), 0)
+    calls_p, n = ctypes.c_void_p(), ctypes.c_int64(0)
+    check(lib().gnx_pileup_calls(ctypes.byref(o), ctypes.byref(calls_p), ctypes.byref(n)))
+    try:
+        if n.value:
+            buf = (ctypes.c_char * (n.value * 24)).from_address(calls_p.value)
+            return np.frombuffer(buf, dtype=PILE_CALL_DTYPE, count=n.value).copy()
+        return np.zeros(0, dtype=PILE_CALL_DTYPE)
+    finally:
+        lib().gnx_free(calls_p)
 
 
 def _chunk_pairs(alphas, betas):

@@ -543,6 +543,81 @@ def MapReadPairsReport(params, reads, min_insert, max_insert, unpaired_penalty=0
     return _report(params, reads, placed, extra, tags=tags)
 
 
+# ---- the pile: per-base counts of placed reads on the resident reference, and the calls they give (gnx_pileup_*) ----
+def PileupOpen(start, length):
+    """A zeroed pile over [start, start + length) of the resident reference (gnx_pileup_open); an open pile is replaced.  The pile
+    belongs to the reference: setting or releasing the reference drops it."""
+    try:
+        _lib.pileup_open(start, length)
+    except _lib.GnxError as e:
+        _raise(e)
+
+
+def PileupClose():
+    try:
+        _lib.pileup_close()
+    except _lib.GnxError as e:
+        _raise(e)
+
+
+def PileupInfo():
+    """{"start", "len", "reads_added", "device_bytes"} of the open pile"""
+    try:
+        return _lib.pileup_info()
+    except _lib.GnxError as e:
+        _raise(e)
+
+
+def PileupAdd(params, reads, windows, strands, routes, use=None):
+    """Add finished alignments to the open pile (gnx_pileup_add_by_offset, GNX_AFFINE_GAP_LOCAL): windows[k] = (start, len) of the
+    resident reference, reads[k] in the orientation it was aligned in (a strand-1 winner: its reverse complement), strands[k] in
+    {0, 1} the counter it goes to, routes[k] its CIGAR; use[k] == 0 leaves pair k out.  include/gnx_align.h defines what is counted."""
+    if not routes:
+        return
+    ops, off = _routes_to_ops(routes)
+    r_cat, r_off = _lib._cat(list(reads))
+    try:
+        _lib.pileup_add_by_offset(params, r_cat, r_off, [w[0] for w in windows], [w[1] for w in windows], strands, ops, off, use=use)
+    except _lib.GnxError as e:
+        _raise(e)
+
+
+def PileupGet(first=0, count=None):
+    """Rows first .. first + count of the open pile (count None: to the end of its region): a structured array with base[2][5]
+    ([strand][A C G T N]), del[2] and ins[2] per reference position."""
+    try:
+        return _lib.pileup_get(first, count)
+    except _lib.GnxError as e:
+        _raise(e)
+
+
+def PileupCalls(min_depth, min_alt, frac=(1, 2), both_strands=False):
+    """The positions where the reads disagree with the reference, by the library's rule (gnx_pileup_calls): one dict per call, ordered
+    by position -- pos, depth, count, count_fwd, kind ("sub" / "del" / "ins"), ref, alt (a base code for a substitution, else None)."""
+    try:
+        calls = _lib.pileup_calls(min_depth, min_alt, frac[0], frac[1], 1 if both_strands else 0)
+    except _lib.GnxError as e:
+        _raise(e)
+    kinds = ("sub", "del", "ins")
+    return [{"pos": int(c["pos"]), "depth": int(c["depth"]), "count": int(c["count"]), "count_fwd": int(c["count_fwd"]), "kind": kinds[int(c["kind"])],
+             "ref": int(c["ref"]), "alt": int(c["alt"]) if int(c["kind"]) == 0 else None} for c in calls]
+
+
+def PileupAddReport(params, reads, report, min_mapq=0):
+    """Add the placed reads of a MapReadsReport / MapReadPairsReport(tags=True) report whose mapq is at least min_mapq, in ONE call:
+    strand-1 reads go in as their reverse complements (as the report's own summaries took them), the window is window_start and the
+    alpha bases the route consumes, and `use` leaves out the reads below min_mapq.  Returns how many reads it added."""
+    idx = [r for r, d in enumerate(report) if d["best"] >= 0]
+    if not idx:
+        return 0
+    oriented = [dna.ReverseComplement(np.array(reads[r], dtype=np.uint8)) if report[r]["strand"] else reads[r] for r in idx]  # (it works in place: on a copy)
+    routes = [report[r]["route"] for r in idx]
+    windows = [(report[r]["window_start"], sum(c[0] for c in route if c[1] != ColI)) for r, route in zip(idx, routes)]
+    use = [1 if report[r]["mapq"] >= min_mapq else 0 for r in idx]
+    PileupAdd(params, oriented, windows, [report[r]["strand"] for r in idx], routes, use=use)
+    return sum(use)
+
+
 def AffineGapChunk(alpha, beta, scores, gapOpen, gapExtend, chunkSize):
     """align.AffineGapChunk (/root/reference/align/affineGap_highMem.go:227-268)."""
     try:

@@ -58,6 +58,7 @@
 #include "ref_seeds.hip.h"
 #include "aln_summary.hip.h"
 #include "aln_md.hip.h"
+#include "pileup.hip.h"
 
 namespace {
 
@@ -152,6 +153,9 @@ struct Ctx {
     DevBuf ri_keys, ri_pos, ri_dir, rs[15];
     int ri_dir_bits = 0; // ri_dir: 2^bits + 1 first entries by key prefix (ref_index_dir_kernel)
     int64_t ri_n = -1, ri_epoch = 0; int ri_seed_len = 0, ri_seed_step = 0; // ri_n >= 0: an index of that many k-mers of the reference of epoch ri_epoch is built
+    // the pile of the resident reference (gnx_pileup_*; context 0 only): PILE_PLANES planes of pl_len counters, and the scratch of a call
+    DevBuf pl_tab, pl_in, pl_cnt, pl_off, pl_calls;
+    int64_t pl_start = 0, pl_len = -1, pl_reads = 0; // pl_len >= 0: a pile over [pl_start, pl_start + pl_len) is open; reads added so far
     PinBuf h_plans; // host-side plans of the general path
     PinBuf st_a[2], st_as[2], st_b[2], st_bs[2];
     // the resident reference, PACKED (gnx_host.hip.h: pack_reference): `ref` = 2 bits per base, ref_flag / ref_rank / ref_exc = the
@@ -2740,6 +2744,11 @@ void drop_reference_index(Ctx &c) {
     c.ri_keys.release(); c.ri_pos.release(); c.ri_dir.release();
     for (DevBuf &b : c.rs) b.release();
 }
+// ... and so does the pile (gnx_pileup_*), though not to a rebuilt index: its counts are positions of THAT reference
+void drop_pile(Ctx &c) {
+    c.pl_len = -1; c.pl_start = 0; c.pl_reads = 0;
+    c.pl_tab.release(); c.pl_in.release(); c.pl_cnt.release(); c.pl_off.release(); c.pl_calls.release();
+}
 std::atomic<int64_t> g_sv_lds{0}, g_sv_slab{0}; // reads voted with the table in LDS / in a slab (gnx_debug_counter(7 / 8))
 
 } // namespace
@@ -2855,6 +2864,7 @@ void gnx_shutdown(void) {
         for (DevBuf &b : c.bo) b.release();
         for (DevBuf &b : c.sm) b.release();
         drop_reference_index(c);
+        drop_pile(c);
         PinBuf *pins[] = {&c.h_plans, &c.st_a[0], &c.st_a[1], &c.st_as[0], &c.st_as[1], &c.st_b[0], &c.st_b[1], &c.st_bs[0], &c.st_bs[1]};
         for (PinBuf *b : pins) b->release();
         c.fpc_ptr = nullptr; c.ref_len = -1; c.sd_n = -1;
@@ -3114,6 +3124,53 @@ int gnx_md_batch_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *
     if (p->mode != GNX_AFFINE_GAP_LOCAL) { set_err("gnx_md_batch_by_offset takes GNX_AFFINE_GAP_LOCAL only (the window is the described side there), not mode %s%lld", "", (long long)p->mode); return GNX_EINVAL; }
     const std::vector<int64_t> rl = lengths_of(read_off, n_pairs);
     return run_md(p, n_pairs, ref_side(ref_start, ref_len), cat_side(read_cat, read_off, n_pairs, rl), ops, ops_off, out_md, out_md_off);
+}
+
+/* ---- the pile of the resident reference: per-position counts of placed reads, and the calls they give (gnx_align.h) ---- */
+int gnx_pileup_open(int64_t region_start, int64_t region_len) {
+    ApiCall api;
+    return run_pile_open(region_start, region_len);
+}
+
+int gnx_pileup_info(int64_t *out_start, int64_t *out_len, int64_t *out_reads_added, int64_t *out_device_bytes) {
+    ApiCall api;
+    Ctx &c = ctx_at(0);
+    CtxScope scope(c);
+    if (int rc = need_pile(c)) return rc;
+    if (out_start) *out_start = c.pl_start;
+    if (out_len) *out_len = c.pl_len;
+    if (out_reads_added) *out_reads_added = c.pl_reads;
+    if (out_device_bytes) *out_device_bytes = c.pl_len * PILE_PLANES * (int64_t)sizeof(int);
+    return GNX_OK;
+}
+
+int gnx_pileup_add_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *read_cat, const int64_t *read_off, const int64_t *ref_start, const int64_t *ref_len,
+                             const uint8_t *strand, const gnx_cigar *ops, const int64_t *ops_off, const uint8_t *use) {
+    ApiCall api;
+    if (!p || n_pairs < 0 || !read_off || !ref_start || !ref_len) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (p->mode != GNX_AFFINE_GAP_LOCAL) { set_err("gnx_pileup_add_by_offset takes GNX_AFFINE_GAP_LOCAL only (the window is the described side there), not mode %s%lld", "", (long long)p->mode); return GNX_EINVAL; }
+    const std::vector<int64_t> rl = lengths_of(read_off, n_pairs);
+    return run_pile_add(p, n_pairs, ref_side(ref_start, ref_len), cat_side(read_cat, read_off, n_pairs, rl), strand, ops, ops_off, use);
+}
+
+int gnx_pileup_get(int64_t first, int64_t count, gnx_pile *out) {
+    ApiCall api;
+    return run_pile_get(first, count, out);
+}
+
+int gnx_pileup_calls(const gnx_pile_call_opts *o, gnx_pile_call **out_calls, int64_t *out_n) {
+    ApiCall api;
+    return run_pile_calls(o, out_calls, out_n);
+}
+
+int gnx_pileup_close(void) {
+    ApiCall api;
+    Ctx &c = ctx_at(0);
+    CtxScope scope(c);
+    if (c.pl_len < 0) return GNX_OK;
+    if (c.inited) { (void)hipSetDevice(c.device); (void)hipStreamSynchronize(c.own_stream); }
+    drop_pile(c);
+    return GNX_OK;
 }
 
 int gnx_mapq_batch(int64_t n, const int64_t *score, const int64_t *second_score, uint8_t *out_mapq) {

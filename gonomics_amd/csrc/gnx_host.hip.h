@@ -201,6 +201,7 @@ int set_reference_packed(const uint8_t *ref, int64_t len, uint64_t seed) {
         hipStream_t st = c0.own_stream;
         c0.ref_len = -1;
         drop_reference_index(c0); // (before anything can fail: an index never outlives the reference it was built from)
+        drop_pile(c0);            // (nor does a pile)
         if (len == 0) { // release: every context gives the reference (and the unpacked-window scratch) back; nothing is re-allocated
             int n_all0; { std::lock_guard<std::mutex> lk(g_ctxs_mu); n_all0 = (int)g_ctxs.size(); }
             for (int d = 0; d < n_all0; d++) {
@@ -1374,6 +1375,212 @@ int run_md(const gnx_params *prm, int64_t n_pairs, const SeqSide &sa, const SeqS
         if (!md) { set_err("pinned host allocation failed%s", ""); return fail(GNX_ENOMEM); }
     }
     *out_md = md; *out_md_off = off;
+    t.dominant_ms = t.total_ms = t.fill_ms; t.dominant_launches = t.n_launches;
+    t.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count();
+    c.timing = t;
+    return GNX_OK;
+}
+
+// ---- gnx_pileup_*: per-position counts of placed reads beside the resident reference, and the calls they give (pileup.hip.h; contract: gnx_align.h) ----
+// One pile, on context 0, owned by the resident reference (drop_pile).  Every entry takes the context's lock before it looks at the
+// pile; "no open pile" needs no device and is answered before ensure_init.
+int need_pile(const Ctx &c) {
+    if (c.pl_len >= 0) return GNX_OK;
+    set_err("no open pile: call gnx_pileup_open first%s", "");
+    return GNX_EINVAL;
+}
+
+int run_pile_open(int64_t region_start, int64_t region_len) {
+    if (region_start < 0 || region_len < 1) { set_err("a pile's region holds at least one position of the reference%s", ""); return GNX_EINVAL; }
+    Ctx &c = ctx_at(0);
+    CtxScope scope(c);
+    int rc;
+    if ((rc = ensure_init())) return rc;
+    if (c.ref_len < 0) { set_err("no resident reference: call gnx_set_reference first%s", ""); return GNX_EINVAL; }
+    if (region_len > c.ref_len - region_start) { set_err("the region ends outside the reference of %s%lld bases", "", (long long)c.ref_len); return GNX_EINVAL; }
+    // beside the open pile, which stays as it was when this one does not fit
+    const size_t bytes = (size_t)region_len * PILE_PLANES * sizeof(int);
+    void *q = nullptr;
+    if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); set_err("device allocation of %s%lld bytes failed", "", (long long)bytes); return GNX_ENOMEM; }
+    if (hipMemsetAsync(q, 0, bytes, c.own_stream) != hipSuccess || hipStreamSynchronize(c.own_stream) != hipSuccess) {
+        set_err_hip(hipGetLastError(), __FILE__, __LINE__);
+        (void)hipFree(q);
+        return GNX_EDEVICE;
+    }
+    c.pl_tab.release();
+    c.pl_tab.p = q; c.pl_tab.cap = bytes;
+    c.pl_start = region_start; c.pl_len = region_len; c.pl_reads = 0;
+    return GNX_OK;
+}
+
+// gnx_md_batch_by_offset's checks and uploads (sa = the windows, sb = the reads), the base check over every launch cut, ONE read-back of
+// its flag -- nothing may change the pile before every error is known --, then pile_add_kernel per sub-batch of GNX_HOST_SUB pairs
+// (GNX_PILE_SUB=<pairs> overrides the cut).
+int run_pile_add(const gnx_params *prm, int64_t n_pairs, const SeqSide &sa, const SeqSide &sb, const uint8_t *strand, const gnx_cigar *ops, const int64_t *ops_off,
+                 const uint8_t *use) {
+    const auto t_entry = std::chrono::steady_clock::now();
+    int rc;
+    int64_t cells = 0;
+    if ((rc = check_cigar_call(prm, n_pairs, sa, sb, ops, ops_off, strand != nullptr || n_pairs == 0, true, cells))) return rc;
+    int64_t n_use = 0;
+    cells = 0; // of the added pairs
+    for (int64_t q = 0; q < n_pairs; q++) {
+        if (strand[q] > 1) { set_err("strand byte > 1 at pair %s%lld", "", (long long)q); return GNX_EINVAL; }
+        if (use && !use[q]) continue;
+        n_use++;
+        for (int64_t x = ops_off[q]; x < ops_off[q + 1]; x++) cells += ops[x].run_length;
+    }
+    Ctx &c = ctx_at(0);
+    CtxScope scope(c);
+    if ((rc = need_pile(c))) return rc;
+    if (n_use > (int64_t)INT32_MAX - c.pl_reads) { set_err("more than 2^31 - 1 reads in one pile (its counters are int32)%s", ""); return GNX_EINVAL; }
+    if (n_pairs == 0) return GNX_OK;
+    if ((rc = ensure_init())) return rc;
+    g_transport = 0; g_bcast_ms = 0;
+    if ((rc = check_resident_windows(c, n_pairs, sa, sb))) return rc;
+    hipStream_t st = c.own_stream;
+    gnx_timing t = {};
+    t.fast_path = 14; t.cells = cells; t.n_contexts = 1;
+    int64_t sub = gnx_host_sub(getenv("GNX_HOST_SUB"));
+    if (const char *e = getenv("GNX_PILE_SUB")) sub = std::max<int64_t>(atoll(e), 1);
+    int cut = 64;
+    if (const char *e = getenv("GNX_PILE_FORM")) cut = e[0] == '0' ? 1 : e[0] == '1' ? 0x7fffffff : 64;
+    DevBuf *sm = c.sm;
+    const size_t np = (size_t)n_pairs;
+    auto run = [&]() -> int {
+        SumArgs a;
+        int pk, r;
+        if ((r = sum_upload(c, st, prm, n_pairs, sa, sb, ops, ops_off, a, pk))) return r;
+        if ((r = c.pl_in.ensure(2 * np))) return r;
+        HIPCHK(hipMemcpyAsync(c.pl_in.p, strand, np, hipMemcpyHostToDevice, st));
+        if (use) HIPCHK(hipMemcpyAsync((uint8_t *)c.pl_in.p + np, use, np, hipMemcpyHostToDevice, st));
+        HIPCHK(hipEventRecord(c.ev[0], st));
+        for (int64_t b = 0; b < n_pairs; b += sub) launch_sum_bases(sum_sub_args(a, sm, b, std::min(sub, n_pairs - b)), pk, sa, sb, b, std::min(sub, n_pairs - b), st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c.ev[1], st));
+        int ef = 0;
+        HIPCHK(hipMemcpyAsync(&ef, sm[SM_MISC].p, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st)); // (also: the sources are pageable memory of the caller -- no return while a copy may still read them)
+        if (ef & 1) { set_err("a base >= 5 was found: the reference would panic (index out of range)%s", ""); return GNX_EBASE; }
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+        t.fill_ms = ms;
+        if (n_use == 0) return GNX_OK;
+        PileArgs pa;
+        pa.reads = (const uint8_t *)sm[SM_B].p; pa.ops = (const gnx_cigar *)sm[SM_OPS].p; pa.cut = cut;
+        pa.pile = (int *)c.pl_tab.p; pa.region_start = c.pl_start; pa.region_len = c.pl_len;
+        HIPCHK(hipEventRecord(c.ev[2], st));
+        for (int64_t b = 0; b < n_pairs; b += sub) {
+            const int64_t cnt = std::min(sub, n_pairs - b);
+            pa.read_start = (const int64_t *)sm[SM_BS].p + b; pa.ref_start = (const int64_t *)sm[SM_AS].p + b; pa.ops_off = (const int64_t *)sm[SM_OFF].p + b;
+            pa.strand = (const uint8_t *)c.pl_in.p + b; pa.use = use ? (const uint8_t *)c.pl_in.p + np + b : nullptr;
+            pa.n_pairs = cnt;
+            hipLaunchKernelGGL(pile_add_kernel, dim3((unsigned)std::min<int64_t>((cnt + 3) / 4, 1 << 20)), dim3(256), 0, st, pa);
+            HIPCHK(hipGetLastError());
+            t.n_launches++;
+        }
+        HIPCHK(hipEventRecord(c.ev[3], st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipEventElapsedTime(&ms, c.ev[2], c.ev[3]));
+        t.fill_ms += ms; t.dominant_ms = ms; // (dominant_ms: pile_add_kernel alone)
+        return GNX_OK;
+    };
+    if ((rc = run())) { (void)hipStreamSynchronize(st); return rc; }
+    c.pl_reads += n_use;
+    t.total_ms = t.fill_ms; t.dominant_launches = t.n_launches;
+    t.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count();
+    c.timing = t;
+    return GNX_OK;
+}
+
+// rows for the caller: the planes come down a slab of rows at a time and are transposed here
+int run_pile_get(int64_t first, int64_t count, gnx_pile *out) {
+    Ctx &c = ctx_at(0);
+    CtxScope scope(c);
+    int rc;
+    if ((rc = need_pile(c))) return rc;
+    if (first < 0 || count < 0 || count > c.pl_len - first || (count > 0 && !out)) { set_err("rows outside the pile's region%s", ""); return GNX_EINVAL; }
+    if (count == 0) return GNX_OK;
+    if ((rc = ensure_init())) return rc;
+    const int64_t slab = std::min<int64_t>(count, (int64_t)1 << 20);
+    std::vector<int> h((size_t)slab * PILE_PLANES);
+    for (int64_t b = 0; b < count; b += slab) {
+        const int64_t n = std::min(slab, count - b);
+        for (int pl = 0; pl < PILE_PLANES; pl++)
+            HIPCHK(hipMemcpyAsync(h.data() + (size_t)pl * (size_t)slab, (const int *)c.pl_tab.p + (size_t)pl * (size_t)c.pl_len + (size_t)(first + b), (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c.own_stream));
+        HIPCHK(hipStreamSynchronize(c.own_stream));
+        for (int64_t k = 0; k < n; k++) {
+            gnx_pile &row = out[b + k];
+            for (int s = 0; s < 2; s++) {
+                for (int x = 0; x < 5; x++) row.base[s][x] = h[(size_t)(s * 5 + x) * (size_t)slab + (size_t)k];
+                row.del[s] = h[(size_t)(PILE_DEL + s) * (size_t)slab + (size_t)k];
+                row.ins[s] = h[(size_t)(PILE_INS + s) * (size_t)slab + (size_t)k];
+                row._reserved[s] = 0;
+            }
+        }
+    }
+    return GNX_OK;
+}
+
+// pile_call_kernel<false>, the scan of the tiles' counts, one read-back that sizes the list, pile_call_kernel<true>
+int run_pile_calls(const gnx_pile_call_opts *o, gnx_pile_call **out_calls, int64_t *out_n) {
+    const auto t_entry = std::chrono::steady_clock::now();
+    if (!o || !out_calls || !out_n) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (o->min_depth < 1 || o->min_alt < 1 || o->frac_num < 1 || o->frac_num > o->frac_den || o->frac_den > (1 << 20) || o->both_strands < 0 || o->both_strands > 1) {
+        set_err("gnx_pile_call_opts: min_depth >= 1, min_alt >= 1, 1 <= frac_num <= frac_den <= 2^20, both_strands 0 or 1%s", ""); return GNX_EINVAL;
+    }
+    Ctx &c = ctx_at(0);
+    CtxScope scope(c);
+    int rc;
+    if ((rc = need_pile(c))) return rc;
+    if ((rc = ensure_init())) return rc;
+    g_transport = 0; g_bcast_ms = 0;
+    hipStream_t st = c.own_stream;
+    gnx_timing t = {};
+    t.fast_path = 15; t.cells = c.pl_len; t.n_contexts = 1;
+    const int64_t n_tiles = (c.pl_len + PILE_TILE - 1) / PILE_TILE;
+    gnx_pile_call *calls = nullptr;
+    int64_t total = 0;
+    auto run = [&]() -> int {
+        int r;
+        if ((r = c.pl_cnt.ensure((size_t)(n_tiles + 1) * 8)) || (r = c.pl_off.ensure((size_t)(n_tiles + 1) * 8))) return r;
+        int64_t *d_carry = (int64_t *)c.pl_cnt.p + n_tiles;
+        HIPCHK(hipMemsetAsync(d_carry, 0, 8, st));
+        PileCallArgs a;
+        memset(&a, 0, sizeof(a));
+        a.kp.b2 = (const unsigned *)c.ref.p; a.kp.bflag = (const unsigned long long *)c.ref_flag.p; a.kp.brank = (const unsigned *)c.ref_rank.p; a.kp.bexc = (const unsigned long long *)c.ref_exc.p;
+        a.pile = (const int *)c.pl_tab.p; a.region_start = c.pl_start; a.region_len = c.pl_len; a.n_tiles = n_tiles;
+        a.min_depth = o->min_depth; a.min_alt = o->min_alt; a.frac_num = o->frac_num; a.frac_den = o->frac_den; a.both_strands = o->both_strands;
+        a.cnt = (int64_t *)c.pl_cnt.p; a.off = (const int64_t *)c.pl_off.p;
+        const dim3 grid((unsigned)std::min<int64_t>((n_tiles + 3) / 4, 1 << 20));
+        HIPCHK(hipEventRecord(c.ev[0], st));
+        hipLaunchKernelGGL(pile_call_kernel<false>, grid, dim3(256), 0, st, a);
+        HIPCHK(hipGetLastError());
+        if ((r = launch_scan(a.cnt, (int)n_tiles, (int64_t *)c.pl_off.p, d_carry, st))) return r;
+        HIPCHK(hipEventRecord(c.ev[1], st));
+        HIPCHK(hipMemcpyAsync(&total, (const int64_t *)c.pl_off.p + n_tiles, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+        t.fill_ms = ms; t.n_launches = 1;
+        calls = (gnx_pile_call *)g_pool.get((size_t)std::max<int64_t>(total, 1) * sizeof(gnx_pile_call));
+        if (!calls) { set_err("pinned host allocation failed%s", ""); return GNX_ENOMEM; }
+        if (total > 0) {
+            if ((r = c.pl_calls.ensure((size_t)total * sizeof(gnx_pile_call)))) return r;
+            a.out = (gnx_pile_call *)c.pl_calls.p;
+            HIPCHK(hipEventRecord(c.ev[2], st));
+            hipLaunchKernelGGL(pile_call_kernel<true>, grid, dim3(256), 0, st, a);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(c.ev[3], st));
+            HIPCHK(hipMemcpyAsync(calls, c.pl_calls.p, (size_t)total * sizeof(gnx_pile_call), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            HIPCHK(hipEventElapsedTime(&ms, c.ev[2], c.ev[3]));
+            t.fill_ms += ms; t.n_launches = 2;
+        }
+        return GNX_OK;
+    };
+    if ((rc = run())) { (void)hipStreamSynchronize(st); if (calls) g_pool.put(calls); return rc; }
+    *out_calls = calls; *out_n = total;
     t.dominant_ms = t.total_ms = t.fill_ms; t.dominant_launches = t.n_launches;
     t.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count();
     c.timing = t;

@@ -535,6 +535,76 @@ int gnx_md_batch_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *
  * Pure host arithmetic: no device, no gnx_init.  n < 0, or a null pointer with n > 0: GNX_EINVAL. */
 int gnx_mapq_batch(int64_t n, const int64_t *score, const int64_t *second_score, uint8_t *out_mapq);
 
+/* ---- Pileup: per-base counts of placed reads on the resident reference, and the calls they give (an extension; sam/pileup.go's stage) -- */
+/* ONE pile per process, resident on the device beside the reference (context 0) and owned by it: gnx_set_reference[_synthetic] -- a new
+ * reference or its release -- and gnx_shutdown drop the pile; gnx_reference_index_build does not.  It covers the region
+ * [region_start, region_start + region_len) of the reference.  What comes back is small: rows on request (gnx_pileup_get) and the sparse
+ * list of positions where the reads disagree with the reference (gnx_pileup_calls); reads, CIGARs and reference stay where they are.
+ * Insertion sequences and deletion lengths are NOT kept (the reference's Pile has maps of both): a count per position is all there is.
+ *
+ * gnx_pileup_add_by_offset.  GNX_AFFINE_GAP_LOCAL only (any other mode: GNX_EINVAL).  Roles, sequences, ops and ops_off are those of
+ * gnx_md_batch_by_offset: the window (ref_start[k], ref_len[k]) is alpha, the read is beta in the orientation it was aligned in -- a
+ * strand-1 winner is passed as its reverse complement, so every counted base is a forward-strand base; strand[k] in {0, 1} only picks the
+ * counter.  Everything is a function of the pair's column sequence as gnx_summarize_* defines it (runs of length 0 vanish, adjacent equal
+ * ops are one run, anchored at (0, 0)).  The leading and the trailing maximal D run are outside, so alpha_start and alpha_end are the
+ * summary's; a sequence that is one D run has nothing inside.  For pair k with use == NULL or use[k] != 0, with x = ref_start[k] + i for a
+ * column at alpha position i, and only where region_start <= x < region_start + region_len:
+ *   an inside M column over read byte b             base[strand][b] += 1 at x (a read N counts in slot 4)
+ *   an inside D column                              del[strand] += 1 at x
+ *   a maximal inside I run behind i consumed alpha bases, alpha_start < i < alpha_end      ins[strand] += 1 at ref_start[k] + i - 1
+ * A terminal I run (i == alpha_start or i == alpha_end) is a soft clip, as the reference's sclipTerminalIns treats it, and counts
+ * nowhere.  Columns outside the region contribute nothing; a read wholly outside the region is not an error.
+ * E.g. window at 100 = ACGTACGTAC, read ACGAACTAC, 6M 1D 3M, strand 0: base A at 100, C at 101, G at 102, A at 103, A at 104, C at 105, del
+ * at 106, T at 107, A at 108, C at 109.  Same window, read TTTACG, 3D 2I 4M 3D: T, A, C, G at 103 .. 106 and nothing else (both D runs are
+ * outside, the I run stands at i == alpha_start).
+ * Return codes, all before the pile changes: those of gnx_md_batch_by_offset (GNX_EBASE exactly where that twin reports it: a byte >= 5
+ * anywhere in a read, or in a window's exception blocks, used or not), and GNX_EINVAL also without an open pile, for a strand byte > 1, and
+ * for a call that would carry reads_added past 2^31 - 1 (every counter grows by at most 1 per read, so int32 cannot overflow).
+ * n_pairs == 0: GNX_OK; GNX_EDEVICE without a device, after the argument checks; never GNX_ERANGE.
+ * pile_add_kernel (pileup.hip.h) has aln_summary_kernel's geometry and reads no reference; the counters are 14 planes of region_len int32
+ * bumped with atomic adds.  Calls are cut into launches of GNX_HOST_SUB pairs.  Switches, read per call: GNX_PILE_SUB=<pairs> overrides
+ * that cut; GNX_PILE_FORM=0 / 1 walks every M and D run a lane per column / a lane per run (same counts).  gnx_get_timing afterwards:
+ * fast_path 14, cells = the CIGAR columns of the added pairs, dominant_ms = pile_add_kernel alone (fill_ms: with the base check).
+ *
+ * gnx_pileup_open: a zeroed pile over the region; an open pile is replaced.  GNX_EINVAL for region_start < 0, region_len < 1, without a
+ * resident reference, for a region that leaves it; GNX_ENOMEM when the table (56 bytes per position) does not fit -- the previous pile
+ * then stays as it was.  gnx_pileup_info: any pointer may be NULL; GNX_EINVAL without an open pile.  gnx_pileup_get: rows
+ * region_start + first .. + count as gnx_pile; GNX_EINVAL for rows outside the region, a null `out` with count > 0, no open pile.
+ * gnx_pileup_close: releases the pile; without one: GNX_OK.
+ *
+ * gnx_pileup_calls.  THIS LIBRARY's rule (as gnx_mapq_batch's is), not a variant caller's.  For every position x of the region, ascending,
+ * with c the reference code at x (4 in an exception block): cnt[a] = base[0][a] + base[1][a], del = del[0] + del[1], ins = ins[0] + ins[1],
+ * depth = cnt[0] + .. + cnt[4] + del.  c == 4: nothing is emitted at x.
+ *   Primary call     the candidates are the bases a in {0, 1, 2, 3} other than c, then the deletion; the winner is the largest count, ties
+ *                    going to the smaller index, the deletion last.  Emitted as kind 0 (alt = a) or kind 1 (alt = 0xFF) if
+ *                    depth >= min_depth, count >= min_alt, count * frac_den >= frac_num * depth (in 64 bits) and, with both_strands, both
+ *                    strand counts are at least 1.
+ *   Insertion call   kind 2 (alt = 0xFF), behind x: the same four tests with count = ins against the same depth.
+ * Output ordered by position, the primary call before the insertion call; ref = c, count_fwd = the strand-0 share of count.  *out_calls is
+ * malloc'd (gnx_free), also for *out_n == 0.  GNX_EINVAL for min_depth < 1, min_alt < 1, not 1 <= frac_num <= frac_den <= 2^20,
+ * both_strands outside {0, 1}, a null pointer, no open pile -- nothing is written then.  pile_call_kernel: one position per lane, a count
+ * pass, the scan family, a write pass.  gnx_get_timing afterwards: fast_path 15, cells = the region's positions. */
+typedef struct gnx_pile {            /* 16 x int32 = 64 bytes, one reference position */
+    int32_t base[2][5];              /* [strand][A C G T N]: read bases in M columns over this position */
+    int32_t del[2];                  /* inside D columns over this position */
+    int32_t ins[2];                  /* maximal inside I runs directly behind this position */
+    int32_t _reserved[2];            /* 0 */
+} gnx_pile;
+typedef struct gnx_pile_call_opts { int32_t min_depth, min_alt, frac_num, frac_den, both_strands, _reserved; } gnx_pile_call_opts;
+typedef struct gnx_pile_call {       /* 24 bytes */
+    int64_t pos;                     /* 0-based reference position */
+    int32_t depth, count, count_fwd;
+    uint8_t kind, ref, alt, _pad;    /* kind 0 substitution, 1 deletion, 2 insertion; alt: a base code for kind 0, else 0xFF */
+} gnx_pile_call;
+int gnx_pileup_open(int64_t region_start, int64_t region_len);
+int gnx_pileup_info(int64_t *out_start, int64_t *out_len, int64_t *out_reads_added, int64_t *out_device_bytes);
+int gnx_pileup_add_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *read_cat, const int64_t *read_off,
+                             const int64_t *ref_start, const int64_t *ref_len, const uint8_t *strand,
+                             const gnx_cigar *ops, const int64_t *ops_off, const uint8_t *use /* NULL: all */);
+int gnx_pileup_get(int64_t first, int64_t count, gnx_pile *out);
+int gnx_pileup_calls(const gnx_pile_call_opts *o, gnx_pile_call **out_calls, int64_t *out_n);
+int gnx_pileup_close(void);
+
 int gnx_get_timing(gnx_timing *out);
 /* Diagnostics (tests only; nothing in the reference corresponds to it): launch n_workgroups workgroups that each hold one CU's whole
  * LDS and spin for `milliseconds` on a stream of their own, and return at once -- the pipelined launches of the library must make

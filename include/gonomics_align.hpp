@@ -494,6 +494,60 @@ inline std::vector<int> Mapq(const std::vector<int64_t> &scores, const std::vect
     return std::vector<int>(q.begin(), q.end() - 1);
 }
 
+// ---- the pile of the resident reference (gnx_pileup_*, an extension): per-position counts of placed reads and the calls they give.
+// One pile per process, owned by the reference; gnx_align.h defines what is counted and the rule of the calls.
+struct PileInfo { int64_t Start = 0, Len = 0, ReadsAdded = 0, DeviceBytes = 0; };
+struct PileCallOpts { int MinDepth = 1, MinAlt = 1, FracNum = 1, FracDen = 2; bool BothStrands = false; };
+inline void PileupOpen(int64_t start, int64_t length) { const int rc = gnx_pileup_open(start, length); if (rc) detail::raise(rc); }
+inline void PileupClose() { const int rc = gnx_pileup_close(); if (rc) detail::raise(rc); }
+inline PileInfo PileupInfo() {
+    PileInfo i;
+    const int rc = gnx_pileup_info(&i.Start, &i.Len, &i.ReadsAdded, &i.DeviceBytes);
+    if (rc) detail::raise(rc);
+    return i;
+}
+// reads (in the orientation they were aligned in) against windows (start, len) of the resident reference; strands[k] picks the counter;
+// use: empty = all, else use[k] == 0 leaves pair k out.  GNX_AFFINE_GAP_LOCAL.
+inline void PileupAdd(const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, const std::vector<std::vector<dna::Base>> &reads,
+                      const std::vector<std::pair<int64_t, int64_t>> &windows, const std::vector<uint8_t> &strands, const std::vector<std::vector<Cigar>> &routes,
+                      const std::vector<uint8_t> &use = {}) {
+    const int64_t n = (int64_t)routes.size();
+    if ((int64_t)reads.size() != n || (int64_t)windows.size() != n || (int64_t)strands.size() != n || (!use.empty() && (int64_t)use.size() != n)) detail::raise(GNX_EINVAL);
+    const gnx_params p = detail::params(GNX_AFFINE_GAP_LOCAL, scores, gapOpen, gapExtend, 10000, 10000);
+    std::vector<dna::Base> cat;
+    std::vector<int64_t> off, ooff((size_t)n + 1, 0), ws, wl;
+    std::vector<gnx_cigar> ops;
+    std::vector<uint8_t> st(strands);
+    detail::flatten(reads, cat, off);
+    for (const auto &w : windows) { ws.push_back(w.first); wl.push_back(w.second); }
+    ws.push_back(0); wl.push_back(0); st.push_back(0);
+    for (int64_t k = 0; k < n; k++) {
+        for (const Cigar &c : routes[(size_t)k]) { gnx_cigar g{}; g.run_length = c.RunLength; g.op = c.Op; ops.push_back(g); }
+        ooff[(size_t)k + 1] = (int64_t)ops.size();
+    }
+    ops.push_back(gnx_cigar{});
+    const int rc = gnx_pileup_add_by_offset(&p, n, cat.data(), off.data(), ws.data(), wl.data(), st.data(), ops.data(), ooff.data(), use.empty() ? nullptr : use.data());
+    if (rc) detail::raise(rc);
+}
+inline std::vector<gnx_pile> PileupGet(int64_t first = 0, int64_t count = -1) {
+    if (count < 0) count = PileupInfo().Len - first;
+    std::vector<gnx_pile> rows((size_t)(count > 0 ? count : 0) + 1);
+    const int rc = gnx_pileup_get(first, count, rows.data());
+    if (rc) detail::raise(rc);
+    rows.pop_back();
+    return rows;
+}
+inline std::vector<gnx_pile_call> PileupCalls(const PileCallOpts &o = PileCallOpts()) {
+    const gnx_pile_call_opts co = {o.MinDepth, o.MinAlt, o.FracNum, o.FracDen, o.BothStrands ? 1 : 0, 0};
+    gnx_pile_call *calls = nullptr;
+    int64_t n = 0;
+    const int rc = gnx_pileup_calls(&co, &calls, &n);
+    if (rc) detail::raise(rc);
+    std::vector<gnx_pile_call> res(calls, calls + n);
+    gnx_free(calls);
+    return res;
+}
+
 inline void AffineGapLocalEngine(const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, std::vector<TargetQueryPair> &pairs) {
     std::vector<std::vector<dna::Base>> t, q;
     for (auto &p : pairs) { t.push_back(p.Target); q.push_back(p.Query); }
