@@ -27,7 +27,8 @@ EXPORTS = ["gnx_device_count", "gnx_init", "gnx_shutdown", "gnx_last_error", "gn
            "gnx_reference_index_build", "gnx_reference_index_info", "gnx_reference_index_get", "gnx_seed_candidates",
            "gnx_summarize_batch", "gnx_summarize_batch_windows", "gnx_summarize_batch_by_offset",
            "gnx_md_batch", "gnx_md_batch_windows", "gnx_md_batch_by_offset", "gnx_mapq_batch",
-           "gnx_pileup_open", "gnx_pileup_info", "gnx_pileup_add_by_offset", "gnx_pileup_get", "gnx_pileup_calls", "gnx_pileup_close"]
+           "gnx_pileup_open", "gnx_pileup_info", "gnx_pileup_add_by_offset", "gnx_pileup_get", "gnx_pileup_calls", "gnx_pileup_close",
+           "gnx_pileup_track_alleles", "gnx_pileup_allele_info", "gnx_pileup_alleles", "gnx_pileup_indel_calls"]
 GNX_XCOL_EQ, GNX_XCOL_X = 3, 4
 
 
@@ -81,6 +82,16 @@ PILE_DTYPE = np.dtype([("base", np.int32, (2, 5)), ("del", np.int32, (2,)), ("in
 PILE_CALL_DTYPE = np.dtype({"names": ["pos", "depth", "count", "count_fwd", "kind", "ref", "alt", "_pad"],
                             "formats": [np.int64, np.int32, np.int32, np.int32, np.uint8, np.uint8, np.uint8, np.uint8],
                             "offsets": [0, 8, 12, 16, 20, 21, 22, 23], "itemsize": 24})
+
+
+# gnx_pile_allele: one distinct indel allele with its counts, 32 bytes; gnx_pile_indel_call: the allele, the depth and the reference code, 40 bytes
+PILE_ALLELE_DTYPE = np.dtype({"names": ["pos", "seq", "length", "count", "count_fwd", "kind", "_pad"],
+                              "formats": [np.int64, np.uint64, np.int32, np.int32, np.int32, np.uint8, (np.uint8, (3,))],
+                              "offsets": [0, 8, 16, 20, 24, 28, 29], "itemsize": 32})
+PILE_INDEL_CALL_DTYPE = np.dtype({"names": ["pos", "seq", "length", "count", "count_fwd", "kind", "_pad", "depth", "ref", "_pad2"],
+                                  "formats": [np.int64, np.uint64, np.int32, np.int32, np.int32, np.uint8, (np.uint8, (3,)), np.int32, np.uint8, (np.uint8, (3,))],
+                                  "offsets": [0, 8, 16, 20, 24, 28, 29, 32, 36, 37], "itemsize": 40})
+PILE_SEQ_MAX = 21  # inserted bases whose sequence an allele keeps
 
 
 class GnxError(RuntimeError):
@@ -209,6 +220,15 @@ def lib():
             L.gnx_pileup_calls.restype = ctypes.c_int
             L.gnx_pileup_close.argtypes = []
             L.gnx_pileup_close.restype = ctypes.c_int
+        if hasattr(L, "gnx_pileup_track_alleles"):
+            L.gnx_pileup_track_alleles.argtypes = [i64]
+            L.gnx_pileup_track_alleles.restype = ctypes.c_int
+            L.gnx_pileup_allele_info.argtypes = [c_p, c_p, c_p]
+            L.gnx_pileup_allele_info.restype = ctypes.c_int
+            L.gnx_pileup_alleles.argtypes = [ctypes.POINTER(c_p), ctypes.POINTER(i64)]
+            L.gnx_pileup_alleles.restype = ctypes.c_int
+            L.gnx_pileup_indel_calls.argtypes = [ctypes.POINTER(GnxPileCallOpts), ctypes.POINTER(c_p), ctypes.POINTER(i64)]
+            L.gnx_pileup_indel_calls.restype = ctypes.c_int
         L.gnx_seed_index_build.argtypes = [c_p, c_p, i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(i64)]
         L.gnx_seed_index_build.restype = ctypes.c_int
         L.gnx_seed_index_set.argtypes = [c_p, c_p, i64, c_p, c_p, i64, ctypes.c_int]
@@ -837,6 +857,59 @@ def pileup_calls(min_depth, min_alt, frac_num, frac_den, both_strands=0):
         return np.zeros(0, dtype=PILE_CALL_DTYPE)
     finally:
         lib().gnx_free(calls_p)
+
+
+def pileup_track_alleles(reserve=0):
+    """gnx_pileup_track_alleles: the open pile, still empty, logs its indel alleles from now on; reserve sizes the first log (0: a default)."""
+    check(lib().gnx_pileup_track_alleles(int(reserve)))
+
+
+def pileup_allele_info():
+    """gnx_pileup_allele_info -> {"tracking", "events", "device_bytes"}"""
+    tr, v = np.zeros(1, dtype=np.int32), np.zeros(2, dtype=np.int64)
+    check(lib().gnx_pileup_allele_info(tr.ctypes.data, v.ctypes.data, v.ctypes.data + 8))
+    return {"tracking": bool(tr[0]), "events": int(v[0]), "device_bytes": int(v[1])}
+
+
+def _taken(call, dtype):
+    """a malloc'd array of `dtype` records that `call(byref(pointer), byref(count))` hands out, copied and freed"""
+    res_p, n = ctypes.c_void_p(), ctypes.c_int64(0)
+    check(call(ctypes.byref(res_p), ctypes.byref(n)))
+    try:
+        if n.value:
+            buf = (ctypes.c_char * (n.value * dtype.itemsize)).from_address(res_p.value)
+            return np.frombuffer(buf, dtype=dtype, count=n.value).copy()
+        return np.zeros(0, dtype=dtype)
+    finally:
+        lib().gnx_free(res_p)
+
+
+def pileup_alleles():
+    """gnx_pileup_alleles -> PILE_ALLELE_DTYPE array, ordered by (pos, kind, key)"""
+    return _taken(lambda p, n: lib().gnx_pileup_alleles(p, n), PILE_ALLELE_DTYPE)
+
+
+def pileup_indel_calls(min_depth, min_alt, frac_num, frac_den, both_strands=0):
+    """gnx_pileup_indel_calls -> PILE_INDEL_CALL_DTYPE array, in the alleles' order"""
+    o = GnxPileCallOpts(int(min_depth), int(min_alt), int(frac_num), int(frac_den), int(both_strands), 0)
+    return _taken(lambda p, n: lib().gnx_pileup_indel_calls(ctypes.byref(o), p, n), PILE_INDEL_CALL_DTYPE)
+
+
+def pack_inserted(bases):
+    """the `seq` of an insertion of at most PILE_SEQ_MAX bases: 3 bits each, code + 1 (a byte >= 4: 5), the first base lowest"""
+    v = 0
+    for k, b in enumerate(bases):
+        v |= (min(int(b), 4) + 1) << (3 * k)
+    return v
+
+
+def unpack_inserted(seq):
+    """the base codes of a packed `seq`"""
+    out, seq = [], int(seq)
+    while seq:
+        out.append((seq & 7) - 1)
+        seq >>= 3
+    return np.asarray(out, dtype=np.uint8)
 
 
 def _chunk_pairs(alphas, betas):

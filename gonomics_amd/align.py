@@ -603,6 +603,51 @@ def PileupCalls(min_depth, min_alt, frac=(1, 2), both_strands=False):
              "ref": int(c["ref"]), "alt": int(c["alt"]) if int(c["kind"]) == 0 else None} for c in calls]
 
 
+def PileupTrackAlleles(reserve=0):
+    """The open pile, still empty, keeps its indel alleles from now on (gnx_pileup_track_alleles): which deletion, which insertion, not
+    only how many.  reserve sizes the first log in events (0: a default); the log grows as reads are added."""
+    try:
+        _lib.pileup_track_alleles(reserve)
+    except _lib.GnxError as e:
+        _raise(e)
+
+
+def PileupAlleleInfo():
+    """{"tracking", "events", "device_bytes"} of the open pile's allele log"""
+    try:
+        return _lib.pileup_allele_info()
+    except _lib.GnxError as e:
+        _raise(e)
+
+
+_ALLELE_KINDS = (None, "del", "ins", "long_ins")
+
+
+def _allele_dict(a):
+    kind = _ALLELE_KINDS[int(a["kind"])]
+    return {"pos": int(a["pos"]), "kind": kind, "length": int(a["length"]), "seq": _lib.unpack_inserted(a["seq"]) if kind == "ins" else None,
+            "count": int(a["count"]), "count_fwd": int(a["count_fwd"])}
+
+
+def PileupAlleles():
+    """The distinct indel alleles of a tracking pile with their counts (gnx_pileup_alleles), ordered by position, kind and key: one dict
+    each -- pos (a deletion's first deleted base; the base an insertion stands behind), kind ("del" / "ins" / "long_ins"), length, seq
+    (the inserted base codes for "ins", else None: a long insertion keeps its length only), count, count_fwd."""
+    try:
+        return [_allele_dict(a) for a in _lib.pileup_alleles()]
+    except _lib.GnxError as e:
+        _raise(e)
+
+
+def PileupIndelCalls(min_depth, min_alt, frac=(1, 2), both_strands=False):
+    """The alleles that pass the library's rule (gnx_pileup_indel_calls), in PileupAlleles' order: its dicts plus depth and ref."""
+    try:
+        calls = _lib.pileup_indel_calls(min_depth, min_alt, frac[0], frac[1], 1 if both_strands else 0)
+    except _lib.GnxError as e:
+        _raise(e)
+    return [dict(_allele_dict(c), depth=int(c["depth"]), ref=int(c["ref"])) for c in calls]
+
+
 def PileupAddReport(params, reads, report, min_mapq=0):
     """Add the placed reads of a MapReadsReport / MapReadPairsReport(tags=True) report whose mapq is at least min_mapq, in ONE call:
     strand-1 reads go in as their reverse complements (as the report's own summaries took them), the window is window_start and the

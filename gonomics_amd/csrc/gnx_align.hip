@@ -59,6 +59,7 @@
 #include "aln_summary.hip.h"
 #include "aln_md.hip.h"
 #include "pileup.hip.h"
+#include "pile_alleles.hip.h"
 
 namespace {
 
@@ -156,6 +157,11 @@ struct Ctx {
     // the pile of the resident reference (gnx_pileup_*; context 0 only): PILE_PLANES planes of pl_len counters, and the scratch of a call
     DevBuf pl_tab, pl_in, pl_cnt, pl_off, pl_calls;
     int64_t pl_start = 0, pl_len = -1, pl_reads = 0; // pl_len >= 0: a pile over [pl_start, pl_start + pl_len) is open; reads added so far
+    // a tracking pile's log of indel events (gnx_pileup_track_alleles; pile_alleles.hip.h): two planes of pl_log_cap words, the cursor, the query's scratch
+    DevBuf pl_log, pl_cur, pl_sort[5], pl_al, pl_icalls;
+    bool pl_track = false;
+    int64_t pl_log_cap = 0, pl_events = 0; // events the planes hold; events logged so far (the cursor's value after the last add)
+    int pl_key_bits = 1;                   // no event's key needs more bits than this (from the runs of the added pairs): the sort's range
     PinBuf h_plans; // host-side plans of the general path
     PinBuf st_a[2], st_as[2], st_b[2], st_bs[2];
     // the resident reference, PACKED (gnx_host.hip.h: pack_reference): `ref` = 2 bits per base, ref_flag / ref_rank / ref_exc = the
@@ -2744,10 +2750,17 @@ void drop_reference_index(Ctx &c) {
     c.ri_keys.release(); c.ri_pos.release(); c.ri_dir.release();
     for (DevBuf &b : c.rs) b.release();
 }
+// the log of a tracking pile goes with the planes (and when gnx_pileup_open replaces the pile: tracking is off again)
+void drop_pile_log(Ctx &c) {
+    c.pl_track = false; c.pl_log_cap = 0; c.pl_events = 0; c.pl_key_bits = 1;
+    c.pl_log.release(); c.pl_cur.release(); c.pl_al.release(); c.pl_icalls.release();
+    for (DevBuf &b : c.pl_sort) b.release();
+}
 // ... and so does the pile (gnx_pileup_*), though not to a rebuilt index: its counts are positions of THAT reference
 void drop_pile(Ctx &c) {
     c.pl_len = -1; c.pl_start = 0; c.pl_reads = 0;
     c.pl_tab.release(); c.pl_in.release(); c.pl_cnt.release(); c.pl_off.release(); c.pl_calls.release();
+    drop_pile_log(c);
 }
 std::atomic<int64_t> g_sv_lds{0}, g_sv_slab{0}; // reads voted with the table in LDS / in a slab (gnx_debug_counter(7 / 8))
 
@@ -3161,6 +3174,32 @@ int gnx_pileup_get(int64_t first, int64_t count, gnx_pile *out) {
 int gnx_pileup_calls(const gnx_pile_call_opts *o, gnx_pile_call **out_calls, int64_t *out_n) {
     ApiCall api;
     return run_pile_calls(o, out_calls, out_n);
+}
+
+int gnx_pileup_track_alleles(int64_t reserve_events) {
+    ApiCall api;
+    return run_pile_track(reserve_events);
+}
+
+int gnx_pileup_allele_info(int32_t *out_tracking, int64_t *out_events, int64_t *out_device_bytes) {
+    ApiCall api;
+    Ctx &c = ctx_at(0);
+    CtxScope scope(c);
+    if (int rc = need_pile(c)) return rc;
+    if (out_tracking) *out_tracking = c.pl_track ? 1 : 0;
+    if (out_events) *out_events = c.pl_events;
+    if (out_device_bytes) *out_device_bytes = c.pl_track ? c.pl_log_cap * 16 + 8 : 0; // (the two planes and the cursor)
+    return GNX_OK;
+}
+
+int gnx_pileup_alleles(gnx_pile_allele **out, int64_t *out_n) {
+    ApiCall api;
+    return run_pile_alleles(out, out_n);
+}
+
+int gnx_pileup_indel_calls(const gnx_pile_call_opts *o, gnx_pile_indel_call **out_calls, int64_t *out_n) {
+    ApiCall api;
+    return run_pile_indel_calls(o, out_calls, out_n);
 }
 
 int gnx_pileup_close(void) {

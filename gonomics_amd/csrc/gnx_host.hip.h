@@ -1408,32 +1408,83 @@ int run_pile_open(int64_t region_start, int64_t region_len) {
         return GNX_EDEVICE;
     }
     c.pl_tab.release();
+    drop_pile_log(c); // (a new pile does not track until it is told to)
     c.pl_tab.p = q; c.pl_tab.cap = bytes;
     c.pl_start = region_start; c.pl_len = region_len; c.pl_reads = 0;
     return GNX_OK;
 }
 
+// The log of a tracking pile holds at least `events` events afterwards.  It grows by allocate-copy-free: the new planes are allocated
+// beside the old ones, which are freed only when the copy has landed; a failure is GNX_ENOMEM with the log as it was.
+int pile_log_reserve(Ctx &c, hipStream_t st, int64_t events) {
+    if (events <= c.pl_log_cap) return GNX_OK;
+    const int64_t cap = c.pl_log_cap == 0 ? events : events + events / 8 + 64; // (the first log is what the caller reserved)
+    void *q = nullptr;
+    if (hipMalloc(&q, (size_t)cap * 16) != hipSuccess) { (void)hipGetLastError(); set_err("device allocation of %s%lld bytes failed", "", (long long)cap * 16); return GNX_ENOMEM; }
+    if (c.pl_events > 0) {
+        const size_t used = (size_t)c.pl_events * 8;
+        if (hipMemcpyAsync(q, c.pl_log.p, used, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+            hipMemcpyAsync((unsigned long long *)q + cap, (const unsigned long long *)c.pl_log.p + c.pl_log_cap, used, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess) {
+            set_err_hip(hipGetLastError(), __FILE__, __LINE__);
+            (void)hipFree(q);
+            return GNX_EDEVICE;
+        }
+    }
+    c.pl_log.release();
+    c.pl_log.p = q; c.pl_log.cap = (size_t)cap * 16;
+    c.pl_log_cap = cap;
+    return GNX_OK;
+}
+
+int run_pile_track(int64_t reserve_events) {
+    Ctx &c = ctx_at(0);
+    CtxScope scope(c);
+    int rc;
+    if ((rc = need_pile(c))) return rc;
+    if (reserve_events < 0 || reserve_events > INT32_MAX) { set_err("reserve_events: 0 (a default) .. 2^31 - 1%s", ""); return GNX_EINVAL; }
+    if (c.pl_reads != 0) { set_err("gnx_pileup_track_alleles: reads have been added to this pile (%s%lld): their alleles are gone", "", (long long)c.pl_reads); return GNX_EINVAL; }
+    if ((rc = ensure_init())) return rc;
+    hipStream_t st = c.own_stream;
+    // the cursor first: a pile tracks only when both allocations stand (a second call on an empty pile keeps a log that is large enough)
+    if (!c.pl_cur.p && hipMalloc(&c.pl_cur.p, 8) != hipSuccess) { (void)hipGetLastError(); c.pl_cur.p = nullptr; set_err("device allocation of %s%lld bytes failed", "", 8); return GNX_ENOMEM; }
+    c.pl_cur.cap = 8;
+    HIPCHK(hipMemsetAsync(c.pl_cur.p, 0, 8, st));
+    HIPCHK(hipStreamSynchronize(st));
+    c.pl_events = 0;
+    if ((rc = pile_log_reserve(c, st, reserve_events > 0 ? reserve_events : (int64_t)1 << 16))) return rc;
+    c.pl_track = true;
+    return GNX_OK;
+}
+
 // gnx_md_batch_by_offset's checks and uploads (sa = the windows, sb = the reads), the base check over every launch cut, ONE read-back of
 // its flag -- nothing may change the pile before every error is known --, then pile_add_kernel per sub-batch of GNX_HOST_SUB pairs
-// (GNX_PILE_SUB=<pairs> overrides the cut).
+// (GNX_PILE_SUB=<pairs> overrides the cut).  On a tracking pile the log is grown first -- beside the old one, before the first launch that could
+// change the pile -- and allele_log_kernel follows pile_add_kernel over the same buffers and the same cuts.
 int run_pile_add(const gnx_params *prm, int64_t n_pairs, const SeqSide &sa, const SeqSide &sb, const uint8_t *strand, const gnx_cigar *ops, const int64_t *ops_off,
                  const uint8_t *use) {
     const auto t_entry = std::chrono::steady_clock::now();
     int rc;
     int64_t cells = 0;
     if ((rc = check_cigar_call(prm, n_pairs, sa, sb, ops, ops_off, strand != nullptr || n_pairs == 0, true, cells))) return rc;
-    int64_t n_use = 0;
+    int64_t n_use = 0, gap_runs = 0, max_ins = 0, max_del = 0; // gap_runs: the I and D runs of non-zero length -- no call logs more events
     cells = 0; // of the added pairs
     for (int64_t q = 0; q < n_pairs; q++) {
         if (strand[q] > 1) { set_err("strand byte > 1 at pair %s%lld", "", (long long)q); return GNX_EINVAL; }
         if (use && !use[q]) continue;
         n_use++;
-        for (int64_t x = ops_off[q]; x < ops_off[q + 1]; x++) cells += ops[x].run_length;
+        int64_t ins = 0, del = 0;
+        for (int64_t x = ops_off[q]; x < ops_off[q + 1]; x++) {
+            cells += ops[x].run_length;
+            if (ops[x].run_length > 0 && ops[x].op != GNX_COL_M) { gap_runs++; (ops[x].op == GNX_COL_I ? ins : del) += ops[x].run_length; }
+        }
+        max_ins = std::max(max_ins, ins); max_del = std::max(max_del, del);
     }
     Ctx &c = ctx_at(0);
     CtxScope scope(c);
     if ((rc = need_pile(c))) return rc;
     if (n_use > (int64_t)INT32_MAX - c.pl_reads) { set_err("more than 2^31 - 1 reads in one pile (its counters are int32)%s", ""); return GNX_EINVAL; }
+    if (c.pl_track && gap_runs > (int64_t)INT32_MAX - c.pl_events) { set_err("more than 2^31 - 1 indel events in one pile%s", ""); return GNX_EINVAL; }
     if (n_pairs == 0) return GNX_OK;
     if ((rc = ensure_init())) return rc;
     g_transport = 0; g_bcast_ms = 0;
@@ -1443,6 +1494,7 @@ int run_pile_add(const gnx_params *prm, int64_t n_pairs, const SeqSide &sa, cons
     t.fast_path = 14; t.cells = cells; t.n_contexts = 1;
     int64_t sub = gnx_host_sub(getenv("GNX_HOST_SUB"));
     if (const char *e = getenv("GNX_PILE_SUB")) sub = std::max<int64_t>(atoll(e), 1);
+    int64_t events = c.pl_events; // the log's cursor after this call
     int cut = 64;
     if (const char *e = getenv("GNX_PILE_FORM")) cut = e[0] == '0' ? 1 : e[0] == '1' ? 0x7fffffff : 64;
     DevBuf *sm = c.sm;
@@ -1466,6 +1518,7 @@ int run_pile_add(const gnx_params *prm, int64_t n_pairs, const SeqSide &sa, cons
         HIPCHK(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
         t.fill_ms = ms;
         if (n_use == 0) return GNX_OK;
+        if (c.pl_track && (r = pile_log_reserve(c, st, c.pl_events + gap_runs))) return r;
         PileArgs pa;
         pa.reads = (const uint8_t *)sm[SM_B].p; pa.ops = (const gnx_cigar *)sm[SM_OPS].p; pa.cut = cut;
         pa.pile = (int *)c.pl_tab.p; pa.region_start = c.pl_start; pa.region_len = c.pl_len;
@@ -1480,14 +1533,39 @@ int run_pile_add(const gnx_params *prm, int64_t n_pairs, const SeqSide &sa, cons
             t.n_launches++;
         }
         HIPCHK(hipEventRecord(c.ev[3], st));
+        t.dominant_launches = t.n_launches;
+        if (c.pl_track) {
+            PileAlleleArgs aa;
+            aa.reads = pa.reads; aa.ops = pa.ops; aa.region_start = c.pl_start; aa.region_len = c.pl_len;
+            aa.w0 = (unsigned long long *)c.pl_log.p; aa.w1 = aa.w0 + c.pl_log_cap; aa.cursor = (unsigned long long *)c.pl_cur.p; aa.cap = (unsigned long long)c.pl_log_cap;
+            for (int64_t b = 0; b < n_pairs; b += sub) {
+                const int64_t cnt = std::min(sub, n_pairs - b);
+                aa.read_start = (const int64_t *)sm[SM_BS].p + b; aa.ref_start = (const int64_t *)sm[SM_AS].p + b; aa.ops_off = (const int64_t *)sm[SM_OFF].p + b;
+                aa.strand = (const uint8_t *)c.pl_in.p + b; aa.use = use ? (const uint8_t *)c.pl_in.p + np + b : nullptr;
+                aa.n_pairs = cnt;
+                hipLaunchKernelGGL(allele_log_kernel, dim3((unsigned)std::min<int64_t>((cnt + 3) / 4, 1 << 20)), dim3(256), 0, st, aa);
+                HIPCHK(hipGetLastError());
+                t.n_launches++;
+            }
+            HIPCHK(hipEventRecord(c.ev[4], st));
+            HIPCHK(hipMemcpyAsync(&events, c.pl_cur.p, 8, hipMemcpyDeviceToHost, st));
+        }
         HIPCHK(hipStreamSynchronize(st));
         HIPCHK(hipEventElapsedTime(&ms, c.ev[2], c.ev[3]));
         t.fill_ms += ms; t.dominant_ms = ms; // (dominant_ms: pile_add_kernel alone)
+        if (c.pl_track) { HIPCHK(hipEventElapsedTime(&ms, c.ev[3], c.ev[4])); t.fill_ms += ms; }
         return GNX_OK;
     };
     if ((rc = run())) { (void)hipStreamSynchronize(st); return rc; }
     c.pl_reads += n_use;
-    t.total_ms = t.fill_ms; t.dominant_launches = t.n_launches;
+    if (c.pl_track && n_use > 0) {
+        c.pl_events = events;
+        const int ins_bits = max_ins == 0 ? 0 : max_ins <= PILE_SEQ_MAX ? 3 * (int)max_ins : 63;
+        int len_bits = 0;
+        while (len_bits < 62 && ((int64_t)1 << len_bits) <= std::max(max_ins, max_del)) len_bits++;
+        c.pl_key_bits = std::max(c.pl_key_bits, std::max(ins_bits, len_bits));
+    }
+    t.total_ms = t.fill_ms;
     t.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count();
     c.timing = t;
     return GNX_OK;
@@ -1522,13 +1600,18 @@ int run_pile_get(int64_t first, int64_t count, gnx_pile *out) {
     return GNX_OK;
 }
 
+// the ranges of gnx_pile_call_opts, for both call entries
+bool pile_call_opts_ok(const gnx_pile_call_opts *o) {
+    if (o->min_depth >= 1 && o->min_alt >= 1 && o->frac_num >= 1 && o->frac_num <= o->frac_den && o->frac_den <= (1 << 20) && o->both_strands >= 0 && o->both_strands <= 1) return true;
+    set_err("gnx_pile_call_opts: min_depth >= 1, min_alt >= 1, 1 <= frac_num <= frac_den <= 2^20, both_strands 0 or 1%s", "");
+    return false;
+}
+
 // pile_call_kernel<false>, the scan of the tiles' counts, one read-back that sizes the list, pile_call_kernel<true>
 int run_pile_calls(const gnx_pile_call_opts *o, gnx_pile_call **out_calls, int64_t *out_n) {
     const auto t_entry = std::chrono::steady_clock::now();
     if (!o || !out_calls || !out_n) { set_err("bad argument%s", ""); return GNX_EINVAL; }
-    if (o->min_depth < 1 || o->min_alt < 1 || o->frac_num < 1 || o->frac_num > o->frac_den || o->frac_den > (1 << 20) || o->both_strands < 0 || o->both_strands > 1) {
-        set_err("gnx_pile_call_opts: min_depth >= 1, min_alt >= 1, 1 <= frac_num <= frac_den <= 2^20, both_strands 0 or 1%s", ""); return GNX_EINVAL;
-    }
+    if (!pile_call_opts_ok(o)) return GNX_EINVAL;
     Ctx &c = ctx_at(0);
     CtxScope scope(c);
     int rc;
@@ -1582,6 +1665,173 @@ int run_pile_calls(const gnx_pile_call_opts *o, gnx_pile_call **out_calls, int64
     if ((rc = run())) { (void)hipStreamSynchronize(st); if (calls) g_pool.put(calls); return rc; }
     *out_calls = calls; *out_n = total;
     t.dominant_ms = t.total_ms = t.fill_ms; t.dominant_launches = t.n_launches;
+    t.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count();
+    c.timing = t;
+    return GNX_OK;
+}
+
+int need_tracking(const Ctx &c) {
+    if (c.pl_track) return GNX_OK;
+    set_err("the open pile does not track alleles: call gnx_pileup_track_alleles before the first add%s", "");
+    return GNX_EINVAL;
+}
+
+// The distinct alleles of the log, ordered and counted, left in c.pl_al on the device: two stable radix sorts of the log's planes into
+// scratch (by w1, then by w0: the order is (pos, kind, key, strand)), allele_reduce_kernel<false>, the scan of the tiles' counts,
+// one read-back that sizes the array, allele_reduce_kernel<true>.  The log is only read.
+int pile_alleles_device(Ctx &c, hipStream_t st, int64_t &n_alleles, gnx_timing &t) {
+    const int64_t n = c.pl_events;
+    n_alleles = 0;
+    if (n == 0) return GNX_OK;
+    int r;
+    for (int k = 0; k < 4; k++) if ((r = c.pl_sort[k].ensure((size_t)n * 8))) return r;
+    unsigned long long *w0 = (unsigned long long *)c.pl_log.p, *w1 = w0 + c.pl_log_cap;
+    unsigned long long *s_w1 = (unsigned long long *)c.pl_sort[0].p, *s_w0 = (unsigned long long *)c.pl_sort[1].p;   // ordered by w1
+    unsigned long long *o_w0 = (unsigned long long *)c.pl_sort[2].p, *o_w1 = (unsigned long long *)c.pl_sort[3].p;   // ordered by (w0, w1)
+    // the bits that can differ: the strand and the longest key of any added pair; the region's positions and the kind
+    const unsigned bits1 = (unsigned)std::min(64, c.pl_key_bits + 1);
+    unsigned bits0 = 2;
+    while (bits0 < 64 && ((uint64_t)1 << (bits0 - 2)) < (uint64_t)c.pl_len) bits0++;
+    size_t tmp1 = 0, tmp0 = 0;
+    HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp1, w1, s_w1, w0, s_w0, (size_t)n, 0u, bits1, st));
+    HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp0, s_w0, o_w0, s_w1, o_w1, (size_t)n, 0u, bits0, st));
+    size_t tmp_bytes = std::max(tmp1, tmp0);
+    if ((r = c.pl_sort[4].ensure(std::max<size_t>(tmp_bytes, 8)))) return r;
+    const int64_t n_tiles = (n + PILE_TILE - 1) / PILE_TILE;
+    if ((r = c.pl_cnt.ensure((size_t)(n_tiles + 1) * 8)) || (r = c.pl_off.ensure((size_t)(n_tiles + 1) * 8))) return r;
+    int64_t *d_carry = (int64_t *)c.pl_cnt.p + n_tiles;
+    HIPCHK(hipMemsetAsync(d_carry, 0, 8, st));
+    HIPCHK(hipEventRecord(c.ev[0], st));
+    HIPCHK(rocprim::radix_sort_pairs(c.pl_sort[4].p, tmp_bytes, w1, s_w1, w0, s_w0, (size_t)n, 0u, bits1, st)); // stable LSD radix sorts: the second keeps the first's order within a w0
+    HIPCHK(rocprim::radix_sort_pairs(c.pl_sort[4].p, tmp_bytes, s_w0, o_w0, s_w1, o_w1, (size_t)n, 0u, bits0, st));
+    PileReduceArgs a;
+    a.w0 = o_w0; a.w1 = o_w1; a.n = n; a.n_tiles = n_tiles; a.region_start = c.pl_start;
+    a.cnt = (int64_t *)c.pl_cnt.p; a.off = (const int64_t *)c.pl_off.p; a.out = nullptr;
+    const dim3 grid((unsigned)std::min<int64_t>((n_tiles + 3) / 4, 1 << 20));
+    hipLaunchKernelGGL(allele_reduce_kernel<false>, grid, dim3(256), 0, st, a);
+    HIPCHK(hipGetLastError());
+    if ((r = launch_scan(a.cnt, (int)n_tiles, (int64_t *)c.pl_off.p, d_carry, st))) return r;
+    HIPCHK(hipEventRecord(c.ev[1], st));
+    HIPCHK(hipMemcpyAsync(&n_alleles, (const int64_t *)c.pl_off.p + n_tiles, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+    t.fill_ms += ms; t.n_launches += 3;
+    if ((r = c.pl_al.ensure((size_t)n_alleles * sizeof(gnx_pile_allele)))) return r;
+    a.out = (gnx_pile_allele *)c.pl_al.p;
+    HIPCHK(hipEventRecord(c.ev[2], st));
+    hipLaunchKernelGGL(allele_reduce_kernel<true>, grid, dim3(256), 0, st, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c.ev[3], st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipEventElapsedTime(&ms, c.ev[2], c.ev[3]));
+    t.fill_ms += ms; t.n_launches++;
+    return GNX_OK;
+}
+
+int run_pile_alleles(gnx_pile_allele **out, int64_t *out_n) {
+    const auto t_entry = std::chrono::steady_clock::now();
+    if (!out || !out_n) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    Ctx &c = ctx_at(0);
+    CtxScope scope(c);
+    int rc;
+    if ((rc = need_pile(c)) || (rc = need_tracking(c))) return rc;
+    if ((rc = ensure_init())) return rc;
+    g_transport = 0; g_bcast_ms = 0;
+    hipStream_t st = c.own_stream;
+    gnx_timing t = {};
+    t.fast_path = 16; t.cells = c.pl_events; t.n_contexts = 1;
+    gnx_pile_allele *res = nullptr;
+    int64_t total = 0;
+    auto run = [&]() -> int {
+        int r;
+        if ((r = pile_alleles_device(c, st, total, t))) return r;
+        res = (gnx_pile_allele *)g_pool.get((size_t)std::max<int64_t>(total, 1) * sizeof(gnx_pile_allele));
+        if (!res) { set_err("pinned host allocation failed%s", ""); return GNX_ENOMEM; }
+        if (total > 0) {
+            HIPCHK(hipMemcpyAsync(res, c.pl_al.p, (size_t)total * sizeof(gnx_pile_allele), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+        }
+        return GNX_OK;
+    };
+    if ((rc = run())) { (void)hipStreamSynchronize(st); if (res) g_pool.put(res); return rc; }
+    *out = res; *out_n = total;
+    t.dominant_ms = t.total_ms = t.fill_ms; t.dominant_launches = t.n_launches;
+    t.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count();
+    c.timing = t;
+    return GNX_OK;
+}
+
+// the alleles as above, then allele_call_kernel<false>, the scan, one read-back, allele_call_kernel<true> over the array the reduce left
+int run_pile_indel_calls(const gnx_pile_call_opts *o, gnx_pile_indel_call **out_calls, int64_t *out_n) {
+    const auto t_entry = std::chrono::steady_clock::now();
+    if (!o || !out_calls || !out_n) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (!pile_call_opts_ok(o)) return GNX_EINVAL;
+    Ctx &c = ctx_at(0);
+    CtxScope scope(c);
+    int rc;
+    if ((rc = need_pile(c)) || (rc = need_tracking(c))) return rc;
+    if ((rc = ensure_init())) return rc;
+    g_transport = 0; g_bcast_ms = 0;
+    hipStream_t st = c.own_stream;
+    gnx_timing t = {}, ta = {};
+    t.fast_path = 17; t.n_contexts = 1;
+    gnx_pile_indel_call *calls = nullptr;
+    int64_t total = 0;
+    auto run = [&]() -> int {
+        int r;
+        int64_t n = 0;
+        if ((r = pile_alleles_device(c, st, n, ta))) return r;
+        t.cells = n;
+        calls = nullptr;
+        if (n > 0) {
+            const int64_t n_tiles = (n + PILE_TILE - 1) / PILE_TILE;
+            if ((r = c.pl_cnt.ensure((size_t)(n_tiles + 1) * 8)) || (r = c.pl_off.ensure((size_t)(n_tiles + 1) * 8))) return r;
+            int64_t *d_carry = (int64_t *)c.pl_cnt.p + n_tiles;
+            HIPCHK(hipMemsetAsync(d_carry, 0, 8, st));
+            PileIndelCallArgs a;
+            memset(&a, 0, sizeof(a));
+            a.c.kp.b2 = (const unsigned *)c.ref.p; a.c.kp.bflag = (const unsigned long long *)c.ref_flag.p; a.c.kp.brank = (const unsigned *)c.ref_rank.p; a.c.kp.bexc = (const unsigned long long *)c.ref_exc.p;
+            a.c.pile = (const int *)c.pl_tab.p; a.c.region_start = c.pl_start; a.c.region_len = c.pl_len; a.c.n_tiles = n_tiles;
+            a.c.min_depth = o->min_depth; a.c.min_alt = o->min_alt; a.c.frac_num = o->frac_num; a.c.frac_den = o->frac_den; a.c.both_strands = o->both_strands;
+            a.c.cnt = (int64_t *)c.pl_cnt.p; a.c.off = (const int64_t *)c.pl_off.p;
+            a.alleles = (const gnx_pile_allele *)c.pl_al.p; a.n = n;
+            const dim3 grid((unsigned)std::min<int64_t>((n_tiles + 3) / 4, 1 << 20));
+            HIPCHK(hipEventRecord(c.ev[0], st));
+            hipLaunchKernelGGL(allele_call_kernel<false>, grid, dim3(256), 0, st, a);
+            HIPCHK(hipGetLastError());
+            if ((r = launch_scan(a.c.cnt, (int)n_tiles, (int64_t *)c.pl_off.p, d_carry, st))) return r;
+            HIPCHK(hipEventRecord(c.ev[1], st));
+            HIPCHK(hipMemcpyAsync(&total, (const int64_t *)c.pl_off.p + n_tiles, 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            float ms = 0;
+            HIPCHK(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+            t.fill_ms += ms; t.n_launches++;
+            if (total > 0) {
+                if ((r = c.pl_icalls.ensure((size_t)total * sizeof(gnx_pile_indel_call)))) return r;
+                a.out = (gnx_pile_indel_call *)c.pl_icalls.p;
+                HIPCHK(hipEventRecord(c.ev[2], st));
+                hipLaunchKernelGGL(allele_call_kernel<true>, grid, dim3(256), 0, st, a);
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipEventRecord(c.ev[3], st));
+                HIPCHK(hipStreamSynchronize(st));
+                HIPCHK(hipEventElapsedTime(&ms, c.ev[2], c.ev[3]));
+                t.fill_ms += ms; t.n_launches++;
+            }
+        }
+        calls = (gnx_pile_indel_call *)g_pool.get((size_t)std::max<int64_t>(total, 1) * sizeof(gnx_pile_indel_call));
+        if (!calls) { set_err("pinned host allocation failed%s", ""); return GNX_ENOMEM; }
+        if (total > 0) {
+            HIPCHK(hipMemcpyAsync(calls, c.pl_icalls.p, (size_t)total * sizeof(gnx_pile_indel_call), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+        }
+        return GNX_OK;
+    };
+    if ((rc = run())) { (void)hipStreamSynchronize(st); if (calls) g_pool.put(calls); return rc; }
+    *out_calls = calls; *out_n = total;
+    t.dominant_ms = t.fill_ms; t.dominant_launches = t.n_launches; // (dominant_ms: the call kernels alone; fill_ms: with the alleles' sort and reduce)
+    t.fill_ms += ta.fill_ms; t.n_launches += ta.n_launches;
+    t.total_ms = t.fill_ms;
     t.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count();
     c.timing = t;
     return GNX_OK;

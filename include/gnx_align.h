@@ -540,7 +540,8 @@ int gnx_mapq_batch(int64_t n, const int64_t *score, const int64_t *second_score,
  * reference or its release -- and gnx_shutdown drop the pile; gnx_reference_index_build does not.  It covers the region
  * [region_start, region_start + region_len) of the reference.  What comes back is small: rows on request (gnx_pileup_get) and the sparse
  * list of positions where the reads disagree with the reference (gnx_pileup_calls); reads, CIGARs and reference stay where they are.
- * Insertion sequences and deletion lengths are NOT kept (the reference's Pile has maps of both): a count per position is all there is.
+ * Insertion sequences and deletion lengths are kept only by a pile that was told to track alleles (gnx_pileup_track_alleles, below; the
+ * reference's Pile has maps of both); otherwise a count per position is all there is.
  *
  * gnx_pileup_add_by_offset.  GNX_AFFINE_GAP_LOCAL only (any other mode: GNX_EINVAL).  Roles, sequences, ops and ops_off are those of
  * gnx_md_batch_by_offset: the window (ref_start[k], ref_len[k]) is alpha, the read is beta in the orientation it was aligned in -- a
@@ -604,6 +605,68 @@ int gnx_pileup_add_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t
 int gnx_pileup_get(int64_t first, int64_t count, gnx_pile *out);
 int gnx_pileup_calls(const gnx_pile_call_opts *o, gnx_pile_call **out_calls, int64_t *out_n);
 int gnx_pileup_close(void);
+
+/* ---- The alleles of the pile: which deletion, which insertion (the reference's Pile.DelCountF/R keyed by length at the 5'-most deleted
+ * base, InsCountF/R keyed by sequence), the calls they give, and with gonomics_amd/vcf.py a VCF record for each ------------------------- */
+/* gnx_pileup_track_alleles switches the open pile to tracking: every later gnx_pileup_add_by_offset also appends one event per indel to a
+ * log on the device (reads and CIGARs are there only during the add).  Allowed only while reads_added == 0: GNX_EINVAL otherwise, as
+ * without an open pile and for reserve_events < 0.  reserve_events sizes the first log (0: a default of 2^16 events); it is a starting
+ * size, not a limit: an add grows the log, beside the old one, before its first launch that could change the pile, and a growth that
+ * fails is GNX_ENOMEM with pile and log as they were.  gnx_pileup_open replaces the pile, so tracking is off again; whatever drops the
+ * pile drops the log.  gnx_pileup_info keeps reporting the planes only; gnx_pileup_allele_info (any pointer may be NULL; GNX_EINVAL
+ * without an open pile) gives tracking 0 / 1, the events logged so far and the log's bytes on the device (0 when not tracking).  A pile that
+ * does not track behaves exactly as before: the same launches, the same bytes.
+ *
+ * What an add records, for pair k with use == NULL or use[k] != 0, as a function of the column sequence (see gnx_pileup_add_by_offset):
+ *   Deletion    each MAXIMAL inside D run of L columns whose first column is at alpha position i: (pos = ref_start[k] + i, kind 1,
+ *               length L), iff pos lies in the region -- and then whole, even if it runs past the region's end.  A run that starts before
+ *               the region records nothing, though its columns inside still bump `del` (the reference: "only recorded for the 5'-most
+ *               base").
+ *   Insertion   each MAXIMAL inside I run of L read bases behind i consumed alpha bases with alpha_start < i < alpha_end -- the runs that
+ *               bump `ins` --: pos = ref_start[k] + i - 1, iff pos lies in the region.  L <= 21: kind 2 with the bases packed into seq, 3 bits
+ *               each, (code + 1), the first base in the lowest bits, a read N (code 4) as digit 5, 0 ends.  L > 21: kind 3, length only.
+ *               21 bases is what 63 bits hold at 3 bits a base; kind 3 MERGES different sequences of equal length.
+ * The leading and trailing D run and a terminal I run record nothing.  A maximal run may be written as several runs, with zero-length runs
+ * of other ops between them: it is one event.  E.g. window at 100 = ACGTACGTAC, read ACGAACTAC, 6M 1D 3M: (pos 106, kind 1, length 1).
+ * Same window, read ACGTTTACGTAC, 4M 2I 6M: (pos 103, kind 2, length 2, seq = 4 | 4 << 3 = 36).  TTTACG, 3D 2I 4M 3D: nothing.
+ * Every error of the add is still raised before anything changes, the log included; more than 2^31 - 1 events in one pile: GNX_EINVAL
+ * before anything changes.  An add on a tracking pile stays fast_path 14 with dominant_ms = pile_add_kernel alone; allele_log_kernel
+ * (pile_alleles.hip.h: one lane per run, events appended with one atomic add per wave and block of 64 runs) runs behind it over the same
+ * sub-batch cuts and counts in fill_ms.
+ *
+ * gnx_pileup_alleles: the distinct alleles with their counts, ordered by (pos, kind, key), key = length for kinds 1 and 3 and seq as an
+ * unsigned number for kind 2.  The log's order is no part of the contract and no result depends on it; the query leaves the log as it is, so
+ * it may be called twice and between adds.  Invariants: per position and strand the counts of kinds 2 + 3 sum to ins[strand] of the planes;
+ * the counts of kind 1 at x never exceed del[strand] at x.  *out is malloc'd (gnx_free), also for *out_n == 0.  GNX_EINVAL for a null
+ * pointer, without an open pile, without tracking.  Two stable radix sorts, a count pass, the scan family, a write pass.  gnx_get_timing:
+ * fast_path 16, cells = the events.
+ *
+ * gnx_pileup_indel_calls: THIS LIBRARY's rule, as gnx_pileup_calls' is, with its options and its argument errors (and GNX_EINVAL without
+ * tracking).  For every allele in the order above, with c the reference code at pos (c == 4: silent) and depth exactly gnx_pileup_calls'
+ * depth at pos: emitted if it passes the same four tests with its own count / count_fwd.  Several alleles at one position may all pass.
+ * gnx_get_timing: fast_path 17, cells = the alleles.
+ *
+ * Not in scope: left-normalisation of indels against the reference (an allele stands where the CIGAR puts it, as the del / ins counters
+ * do); the sequences of insertions longer than 21 bases; base qualities; more than one region. */
+typedef struct gnx_pile_allele {     /* 32 bytes */
+    int64_t  pos;                    /* deletion: its first deleted base; insertion: the base it stands behind (0-based) */
+    uint64_t seq;                    /* kind 2: the inserted bases, 3 bits each, (code + 1), first base in the lowest bits, 0 ends; else 0 */
+    int32_t  length;                 /* deleted / inserted bases */
+    int32_t  count, count_fwd;       /* reads with exactly this allele; the strand-0 share */
+    uint8_t  kind, _pad[3];          /* 1 deletion, 2 insertion (<= 21 bases, sequence kept), 3 long insertion (> 21, sequence not kept) */
+} gnx_pile_allele;
+typedef struct gnx_pile_indel_call { /* 40 bytes: the allele, then what the rule saw */
+    int64_t  pos;
+    uint64_t seq;
+    int32_t  length, count, count_fwd;
+    uint8_t  kind, _pad[3];
+    int32_t  depth;                  /* gnx_pileup_calls' depth at pos */
+    uint8_t  ref, _pad2[3];          /* the reference code at pos */
+} gnx_pile_indel_call;
+int gnx_pileup_track_alleles(int64_t reserve_events);
+int gnx_pileup_allele_info(int32_t *out_tracking, int64_t *out_events, int64_t *out_device_bytes);
+int gnx_pileup_alleles(gnx_pile_allele **out, int64_t *out_n);
+int gnx_pileup_indel_calls(const gnx_pile_call_opts *o, gnx_pile_indel_call **out_calls, int64_t *out_n);
 
 int gnx_get_timing(gnx_timing *out);
 /* Diagnostics (tests only; nothing in the reference corresponds to it): launch n_workgroups workgroups that each hold one CU's whole

@@ -548,6 +548,34 @@ inline std::vector<gnx_pile_call> PileupCalls(const PileCallOpts &o = PileCallOp
     return res;
 }
 
+// the alleles of the pile (gnx_pileup_track_alleles .. gnx_pileup_indel_calls): which deletion, which insertion
+inline void PileupTrackAlleles(int64_t reserve = 0) { const int rc = gnx_pileup_track_alleles(reserve); if (rc) detail::raise(rc); }
+inline std::vector<gnx_pile_allele> PileupAlleles() {
+    gnx_pile_allele *res = nullptr;
+    int64_t n = 0;
+    const int rc = gnx_pileup_alleles(&res, &n);
+    if (rc) detail::raise(rc);
+    std::vector<gnx_pile_allele> out(res, res + n);
+    gnx_free(res);
+    return out;
+}
+inline std::vector<gnx_pile_indel_call> PileupIndelCalls(const PileCallOpts &o = PileCallOpts()) {
+    const gnx_pile_call_opts co = {o.MinDepth, o.MinAlt, o.FracNum, o.FracDen, o.BothStrands ? 1 : 0, 0};
+    gnx_pile_indel_call *calls = nullptr;
+    int64_t n = 0;
+    const int rc = gnx_pileup_indel_calls(&co, &calls, &n);
+    if (rc) detail::raise(rc);
+    std::vector<gnx_pile_indel_call> res(calls, calls + n);
+    gnx_free(calls);
+    return res;
+}
+// the inserted bases of a kind-2 allele's seq
+inline std::vector<dna::Base> PileupAlleleBases(uint64_t seq) {
+    std::vector<dna::Base> b;
+    for (; seq; seq >>= 3) b.push_back((dna::Base)((seq & 7) - 1));
+    return b;
+}
+
 inline void AffineGapLocalEngine(const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, std::vector<TargetQueryPair> &pairs) {
     std::vector<std::vector<dna::Base>> t, q;
     for (auto &p : pairs) { t.push_back(p.Target); q.push_back(p.Query); }
