@@ -28,7 +28,8 @@ EXPORTS = ["gnx_device_count", "gnx_init", "gnx_shutdown", "gnx_last_error", "gn
            "gnx_summarize_batch", "gnx_summarize_batch_windows", "gnx_summarize_batch_by_offset",
            "gnx_md_batch", "gnx_md_batch_windows", "gnx_md_batch_by_offset", "gnx_mapq_batch",
            "gnx_pileup_open", "gnx_pileup_info", "gnx_pileup_add_by_offset", "gnx_pileup_get", "gnx_pileup_calls", "gnx_pileup_close",
-           "gnx_pileup_track_alleles", "gnx_pileup_allele_info", "gnx_pileup_alleles", "gnx_pileup_indel_calls"]
+           "gnx_pileup_track_alleles", "gnx_pileup_allele_info", "gnx_pileup_alleles", "gnx_pileup_indel_calls",
+           "gnx_pileup_alleles_norm", "gnx_pileup_indel_calls_norm"]
 GNX_XCOL_EQ, GNX_XCOL_X = 3, 4
 
 
@@ -229,6 +230,11 @@ def lib():
             L.gnx_pileup_alleles.restype = ctypes.c_int
             L.gnx_pileup_indel_calls.argtypes = [ctypes.POINTER(GnxPileCallOpts), ctypes.POINTER(c_p), ctypes.POINTER(i64)]
             L.gnx_pileup_indel_calls.restype = ctypes.c_int
+        if hasattr(L, "gnx_pileup_alleles_norm"):
+            L.gnx_pileup_alleles_norm.argtypes = L.gnx_pileup_alleles.argtypes
+            L.gnx_pileup_alleles_norm.restype = ctypes.c_int
+            L.gnx_pileup_indel_calls_norm.argtypes = L.gnx_pileup_indel_calls.argtypes
+            L.gnx_pileup_indel_calls_norm.restype = ctypes.c_int
         L.gnx_seed_index_build.argtypes = [c_p, c_p, i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(i64)]
         L.gnx_seed_index_build.restype = ctypes.c_int
         L.gnx_seed_index_set.argtypes = [c_p, c_p, i64, c_p, c_p, i64, ctypes.c_int]
@@ -884,15 +890,18 @@ def _taken(call, dtype):
         lib().gnx_free(res_p)
 
 
-def pileup_alleles():
-    """gnx_pileup_alleles -> PILE_ALLELE_DTYPE array, ordered by (pos, kind, key)"""
-    return _taken(lambda p, n: lib().gnx_pileup_alleles(p, n), PILE_ALLELE_DTYPE)
+def pileup_alleles(normalize=False):
+    """gnx_pileup_alleles (normalize: gnx_pileup_alleles_norm, every event left-normalised first) -> PILE_ALLELE_DTYPE array, ordered by
+    (pos, kind, key)"""
+    entry = lib().gnx_pileup_alleles_norm if normalize else lib().gnx_pileup_alleles
+    return _taken(lambda p, n: entry(p, n), PILE_ALLELE_DTYPE)
 
 
-def pileup_indel_calls(min_depth, min_alt, frac_num, frac_den, both_strands=0):
-    """gnx_pileup_indel_calls -> PILE_INDEL_CALL_DTYPE array, in the alleles' order"""
+def pileup_indel_calls(min_depth, min_alt, frac_num, frac_den, both_strands=0, normalize=False):
+    """gnx_pileup_indel_calls (normalize: gnx_pileup_indel_calls_norm) -> PILE_INDEL_CALL_DTYPE array, in the alleles' order"""
     o = GnxPileCallOpts(int(min_depth), int(min_alt), int(frac_num), int(frac_den), int(both_strands), 0)
-    return _taken(lambda p, n: lib().gnx_pileup_indel_calls(ctypes.byref(o), p, n), PILE_INDEL_CALL_DTYPE)
+    entry = lib().gnx_pileup_indel_calls_norm if normalize else lib().gnx_pileup_indel_calls
+    return _taken(lambda p, n: entry(ctypes.byref(o), p, n), PILE_INDEL_CALL_DTYPE)
 
 
 def pack_inserted(bases):

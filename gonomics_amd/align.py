@@ -629,20 +629,24 @@ def _allele_dict(a):
             "count": int(a["count"]), "count_fwd": int(a["count_fwd"])}
 
 
-def PileupAlleles():
+def PileupAlleles(normalize=False):
     """The distinct indel alleles of a tracking pile with their counts (gnx_pileup_alleles), ordered by position, kind and key: one dict
     each -- pos (a deletion's first deleted base; the base an insertion stands behind), kind ("del" / "ins" / "long_ins"), length, seq
-    (the inserted base codes for "ins", else None: a long insertion keeps its length only), count, count_fwd."""
+    (the inserted base codes for "ins", else None: a long insertion keeps its length only), count, count_fwd.
+    normalize=True (gnx_pileup_alleles_norm): every allele is first moved to its leftmost placement against the reference inside the
+    pile's region, so the placements of one deletion along a homopolymer or a tandem repeat are one allele with the summed counts; a
+    long insertion stays where it is.  The pile and its log are not changed."""
     try:
-        return [_allele_dict(a) for a in _lib.pileup_alleles()]
+        return [_allele_dict(a) for a in _lib.pileup_alleles(normalize=bool(normalize))]
     except _lib.GnxError as e:
         _raise(e)
 
 
-def PileupIndelCalls(min_depth, min_alt, frac=(1, 2), both_strands=False):
-    """The alleles that pass the library's rule (gnx_pileup_indel_calls), in PileupAlleles' order: its dicts plus depth and ref."""
+def PileupIndelCalls(min_depth, min_alt, frac=(1, 2), both_strands=False, normalize=False):
+    """The alleles that pass the library's rule (gnx_pileup_indel_calls), in PileupAlleles' order: its dicts plus depth and ref.
+    normalize=True (gnx_pileup_indel_calls_norm): the rule is put to the left-normalised alleles, with the depth at their new position."""
     try:
-        calls = _lib.pileup_indel_calls(min_depth, min_alt, frac[0], frac[1], 1 if both_strands else 0)
+        calls = _lib.pileup_indel_calls(min_depth, min_alt, frac[0], frac[1], 1 if both_strands else 0, normalize=bool(normalize))
     except _lib.GnxError as e:
         _raise(e)
     return [dict(_allele_dict(c), depth=int(c["depth"]), ref=int(c["ref"])) for c in calls]

@@ -60,6 +60,7 @@
 #include "aln_md.hip.h"
 #include "pileup.hip.h"
 #include "pile_alleles.hip.h"
+#include "pile_norm.hip.h"
 
 namespace {
 
@@ -158,7 +159,7 @@ struct Ctx {
     DevBuf pl_tab, pl_in, pl_cnt, pl_off, pl_calls;
     int64_t pl_start = 0, pl_len = -1, pl_reads = 0; // pl_len >= 0: a pile over [pl_start, pl_start + pl_len) is open; reads added so far
     // a tracking pile's log of indel events (gnx_pileup_track_alleles; pile_alleles.hip.h): two planes of pl_log_cap words, the cursor, the query's scratch
-    DevBuf pl_log, pl_cur, pl_sort[5], pl_al, pl_icalls;
+    DevBuf pl_log, pl_cur, pl_sort[5], pl_al, pl_icalls, pl_norm; // pl_norm: the normalised events of a ..._norm query (pile_norm.hip.h), two planes
     bool pl_track = false;
     int64_t pl_log_cap = 0, pl_events = 0; // events the planes hold; events logged so far (the cursor's value after the last add)
     int pl_key_bits = 1;                   // no event's key needs more bits than this (from the runs of the added pairs): the sort's range
@@ -2753,7 +2754,7 @@ void drop_reference_index(Ctx &c) {
 // the log of a tracking pile goes with the planes (and when gnx_pileup_open replaces the pile: tracking is off again)
 void drop_pile_log(Ctx &c) {
     c.pl_track = false; c.pl_log_cap = 0; c.pl_events = 0; c.pl_key_bits = 1;
-    c.pl_log.release(); c.pl_cur.release(); c.pl_al.release(); c.pl_icalls.release();
+    c.pl_log.release(); c.pl_cur.release(); c.pl_al.release(); c.pl_icalls.release(); c.pl_norm.release();
     for (DevBuf &b : c.pl_sort) b.release();
 }
 // ... and so does the pile (gnx_pileup_*), though not to a rebuilt index: its counts are positions of THAT reference
@@ -3194,12 +3195,22 @@ int gnx_pileup_allele_info(int32_t *out_tracking, int64_t *out_events, int64_t *
 
 int gnx_pileup_alleles(gnx_pile_allele **out, int64_t *out_n) {
     ApiCall api;
-    return run_pile_alleles(out, out_n);
+    return run_pile_alleles(out, out_n, false);
 }
 
 int gnx_pileup_indel_calls(const gnx_pile_call_opts *o, gnx_pile_indel_call **out_calls, int64_t *out_n) {
     ApiCall api;
-    return run_pile_indel_calls(o, out_calls, out_n);
+    return run_pile_indel_calls(o, out_calls, out_n, false);
+}
+
+int gnx_pileup_alleles_norm(gnx_pile_allele **out, int64_t *out_n) {
+    ApiCall api;
+    return run_pile_alleles(out, out_n, true);
+}
+
+int gnx_pileup_indel_calls_norm(const gnx_pile_call_opts *o, gnx_pile_indel_call **out_calls, int64_t *out_n) {
+    ApiCall api;
+    return run_pile_indel_calls(o, out_calls, out_n, true);
 }
 
 int gnx_pileup_close(void) {

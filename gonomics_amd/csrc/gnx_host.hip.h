@@ -1679,13 +1679,32 @@ int need_tracking(const Ctx &c) {
 // The distinct alleles of the log, ordered and counted, left in c.pl_al on the device: two stable radix sorts of the log's planes into
 // scratch (by w1, then by w0: the order is (pos, kind, key, strand)), allele_reduce_kernel<false>, the scan of the tiles' counts,
 // one read-back that sizes the array, allele_reduce_kernel<true>.  The log is only read.
-int pile_alleles_device(Ctx &c, hipStream_t st, int64_t &n_alleles, gnx_timing &t) {
+// norm (the ..._norm entries): norm_shift_kernel first writes every event, left-normalised, into the two planes of
+// c.pl_norm, and the sorts read those.  Their bit ranges hold: a rotated sequence has its digits, a position only shrinks.  norm_ms is
+// that kernel alone.  GNX_NORM_COOP=0: every lane finishes its event alone (tests; the results do not depend on it).
+int pile_alleles_device(Ctx &c, hipStream_t st, int64_t &n_alleles, gnx_timing &t, bool norm = false, float *norm_ms = nullptr) {
     const int64_t n = c.pl_events;
     n_alleles = 0;
     if (n == 0) return GNX_OK;
     int r;
     for (int k = 0; k < 4; k++) if ((r = c.pl_sort[k].ensure((size_t)n * 8))) return r;
     unsigned long long *w0 = (unsigned long long *)c.pl_log.p, *w1 = w0 + c.pl_log_cap;
+    if (norm) {
+        if ((r = c.pl_norm.ensure((size_t)n * 16))) return r;
+        NormArgs na;
+        memset(&na, 0, sizeof(na));
+        na.kp.b2 = (const unsigned *)c.ref.p; na.kp.bflag = (const unsigned long long *)c.ref_flag.p; na.kp.brank = (const unsigned *)c.ref_rank.p; na.kp.bexc = (const unsigned long long *)c.ref_exc.p;
+        na.w0 = w0; na.w1 = w1; na.o0 = (unsigned long long *)c.pl_norm.p; na.o1 = na.o0 + n;
+        na.n = n; na.region_start = c.pl_start; na.ref_len = c.ref_len;
+        const char *e = getenv("GNX_NORM_COOP");
+        na.coop = e && e[0] == '0' ? 0 : 1;
+        HIPCHK(hipEventRecord(c.ev[4], st));
+        hipLaunchKernelGGL(norm_shift_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1 << 20)), dim3(256), 0, st, na);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c.ev[5], st));
+        t.n_launches++;
+        w0 = na.o0; w1 = na.o1;
+    }
     unsigned long long *s_w1 = (unsigned long long *)c.pl_sort[0].p, *s_w0 = (unsigned long long *)c.pl_sort[1].p;   // ordered by w1
     unsigned long long *o_w0 = (unsigned long long *)c.pl_sort[2].p, *o_w1 = (unsigned long long *)c.pl_sort[3].p;   // ordered by (w0, w1)
     // the bits that can differ: the strand and the longest key of any added pair; the region's positions and the kind
@@ -1717,6 +1736,11 @@ int pile_alleles_device(Ctx &c, hipStream_t st, int64_t &n_alleles, gnx_timing &
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
     t.fill_ms += ms; t.n_launches += 3;
+    if (norm) {
+        HIPCHK(hipEventElapsedTime(&ms, c.ev[4], c.ev[5]));
+        t.fill_ms += ms;
+        if (norm_ms) *norm_ms = ms;
+    }
     if ((r = c.pl_al.ensure((size_t)n_alleles * sizeof(gnx_pile_allele)))) return r;
     a.out = (gnx_pile_allele *)c.pl_al.p;
     HIPCHK(hipEventRecord(c.ev[2], st));
@@ -1729,7 +1753,7 @@ int pile_alleles_device(Ctx &c, hipStream_t st, int64_t &n_alleles, gnx_timing &
     return GNX_OK;
 }
 
-int run_pile_alleles(gnx_pile_allele **out, int64_t *out_n) {
+int run_pile_alleles(gnx_pile_allele **out, int64_t *out_n, bool norm) {
     const auto t_entry = std::chrono::steady_clock::now();
     if (!out || !out_n) { set_err("bad argument%s", ""); return GNX_EINVAL; }
     Ctx &c = ctx_at(0);
@@ -1740,12 +1764,13 @@ int run_pile_alleles(gnx_pile_allele **out, int64_t *out_n) {
     g_transport = 0; g_bcast_ms = 0;
     hipStream_t st = c.own_stream;
     gnx_timing t = {};
-    t.fast_path = 16; t.cells = c.pl_events; t.n_contexts = 1;
+    t.fast_path = norm ? 18 : 16; t.cells = c.pl_events; t.n_contexts = 1;
     gnx_pile_allele *res = nullptr;
     int64_t total = 0;
+    float norm_ms = 0;
     auto run = [&]() -> int {
         int r;
-        if ((r = pile_alleles_device(c, st, total, t))) return r;
+        if ((r = pile_alleles_device(c, st, total, t, norm, &norm_ms))) return r;
         res = (gnx_pile_allele *)g_pool.get((size_t)std::max<int64_t>(total, 1) * sizeof(gnx_pile_allele));
         if (!res) { set_err("pinned host allocation failed%s", ""); return GNX_ENOMEM; }
         if (total > 0) {
@@ -1757,13 +1782,14 @@ int run_pile_alleles(gnx_pile_allele **out, int64_t *out_n) {
     if ((rc = run())) { (void)hipStreamSynchronize(st); if (res) g_pool.put(res); return rc; }
     *out = res; *out_n = total;
     t.dominant_ms = t.total_ms = t.fill_ms; t.dominant_launches = t.n_launches;
+    if (norm) { t.dominant_ms = norm_ms; t.dominant_launches = c.pl_events > 0 ? 1 : 0; } // (dominant_ms: norm_shift_kernel alone)
     t.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count();
     c.timing = t;
     return GNX_OK;
 }
 
 // the alleles as above, then allele_call_kernel<false>, the scan, one read-back, allele_call_kernel<true> over the array the reduce left
-int run_pile_indel_calls(const gnx_pile_call_opts *o, gnx_pile_indel_call **out_calls, int64_t *out_n) {
+int run_pile_indel_calls(const gnx_pile_call_opts *o, gnx_pile_indel_call **out_calls, int64_t *out_n, bool norm) {
     const auto t_entry = std::chrono::steady_clock::now();
     if (!o || !out_calls || !out_n) { set_err("bad argument%s", ""); return GNX_EINVAL; }
     if (!pile_call_opts_ok(o)) return GNX_EINVAL;
@@ -1775,13 +1801,14 @@ int run_pile_indel_calls(const gnx_pile_call_opts *o, gnx_pile_indel_call **out_
     g_transport = 0; g_bcast_ms = 0;
     hipStream_t st = c.own_stream;
     gnx_timing t = {}, ta = {};
-    t.fast_path = 17; t.n_contexts = 1;
+    t.fast_path = norm ? 19 : 17; t.n_contexts = 1;
     gnx_pile_indel_call *calls = nullptr;
     int64_t total = 0;
+    float norm_ms = 0;
     auto run = [&]() -> int {
         int r;
         int64_t n = 0;
-        if ((r = pile_alleles_device(c, st, n, ta))) return r;
+        if ((r = pile_alleles_device(c, st, n, ta, norm, &norm_ms))) return r;
         t.cells = n;
         calls = nullptr;
         if (n > 0) {
@@ -1830,6 +1857,7 @@ int run_pile_indel_calls(const gnx_pile_call_opts *o, gnx_pile_indel_call **out_
     if ((rc = run())) { (void)hipStreamSynchronize(st); if (calls) g_pool.put(calls); return rc; }
     *out_calls = calls; *out_n = total;
     t.dominant_ms = t.fill_ms; t.dominant_launches = t.n_launches; // (dominant_ms: the call kernels alone; fill_ms: with the alleles' sort and reduce)
+    if (norm) { t.dominant_ms = norm_ms; t.dominant_launches = c.pl_events > 0 ? 1 : 0; } // (the normalised query: norm_shift_kernel alone)
     t.fill_ms += ta.fill_ms; t.n_launches += ta.n_launches;
     t.total_ms = t.fill_ms;
     t.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count();

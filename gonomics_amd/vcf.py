@@ -2,7 +2,8 @@
 
 WriteVcf() is text formatting only, as sam.Lines() is: which positions are called, with which allele, depth and counts, was decided on
 the device by the library's two rules (include/gnx_align.h); the only bases looked up here are the reference letters a VCF record has
-to spell out.  Indels stand where the CIGARs put them: nothing is left-normalised.
+to spell out.  Indels stand where the calls put them: nothing is left-normalised here.  Left-aligned records come from normalised calls,
+align.PileupIndelCalls(..., normalize=True), which are the same dicts.
 """
 import numpy as np
 

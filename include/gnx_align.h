@@ -646,8 +646,27 @@ int gnx_pileup_close(void);
  * depth at pos: emitted if it passes the same four tests with its own count / count_fwd.  Several alleles at one position may all pass.
  * gnx_get_timing: fast_path 17, cells = the alleles.
  *
- * Not in scope: left-normalisation of indels against the reference (an allele stands where the CIGAR puts it, as the del / ins counters
- * do); the sequences of insertions longer than 21 bases; base qualities; more than one region. */
+ * gnx_pileup_alleles_norm / gnx_pileup_indel_calls_norm: the same two queries over LEFT-NORMALISED events.  The plain
+ * queries leave an allele where the CIGAR puts it, so one deletion in a homopolymer or a tandem repeat comes out as several alleles with a
+ * share of the count each; these move every event of the log to its leftmost placement first.  The rule is the standard one (bcftools norm;
+ * Tan et al. 2015), taken per allele against the reference alone, R = the reference in codes, lo = the pile's region_start:
+ *   Deletion (x, L)            while x - 1 >= lo, R[x - 1] < 4 and R[x - 1] == R[x + L - 1]: x -= 1.  The length does not change.
+ *   Insertion (x, s), kind 2   while x - 1 >= lo, R[x] < 4, s's last base is no read N and R[x] == s[L - 1]: s = R[x] + s[0 .. L - 1), x -= 1.
+ *   Long insertion, kind 3     unchanged: only its length was kept, and without its bases it cannot be shifted.
+ * An N, in the reference or among the inserted bases, matches nothing and stops the shift.  The position never goes below region_start:
+ * the result is the leftmost placement INSIDE THE REGION, so a pile whose region starts inside a repeat reports the allele at the
+ * region's first base where a wider region would move it further.  The shift has no upper bound.  E.g. reference GATTTTTC: deletion (6, 1)
+ * -> (2, 1); insertion T behind 6 -> T behind 1; insertion GT behind 6 -> TG behind 5.
+ * The normalised events are then reduced as gnx_pileup_alleles reduces the raw ones -- alleles that stood apart may merge; the sum of count
+ * and of count_fwd over the alleles of a kind equals the plain query's -- and gnx_pileup_indel_calls_norm puts them to gnx_pileup_indel_calls'
+ * four tests with that rule's depth and reference code at the NORMALISED position.  Signatures, errors and the ownership of the result
+ * are those of the plain entries.  The log stays raw: a plain query after a normalised one returns what it returned before, and adds go on
+ * as before.  The del / ins counters of the planes, and so gnx_pileup_calls, stay per column.  gnx_get_timing: fast_path 18 (alleles) and
+ * 19 (calls), dominant_ms = norm_shift_kernel alone (pile_norm.hip.h).  GNX_NORM_COOP=0 makes every lane of that kernel finish its event
+ * alone; the results are the same.
+ *
+ * Not in scope: the sequences of insertions longer than 21 bases; normalising an allele across other variants of the same read; base
+ * qualities; more than one region. */
 typedef struct gnx_pile_allele {     /* 32 bytes */
     int64_t  pos;                    /* deletion: its first deleted base; insertion: the base it stands behind (0-based) */
     uint64_t seq;                    /* kind 2: the inserted bases, 3 bits each, (code + 1), first base in the lowest bits, 0 ends; else 0 */
@@ -667,6 +686,8 @@ int gnx_pileup_track_alleles(int64_t reserve_events);
 int gnx_pileup_allele_info(int32_t *out_tracking, int64_t *out_events, int64_t *out_device_bytes);
 int gnx_pileup_alleles(gnx_pile_allele **out, int64_t *out_n);
 int gnx_pileup_indel_calls(const gnx_pile_call_opts *o, gnx_pile_indel_call **out_calls, int64_t *out_n);
+int gnx_pileup_alleles_norm(gnx_pile_allele **out, int64_t *out_n);
+int gnx_pileup_indel_calls_norm(const gnx_pile_call_opts *o, gnx_pile_indel_call **out_calls, int64_t *out_n);
 
 int gnx_get_timing(gnx_timing *out);
 /* Diagnostics (tests only; nothing in the reference corresponds to it): launch n_workgroups workgroups that each hold one CU's whole

@@ -550,20 +550,22 @@ inline std::vector<gnx_pile_call> PileupCalls(const PileCallOpts &o = PileCallOp
 
 // the alleles of the pile (gnx_pileup_track_alleles .. gnx_pileup_indel_calls): which deletion, which insertion
 inline void PileupTrackAlleles(int64_t reserve = 0) { const int rc = gnx_pileup_track_alleles(reserve); if (rc) detail::raise(rc); }
-inline std::vector<gnx_pile_allele> PileupAlleles() {
+// normalize: every allele is first moved to its leftmost placement against the reference inside the region (gnx_pileup_alleles_norm /
+// gnx_pileup_indel_calls_norm); the pile and its log are not changed
+inline std::vector<gnx_pile_allele> PileupAlleles(bool normalize = false) {
     gnx_pile_allele *res = nullptr;
     int64_t n = 0;
-    const int rc = gnx_pileup_alleles(&res, &n);
+    const int rc = normalize ? gnx_pileup_alleles_norm(&res, &n) : gnx_pileup_alleles(&res, &n);
     if (rc) detail::raise(rc);
     std::vector<gnx_pile_allele> out(res, res + n);
     gnx_free(res);
     return out;
 }
-inline std::vector<gnx_pile_indel_call> PileupIndelCalls(const PileCallOpts &o = PileCallOpts()) {
+inline std::vector<gnx_pile_indel_call> PileupIndelCalls(const PileCallOpts &o = PileCallOpts(), bool normalize = false) {
     const gnx_pile_call_opts co = {o.MinDepth, o.MinAlt, o.FracNum, o.FracDen, o.BothStrands ? 1 : 0, 0};
     gnx_pile_indel_call *calls = nullptr;
     int64_t n = 0;
-    const int rc = gnx_pileup_indel_calls(&co, &calls, &n);
+    const int rc = normalize ? gnx_pileup_indel_calls_norm(&co, &calls, &n) : gnx_pileup_indel_calls(&co, &calls, &n);
     if (rc) detail::raise(rc);
     std::vector<gnx_pile_indel_call> res(calls, calls + n);
     gnx_free(calls);
