@@ -29,7 +29,8 @@ EXPORTS = ["gnx_device_count", "gnx_init", "gnx_shutdown", "gnx_last_error", "gn
            "gnx_md_batch", "gnx_md_batch_windows", "gnx_md_batch_by_offset", "gnx_mapq_batch",
            "gnx_pileup_open", "gnx_pileup_info", "gnx_pileup_add_by_offset", "gnx_pileup_get", "gnx_pileup_calls", "gnx_pileup_close",
            "gnx_pileup_track_alleles", "gnx_pileup_allele_info", "gnx_pileup_alleles", "gnx_pileup_indel_calls",
-           "gnx_pileup_alleles_norm", "gnx_pileup_indel_calls_norm"]
+           "gnx_pileup_alleles_norm", "gnx_pileup_indel_calls_norm",
+           "gnx_pileup_track_qualities", "gnx_pileup_qual_info", "gnx_pileup_add_by_offset_qual", "gnx_pileup_get_qual", "gnx_pileup_genotypes"]
 GNX_XCOL_EQ, GNX_XCOL_X = 3, 4
 
 
@@ -93,6 +94,19 @@ PILE_INDEL_CALL_DTYPE = np.dtype({"names": ["pos", "seq", "length", "count", "co
                                   "formats": [np.int64, np.uint64, np.int32, np.int32, np.int32, np.uint8, (np.uint8, (3,)), np.int32, np.uint8, (np.uint8, (3,))],
                                   "offsets": [0, 8, 16, 20, 24, 28, 29, 32, 36, 37], "itemsize": 40})
 PILE_SEQ_MAX = 21  # inserted bases whose sequence an allele keeps
+
+
+class GnxGenoOpts(ctypes.Structure):
+    _fields_ = [("min_depth", ctypes.c_int32), ("min_qual", ctypes.c_int32), ("prior_het", ctypes.c_int32), ("prior_hom", ctypes.c_int32),
+                ("_reserved", ctypes.c_int32 * 2)]
+
+
+# gnx_pile_genotype: one diploid SNP genotype, 48 bytes (centi-Phred pl / gq / qual)
+PILE_GENOTYPE_DTYPE = np.dtype({"names": ["pos", "pl", "gq", "qual", "depth", "ref_count", "alt_count", "alt_fwd", "gt", "ref", "alt", "_pad"],
+                                "formats": [np.int64, (np.int32, (3,)), np.int32, np.int32, np.int32, np.int32, np.int32, np.int32, np.uint8, np.uint8, np.uint8, np.uint8],
+                                "offsets": [0, 8, 20, 24, 28, 32, 36, 40, 44, 45, 46, 47], "itemsize": 48})
+QUAL_MAX = 93                      # a quality byte above it counts as 93
+QUAL_MAX_READS = (2 ** 31 - 1) // 93  # reads a quality pile takes: 23 091 222
 
 
 class GnxError(RuntimeError):
@@ -235,6 +249,17 @@ def lib():
             L.gnx_pileup_alleles_norm.restype = ctypes.c_int
             L.gnx_pileup_indel_calls_norm.argtypes = L.gnx_pileup_indel_calls.argtypes
             L.gnx_pileup_indel_calls_norm.restype = ctypes.c_int
+        if hasattr(L, "gnx_pileup_track_qualities"):
+            L.gnx_pileup_track_qualities.argtypes = [ctypes.c_int32]
+            L.gnx_pileup_track_qualities.restype = ctypes.c_int
+            L.gnx_pileup_qual_info.argtypes = [c_p, c_p, c_p]
+            L.gnx_pileup_qual_info.restype = ctypes.c_int
+            L.gnx_pileup_add_by_offset_qual.argtypes = L.gnx_pileup_add_by_offset.argtypes + [c_p]
+            L.gnx_pileup_add_by_offset_qual.restype = ctypes.c_int
+            L.gnx_pileup_get_qual.argtypes = [i64, i64, c_p]
+            L.gnx_pileup_get_qual.restype = ctypes.c_int
+            L.gnx_pileup_genotypes.argtypes = [ctypes.POINTER(GnxGenoOpts), ctypes.POINTER(c_p), ctypes.POINTER(i64)]
+            L.gnx_pileup_genotypes.restype = ctypes.c_int
         L.gnx_seed_index_build.argtypes = [c_p, c_p, i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(i64)]
         L.gnx_seed_index_build.restype = ctypes.c_int
         L.gnx_seed_index_set.argtypes = [c_p, c_p, i64, c_p, c_p, i64, ctypes.c_int]
@@ -902,6 +927,49 @@ def pileup_indel_calls(min_depth, min_alt, frac_num, frac_den, both_strands=0, n
     o = GnxPileCallOpts(int(min_depth), int(min_alt), int(frac_num), int(frac_den), int(both_strands), 0)
     entry = lib().gnx_pileup_indel_calls_norm if normalize else lib().gnx_pileup_indel_calls
     return _taken(lambda p, n: entry(ctypes.byref(o), p, n), PILE_INDEL_CALL_DTYPE)
+
+
+def pileup_track_qualities(min_baseq=0):
+    """gnx_pileup_track_qualities: the open pile, still empty, sums the qualities of its bases from now on; bases below min_baseq count nowhere."""
+    check(lib().gnx_pileup_track_qualities(int(min_baseq)))
+
+
+def pileup_qual_info():
+    """gnx_pileup_qual_info -> {"tracking", "min_baseq", "device_bytes"}"""
+    tr, v = np.zeros(2, dtype=np.int32), np.zeros(1, dtype=np.int64)
+    check(lib().gnx_pileup_qual_info(tr.ctypes.data, tr.ctypes.data + 4, v.ctypes.data))
+    return {"tracking": bool(tr[0]), "min_baseq": int(tr[1]), "device_bytes": int(v[0])}
+
+
+def pileup_add_by_offset_qual(params, read_cat, read_off, ref_start, ref_len, strand, ops, ops_off, qual_cat, use=None):
+    """gnx_pileup_add_by_offset_qual: pileup_add_by_offset with the reads' raw Phred qualities, laid out like read_cat."""
+    read_cat, read_off, ref_start, ref_len, ops_off, strand = _u8(read_cat), _i64(read_off), _i64(ref_start), _i64(ref_len), _i64(ops_off), _u8(strand)
+    n, ops = int(ref_start.shape[0]), _ops_array(ops)
+    if strand.shape[0] != n or (use is not None and len(use) != n):
+        raise ValueError("pileup_add_by_offset_qual: one strand byte (and one use byte) per pair")
+    if qual_cat is not None:
+        qual_cat = _u8(qual_cat)
+        if qual_cat.shape[0] != read_cat.shape[0]:
+            raise ValueError("pileup_add_by_offset_qual: one quality per read base")
+    use = None if use is None else _u8(use)
+    check(lib().gnx_pileup_add_by_offset_qual(ctypes.byref(params), n, read_cat.ctypes.data, read_off.ctypes.data, ref_start.ctypes.data, ref_len.ctypes.data,
+                                              strand.ctypes.data if n else None, ops.ctypes.data, ops_off.ctypes.data, None if use is None else use.ctypes.data,
+                                              None if qual_cat is None else qual_cat.ctypes.data))
+
+
+def pileup_get_qual(first=0, count=None):
+    """gnx_pileup_get_qual: the qsum rows first .. first + count of the open quality pile as an int32 array [count][4] (A C G T)."""
+    if count is None:
+        count = pileup_info()["len"] - int(first)
+    out = np.zeros((max(int(count), 1), 4), dtype=np.int32)
+    check(lib().gnx_pileup_get_qual(int(first), int(count), out.ctypes.data))
+    return out[:max(int(count), 0)]
+
+
+def pileup_genotypes(min_depth, min_qual=0, prior_het=3000, prior_hom=3300):
+    """gnx_pileup_genotypes -> PILE_GENOTYPE_DTYPE array, ordered by position"""
+    o = GnxGenoOpts(int(min_depth), int(min_qual), int(prior_het), int(prior_hom))
+    return _taken(lambda p, n: lib().gnx_pileup_genotypes(ctypes.byref(o), p, n), PILE_GENOTYPE_DTYPE)
 
 
 def pack_inserted(bases):

@@ -568,16 +568,35 @@ def PileupInfo():
         _raise(e)
 
 
-def PileupAdd(params, reads, windows, strands, routes, use=None):
+def _phred(q):
+    """one read's qualities as raw Phred bytes: a uint8 array as it is, a str / bytes as ASCII + 33"""
+    if isinstance(q, (str, bytes)):
+        v = np.frombuffer(q.encode("ascii") if isinstance(q, str) else q, dtype=np.uint8)
+        if v.size and v.min() < 33:
+            raise ValueError("a quality character below '!' (ASCII 33)")
+        return v - 33
+    return np.asarray(q, dtype=np.uint8)
+
+
+def PileupAdd(params, reads, windows, strands, routes, use=None, quals=None):
     """Add finished alignments to the open pile (gnx_pileup_add_by_offset, GNX_AFFINE_GAP_LOCAL): windows[k] = (start, len) of the
     resident reference, reads[k] in the orientation it was aligned in (a strand-1 winner: its reverse complement), strands[k] in
-    {0, 1} the counter it goes to, routes[k] its CIGAR; use[k] == 0 leaves pair k out.  include/gnx_align.h defines what is counted."""
+    {0, 1} the counter it goes to, routes[k] its CIGAR; use[k] == 0 leaves pair k out.  include/gnx_align.h defines what is counted.
+    quals (a pile that tracks qualities, PileupTrackQualities; gnx_pileup_add_by_offset_qual): quals[k] holds one quality per base of
+    reads[k], in the same orientation, as a uint8 array of raw Phred values or as a string of ASCII + 33 characters."""
     if not routes:
         return
     ops, off = _routes_to_ops(routes)
     r_cat, r_off = _lib._cat(list(reads))
     try:
-        _lib.pileup_add_by_offset(params, r_cat, r_off, [w[0] for w in windows], [w[1] for w in windows], strands, ops, off, use=use)
+        if quals is None:
+            _lib.pileup_add_by_offset(params, r_cat, r_off, [w[0] for w in windows], [w[1] for w in windows], strands, ops, off, use=use)
+        else:
+            quals = [_phred(q) for q in quals]
+            if len(quals) != len(reads) or any(len(q) != len(r) for q, r in zip(quals, reads)):
+                raise ValueError("PileupAdd: one quality per read base")
+            q_cat, _ = _lib._cat(quals)
+            _lib.pileup_add_by_offset_qual(params, r_cat, r_off, [w[0] for w in windows], [w[1] for w in windows], strands, ops, off, q_cat, use=use)
     except _lib.GnxError as e:
         _raise(e)
 
@@ -652,10 +671,49 @@ def PileupIndelCalls(min_depth, min_alt, frac=(1, 2), both_strands=False, normal
     return [dict(_allele_dict(c), depth=int(c["depth"]), ref=int(c["ref"])) for c in calls]
 
 
-def PileupAddReport(params, reads, report, min_mapq=0):
+def PileupTrackQualities(min_baseq=0):
+    """The open pile, still empty, sums the base qualities of what it counts from now on (gnx_pileup_track_qualities), and a read base
+    whose quality is below min_baseq (0 .. 93) counts nowhere.  Its reads then come through PileupAdd(..., quals=...)."""
+    try:
+        _lib.pileup_track_qualities(min_baseq)
+    except _lib.GnxError as e:
+        _raise(e)
+
+
+def PileupQualInfo():
+    """{"tracking", "min_baseq", "device_bytes"} of the open pile's quality planes"""
+    try:
+        return _lib.pileup_qual_info()
+    except _lib.GnxError as e:
+        _raise(e)
+
+
+def PileupGetQual(first=0, count=None):
+    """The quality sums of rows first .. first + count of the open quality pile (count None: to the end of its region): an int32 array
+    [count][4], the summed Phred qualities of the counted A C G T bases, both strands."""
+    try:
+        return _lib.pileup_get_qual(first, count)
+    except _lib.GnxError as e:
+        _raise(e)
+
+
+def PileupGenotypes(min_depth, min_qual=0, prior_het=3000, prior_hom=3300):
+    """The diploid SNP genotypes of a quality pile by the library's rule (gnx_pileup_genotypes), ordered by position: one dict per
+    position whose best genotype is not ref / ref -- pos, gt (1 ref / alt, 2 alt / alt), ref, alt (base codes), pl (three values, 0 for
+    the called genotype), gq, qual (all in centi-Phred, 1/100 of a Phred unit), depth, ref_count, alt_count, alt_fwd."""
+    try:
+        recs = _lib.pileup_genotypes(min_depth, min_qual, prior_het, prior_hom)
+    except _lib.GnxError as e:
+        _raise(e)
+    return [{"pos": int(g["pos"]), "gt": int(g["gt"]), "ref": int(g["ref"]), "alt": int(g["alt"]), "pl": [int(v) for v in g["pl"]], "gq": int(g["gq"]), "qual": int(g["qual"]),
+             "depth": int(g["depth"]), "ref_count": int(g["ref_count"]), "alt_count": int(g["alt_count"]), "alt_fwd": int(g["alt_fwd"])} for g in recs]
+
+
+def PileupAddReport(params, reads, report, min_mapq=0, quals=None):
     """Add the placed reads of a MapReadsReport / MapReadPairsReport(tags=True) report whose mapq is at least min_mapq, in ONE call:
     strand-1 reads go in as their reverse complements (as the report's own summaries took them), the window is window_start and the
-    alpha bases the route consumes, and `use` leaves out the reads below min_mapq.  Returns how many reads it added."""
+    alpha bases the route consumes, and `use` leaves out the reads below min_mapq.  quals (a quality pile): one entry per read as
+    PileupAdd takes them, in the read's own orientation -- those of a strand-1 read are reversed here.  Returns how many reads it added."""
     idx = [r for r, d in enumerate(report) if d["best"] >= 0]
     if not idx:
         return 0
@@ -663,7 +721,9 @@ def PileupAddReport(params, reads, report, min_mapq=0):
     routes = [report[r]["route"] for r in idx]
     windows = [(report[r]["window_start"], sum(c[0] for c in route if c[1] != ColI)) for r, route in zip(idx, routes)]
     use = [1 if report[r]["mapq"] >= min_mapq else 0 for r in idx]
-    PileupAdd(params, oriented, windows, [report[r]["strand"] for r in idx], routes, use=use)
+    if quals is not None:
+        quals = [_phred(quals[r])[::-1] if report[r]["strand"] else _phred(quals[r]) for r in idx]
+    PileupAdd(params, oriented, windows, [report[r]["strand"] for r in idx], routes, use=use, quals=quals)
     return sum(use)
 
 

@@ -61,6 +61,7 @@
 #include "pileup.hip.h"
 #include "pile_alleles.hip.h"
 #include "pile_norm.hip.h"
+#include "pile_qual.hip.h"
 
 namespace {
 
@@ -163,6 +164,10 @@ struct Ctx {
     bool pl_track = false;
     int64_t pl_log_cap = 0, pl_events = 0; // events the planes hold; events logged so far (the cursor's value after the last add)
     int pl_key_bits = 1;                   // no event's key needs more bits than this (from the runs of the added pairs): the sort's range
+    // a quality pile's four qsum planes (gnx_pileup_track_qualities; pile_qual.hip.h), the qualities of an add, the records of a genotype query
+    DevBuf pl_qsum, pl_qin, pl_geno;
+    bool pl_qual = false;
+    int pl_minq = 0; // bases below it count nowhere
     PinBuf h_plans; // host-side plans of the general path
     PinBuf st_a[2], st_as[2], st_b[2], st_bs[2];
     // the resident reference, PACKED (gnx_host.hip.h: pack_reference): `ref` = 2 bits per base, ref_flag / ref_rank / ref_exc = the
@@ -2757,11 +2762,17 @@ void drop_pile_log(Ctx &c) {
     c.pl_log.release(); c.pl_cur.release(); c.pl_al.release(); c.pl_icalls.release(); c.pl_norm.release();
     for (DevBuf &b : c.pl_sort) b.release();
 }
+// ... and so do the quality planes of a quality pile
+void drop_pile_qual(Ctx &c) {
+    c.pl_qual = false; c.pl_minq = 0;
+    c.pl_qsum.release(); c.pl_qin.release(); c.pl_geno.release();
+}
 // ... and so does the pile (gnx_pileup_*), though not to a rebuilt index: its counts are positions of THAT reference
 void drop_pile(Ctx &c) {
     c.pl_len = -1; c.pl_start = 0; c.pl_reads = 0;
     c.pl_tab.release(); c.pl_in.release(); c.pl_cnt.release(); c.pl_off.release(); c.pl_calls.release();
     drop_pile_log(c);
+    drop_pile_qual(c);
 }
 std::atomic<int64_t> g_sv_lds{0}, g_sv_slab{0}; // reads voted with the table in LDS / in a slab (gnx_debug_counter(7 / 8))
 
@@ -3164,7 +3175,17 @@ int gnx_pileup_add_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t
     if (!p || n_pairs < 0 || !read_off || !ref_start || !ref_len) { set_err("bad argument%s", ""); return GNX_EINVAL; }
     if (p->mode != GNX_AFFINE_GAP_LOCAL) { set_err("gnx_pileup_add_by_offset takes GNX_AFFINE_GAP_LOCAL only (the window is the described side there), not mode %s%lld", "", (long long)p->mode); return GNX_EINVAL; }
     const std::vector<int64_t> rl = lengths_of(read_off, n_pairs);
-    return run_pile_add(p, n_pairs, ref_side(ref_start, ref_len), cat_side(read_cat, read_off, n_pairs, rl), strand, ops, ops_off, use);
+    return run_pile_add(p, n_pairs, ref_side(ref_start, ref_len), cat_side(read_cat, read_off, n_pairs, rl), strand, ops, ops_off, use, nullptr, false);
+}
+
+int gnx_pileup_add_by_offset_qual(const gnx_params *p, int64_t n_pairs, const uint8_t *read_cat, const int64_t *read_off, const int64_t *ref_start, const int64_t *ref_len,
+                                  const uint8_t *strand, const gnx_cigar *ops, const int64_t *ops_off, const uint8_t *use, const uint8_t *qual_cat) {
+    ApiCall api;
+    if (!p || n_pairs < 0 || !read_off || !ref_start || !ref_len) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (p->mode != GNX_AFFINE_GAP_LOCAL) { set_err("gnx_pileup_add_by_offset_qual takes GNX_AFFINE_GAP_LOCAL only (the window is the described side there), not mode %s%lld", "", (long long)p->mode); return GNX_EINVAL; }
+    if (n_pairs > 0 && !qual_cat) { set_err("gnx_pileup_add_by_offset_qual: null qual_cat%s", ""); return GNX_EINVAL; }
+    const std::vector<int64_t> rl = lengths_of(read_off, n_pairs);
+    return run_pile_add(p, n_pairs, ref_side(ref_start, ref_len), cat_side(read_cat, read_off, n_pairs, rl), strand, ops, ops_off, use, qual_cat, true);
 }
 
 int gnx_pileup_get(int64_t first, int64_t count, gnx_pile *out) {
@@ -3196,6 +3217,32 @@ int gnx_pileup_allele_info(int32_t *out_tracking, int64_t *out_events, int64_t *
 int gnx_pileup_alleles(gnx_pile_allele **out, int64_t *out_n) {
     ApiCall api;
     return run_pile_alleles(out, out_n, false);
+}
+
+int gnx_pileup_track_qualities(int32_t min_baseq) {
+    ApiCall api;
+    return run_pile_track_qual(min_baseq);
+}
+
+int gnx_pileup_qual_info(int32_t *out_tracking, int32_t *out_min_baseq, int64_t *out_device_bytes) {
+    ApiCall api;
+    Ctx &c = ctx_at(0);
+    CtxScope scope(c);
+    if (int rc = need_pile(c)) return rc;
+    if (out_tracking) *out_tracking = c.pl_qual ? 1 : 0;
+    if (out_min_baseq) *out_min_baseq = c.pl_qual ? c.pl_minq : 0;
+    if (out_device_bytes) *out_device_bytes = c.pl_qual ? c.pl_len * QUAL_PLANES * (int64_t)sizeof(int) : 0;
+    return GNX_OK;
+}
+
+int gnx_pileup_get_qual(int64_t first, int64_t count, int32_t *out) {
+    ApiCall api;
+    return run_pile_get_qual(first, count, out);
+}
+
+int gnx_pileup_genotypes(const gnx_geno_opts *o, gnx_pile_genotype **out, int64_t *out_n) {
+    ApiCall api;
+    return run_pile_genotypes(o, out, out_n);
 }
 
 int gnx_pileup_indel_calls(const gnx_pile_call_opts *o, gnx_pile_indel_call **out_calls, int64_t *out_n) {

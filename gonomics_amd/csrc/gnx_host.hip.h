@@ -1409,6 +1409,7 @@ int run_pile_open(int64_t region_start, int64_t region_len) {
     }
     c.pl_tab.release();
     drop_pile_log(c); // (a new pile does not track until it is told to)
+    drop_pile_qual(c);
     c.pl_tab.p = q; c.pl_tab.cap = bytes;
     c.pl_start = region_start; c.pl_len = region_len; c.pl_reads = 0;
     return GNX_OK;
@@ -1457,12 +1458,37 @@ int run_pile_track(int64_t reserve_events) {
     return GNX_OK;
 }
 
+// gnx_pileup_track_qualities: four zeroed qsum planes beside the 14, allocated before anything changes (a second call on an empty pile
+// keeps the planes, zeroes them again and takes the new min_baseq)
+int run_pile_track_qual(int32_t min_baseq) {
+    Ctx &c = ctx_at(0);
+    CtxScope scope(c);
+    int rc;
+    if ((rc = need_pile(c))) return rc;
+    if (min_baseq < 0 || min_baseq > QUAL_MAX) { set_err("min_baseq: 0 .. 93, not %s%lld", "", (long long)min_baseq); return GNX_EINVAL; }
+    if (c.pl_reads != 0) { set_err("gnx_pileup_track_qualities: reads have been added to this pile (%s%lld): their qualities are gone", "", (long long)c.pl_reads); return GNX_EINVAL; }
+    if ((rc = ensure_init())) return rc;
+    const size_t bytes = (size_t)c.pl_len * QUAL_PLANES * sizeof(int);
+    void *q = c.pl_qsum.p;
+    if (!q && hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); set_err("device allocation of %s%lld bytes failed", "", (long long)bytes); return GNX_ENOMEM; }
+    if (hipMemsetAsync(q, 0, bytes, c.own_stream) != hipSuccess || hipStreamSynchronize(c.own_stream) != hipSuccess) {
+        set_err_hip(hipGetLastError(), __FILE__, __LINE__);
+        if (!c.pl_qsum.p) (void)hipFree(q);
+        return GNX_EDEVICE;
+    }
+    c.pl_qsum.p = q; c.pl_qsum.cap = bytes;
+    c.pl_qual = true; c.pl_minq = min_baseq;
+    return GNX_OK;
+}
+
 // gnx_md_batch_by_offset's checks and uploads (sa = the windows, sb = the reads), the base check over every launch cut, ONE read-back of
 // its flag -- nothing may change the pile before every error is known --, then pile_add_kernel per sub-batch of GNX_HOST_SUB pairs
 // (GNX_PILE_SUB=<pairs> overrides the cut).  On a tracking pile the log is grown first -- beside the old one, before the first launch that could
 // change the pile -- and allele_log_kernel follows pile_add_kernel over the same buffers and the same cuts.
+// with_qual: gnx_pileup_add_by_offset_qual -- the entry and the pile must agree; the qualities go up beside the reads and qual_add_kernel
+// (pile_qual.hip.h) takes pile_add_kernel's place.  A plain pile runs nothing of that.
 int run_pile_add(const gnx_params *prm, int64_t n_pairs, const SeqSide &sa, const SeqSide &sb, const uint8_t *strand, const gnx_cigar *ops, const int64_t *ops_off,
-                 const uint8_t *use) {
+                 const uint8_t *use, const uint8_t *qual_cat, bool with_qual) {
     const auto t_entry = std::chrono::steady_clock::now();
     int rc;
     int64_t cells = 0;
@@ -1483,6 +1509,12 @@ int run_pile_add(const gnx_params *prm, int64_t n_pairs, const SeqSide &sa, cons
     Ctx &c = ctx_at(0);
     CtxScope scope(c);
     if ((rc = need_pile(c))) return rc;
+    if (with_qual != c.pl_qual) {
+        if (with_qual) set_err("gnx_pileup_add_by_offset_qual: the open pile does not track qualities: call gnx_pileup_track_qualities before the first add%s", "");
+        else set_err("gnx_pileup_add_by_offset: the open pile tracks qualities: its reads come through gnx_pileup_add_by_offset_qual%s", "");
+        return GNX_EINVAL;
+    }
+    if (c.pl_qual && n_use > QUAL_MAX_READS - c.pl_reads) { set_err("more than %s%lld reads in one quality pile (a read adds up to 93 to an int32 sum)", "", (long long)QUAL_MAX_READS); return GNX_EINVAL; }
     if (n_use > (int64_t)INT32_MAX - c.pl_reads) { set_err("more than 2^31 - 1 reads in one pile (its counters are int32)%s", ""); return GNX_EINVAL; }
     if (c.pl_track && gap_runs > (int64_t)INT32_MAX - c.pl_events) { set_err("more than 2^31 - 1 indel events in one pile%s", ""); return GNX_EINVAL; }
     if (n_pairs == 0) return GNX_OK;
@@ -1506,6 +1538,10 @@ int run_pile_add(const gnx_params *prm, int64_t n_pairs, const SeqSide &sa, cons
         if ((r = c.pl_in.ensure(2 * np))) return r;
         HIPCHK(hipMemcpyAsync(c.pl_in.p, strand, np, hipMemcpyHostToDevice, st));
         if (use) HIPCHK(hipMemcpyAsync((uint8_t *)c.pl_in.p + np, use, np, hipMemcpyHostToDevice, st));
+        if (c.pl_qual) { // the qualities beside the reads: the same layout, the same starts
+            if ((r = c.pl_qin.ensure((size_t)sb.buf_len + 16))) return r;
+            if (sb.buf_len > 0) HIPCHK(hipMemcpyAsync(c.pl_qin.p, qual_cat, (size_t)sb.buf_len, hipMemcpyHostToDevice, st));
+        }
         HIPCHK(hipEventRecord(c.ev[0], st));
         for (int64_t b = 0; b < n_pairs; b += sub) launch_sum_bases(sum_sub_args(a, sm, b, std::min(sub, n_pairs - b)), pk, sa, sb, b, std::min(sub, n_pairs - b), st);
         HIPCHK(hipGetLastError());
@@ -1528,7 +1564,13 @@ int run_pile_add(const gnx_params *prm, int64_t n_pairs, const SeqSide &sa, cons
             pa.read_start = (const int64_t *)sm[SM_BS].p + b; pa.ref_start = (const int64_t *)sm[SM_AS].p + b; pa.ops_off = (const int64_t *)sm[SM_OFF].p + b;
             pa.strand = (const uint8_t *)c.pl_in.p + b; pa.use = use ? (const uint8_t *)c.pl_in.p + np + b : nullptr;
             pa.n_pairs = cnt;
-            hipLaunchKernelGGL(pile_add_kernel, dim3((unsigned)std::min<int64_t>((cnt + 3) / 4, 1 << 20)), dim3(256), 0, st, pa);
+            if (c.pl_qual) {
+                QualAddArgs qa;
+                qa.p = pa; qa.quals = (const uint8_t *)c.pl_qin.p; qa.qsum = (int *)c.pl_qsum.p; qa.min_baseq = c.pl_minq;
+                hipLaunchKernelGGL(qual_add_kernel, dim3((unsigned)std::min<int64_t>((cnt + 3) / 4, 1 << 20)), dim3(256), 0, st, qa);
+            } else {
+                hipLaunchKernelGGL(pile_add_kernel, dim3((unsigned)std::min<int64_t>((cnt + 3) / 4, 1 << 20)), dim3(256), 0, st, pa);
+            }
             HIPCHK(hipGetLastError());
             t.n_launches++;
         }
@@ -1552,7 +1594,7 @@ int run_pile_add(const gnx_params *prm, int64_t n_pairs, const SeqSide &sa, cons
         }
         HIPCHK(hipStreamSynchronize(st));
         HIPCHK(hipEventElapsedTime(&ms, c.ev[2], c.ev[3]));
-        t.fill_ms += ms; t.dominant_ms = ms; // (dominant_ms: pile_add_kernel alone)
+        t.fill_ms += ms; t.dominant_ms = ms; // (dominant_ms: pile_add_kernel alone; on a quality pile: qual_add_kernel alone)
         if (c.pl_track) { HIPCHK(hipEventElapsedTime(&ms, c.ev[3], c.ev[4])); t.fill_ms += ms; }
         return GNX_OK;
     };
@@ -1596,6 +1638,29 @@ int run_pile_get(int64_t first, int64_t count, gnx_pile *out) {
                 row._reserved[s] = 0;
             }
         }
+    }
+    return GNX_OK;
+}
+
+// the qsum rows of a quality pile: [count][4], A C G T
+int run_pile_get_qual(int64_t first, int64_t count, int32_t *out) {
+    Ctx &c = ctx_at(0);
+    CtxScope scope(c);
+    int rc;
+    if ((rc = need_pile(c))) return rc;
+    if (!c.pl_qual) { set_err("the open pile does not track qualities: call gnx_pileup_track_qualities before the first add%s", ""); return GNX_EINVAL; }
+    if (first < 0 || count < 0 || count > c.pl_len - first || (count > 0 && !out)) { set_err("rows outside the pile's region%s", ""); return GNX_EINVAL; }
+    if (count == 0) return GNX_OK;
+    if ((rc = ensure_init())) return rc;
+    const int64_t slab = std::min<int64_t>(count, (int64_t)1 << 20);
+    std::vector<int> h((size_t)slab * QUAL_PLANES);
+    for (int64_t b = 0; b < count; b += slab) {
+        const int64_t n = std::min(slab, count - b);
+        for (int pl = 0; pl < QUAL_PLANES; pl++)
+            HIPCHK(hipMemcpyAsync(h.data() + (size_t)pl * (size_t)slab, (const int *)c.pl_qsum.p + (size_t)pl * (size_t)c.pl_len + (size_t)(first + b), (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c.own_stream));
+        HIPCHK(hipStreamSynchronize(c.own_stream));
+        for (int64_t k = 0; k < n; k++)
+            for (int x = 0; x < QUAL_PLANES; x++) out[(b + k) * QUAL_PLANES + x] = h[(size_t)x * (size_t)slab + (size_t)k];
     }
     return GNX_OK;
 }
@@ -1664,6 +1729,74 @@ int run_pile_calls(const gnx_pile_call_opts *o, gnx_pile_call **out_calls, int64
     };
     if ((rc = run())) { (void)hipStreamSynchronize(st); if (calls) g_pool.put(calls); return rc; }
     *out_calls = calls; *out_n = total;
+    t.dominant_ms = t.total_ms = t.fill_ms; t.dominant_launches = t.n_launches;
+    t.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count();
+    c.timing = t;
+    return GNX_OK;
+}
+
+// gnx_pileup_genotypes: run_pile_calls' pattern around geno_call_kernel -- the count pass, the scan of the tiles' counts, one read-back
+// that sizes the list, the write pass
+int run_pile_genotypes(const gnx_geno_opts *o, gnx_pile_genotype **out_recs, int64_t *out_n) {
+    const auto t_entry = std::chrono::steady_clock::now();
+    if (!o || !out_recs || !out_n) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (o->min_depth < 1 || o->min_qual < 0 || o->prior_het < 0 || o->prior_het > (1 << 20) || o->prior_hom < 0 || o->prior_hom > (1 << 20)) {
+        set_err("gnx_geno_opts: min_depth >= 1, min_qual >= 0, 0 <= prior_het, prior_hom <= 2^20%s", "");
+        return GNX_EINVAL;
+    }
+    Ctx &c = ctx_at(0);
+    CtxScope scope(c);
+    int rc;
+    if ((rc = need_pile(c))) return rc;
+    if (!c.pl_qual) { set_err("the open pile does not track qualities: call gnx_pileup_track_qualities before the first add%s", ""); return GNX_EINVAL; }
+    if ((rc = ensure_init())) return rc;
+    g_transport = 0; g_bcast_ms = 0;
+    hipStream_t st = c.own_stream;
+    gnx_timing t = {};
+    t.fast_path = 20; t.cells = c.pl_len; t.n_contexts = 1;
+    const int64_t n_tiles = (c.pl_len + PILE_TILE - 1) / PILE_TILE;
+    gnx_pile_genotype *recs = nullptr;
+    int64_t total = 0;
+    auto run = [&]() -> int {
+        int r;
+        if ((r = c.pl_cnt.ensure((size_t)(n_tiles + 1) * 8)) || (r = c.pl_off.ensure((size_t)(n_tiles + 1) * 8))) return r;
+        int64_t *d_carry = (int64_t *)c.pl_cnt.p + n_tiles;
+        HIPCHK(hipMemsetAsync(d_carry, 0, 8, st));
+        GenoCallArgs a;
+        memset(&a, 0, sizeof(a));
+        a.kp.b2 = (const unsigned *)c.ref.p; a.kp.bflag = (const unsigned long long *)c.ref_flag.p; a.kp.brank = (const unsigned *)c.ref_rank.p; a.kp.bexc = (const unsigned long long *)c.ref_exc.p;
+        a.pile = (const int *)c.pl_tab.p; a.qsum = (const int *)c.pl_qsum.p; a.region_start = c.pl_start; a.region_len = c.pl_len; a.n_tiles = n_tiles;
+        a.o.min_depth = o->min_depth; a.o.min_qual = o->min_qual; a.o.prior_het = o->prior_het; a.o.prior_hom = o->prior_hom;
+        a.cnt = (int64_t *)c.pl_cnt.p; a.off = (const int64_t *)c.pl_off.p;
+        const dim3 grid((unsigned)std::min<int64_t>((n_tiles + 3) / 4, 1 << 20));
+        HIPCHK(hipEventRecord(c.ev[0], st));
+        hipLaunchKernelGGL(geno_call_kernel<false>, grid, dim3(256), 0, st, a);
+        HIPCHK(hipGetLastError());
+        if ((r = launch_scan(a.cnt, (int)n_tiles, (int64_t *)c.pl_off.p, d_carry, st))) return r;
+        HIPCHK(hipEventRecord(c.ev[1], st));
+        HIPCHK(hipMemcpyAsync(&total, (const int64_t *)c.pl_off.p + n_tiles, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+        t.fill_ms = ms; t.n_launches = 1;
+        recs = (gnx_pile_genotype *)g_pool.get((size_t)std::max<int64_t>(total, 1) * sizeof(gnx_pile_genotype));
+        if (!recs) { set_err("pinned host allocation failed%s", ""); return GNX_ENOMEM; }
+        if (total > 0) {
+            if ((r = c.pl_geno.ensure((size_t)total * sizeof(gnx_pile_genotype)))) return r;
+            a.out = (gnx_pile_genotype *)c.pl_geno.p;
+            HIPCHK(hipEventRecord(c.ev[2], st));
+            hipLaunchKernelGGL(geno_call_kernel<true>, grid, dim3(256), 0, st, a);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(c.ev[3], st));
+            HIPCHK(hipMemcpyAsync(recs, c.pl_geno.p, (size_t)total * sizeof(gnx_pile_genotype), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            HIPCHK(hipEventElapsedTime(&ms, c.ev[2], c.ev[3]));
+            t.fill_ms += ms; t.n_launches = 2;
+        }
+        return GNX_OK;
+    };
+    if ((rc = run())) { (void)hipStreamSynchronize(st); if (recs) g_pool.put(recs); return rc; }
+    *out_recs = recs; *out_n = total;
     t.dominant_ms = t.total_ms = t.fill_ms; t.dominant_launches = t.n_launches;
     t.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count();
     c.timing = t;

@@ -689,6 +689,75 @@ int gnx_pileup_indel_calls(const gnx_pile_call_opts *o, gnx_pile_indel_call **ou
 int gnx_pileup_alleles_norm(gnx_pile_allele **out, int64_t *out_n);
 int gnx_pileup_indel_calls_norm(const gnx_pile_call_opts *o, gnx_pile_indel_call **out_calls, int64_t *out_n);
 
+/* ---- Base qualities in the pile, and diploid SNP genotypes from them ---------------------------------------------------- */
+/* gnx_pileup_track_qualities switches the open pile to quality tracking: four more planes of region_len int32 beside the 14, qsum[A C G T],
+ * the summed Phred qualities of the counted read bases, both strands together (16 bytes per position).  Allowed only while
+ * reads_added == 0: GNX_EINVAL otherwise, as without an open pile and for min_baseq outside 0 .. 93; an allocation that fails is GNX_ENOMEM
+ * with the pile as it was.  gnx_pileup_open replaces the pile, so quality tracking is off again; whatever drops the pile drops the planes.
+ * It is independent of gnx_pileup_track_alleles: both may be on, in either order, and the allele log does not depend on quality (an indel
+ * has none).  gnx_pileup_info keeps reporting the 14 planes; gnx_pileup_qual_info (any pointer may be NULL; GNX_EINVAL without an open
+ * pile) gives tracking 0 / 1, min_baseq and the planes' bytes, 16 * region_len (a plain pile: 0, 0, 0).  A pile that does not track
+ * qualities behaves exactly as before: the same launches, the same bytes.
+ *
+ * gnx_pileup_add_by_offset_qual: gnx_pileup_add_by_offset with one more array.  qual_cat is laid out exactly like read_cat and uses the
+ * same read_off; its bytes are raw Phred values (NOT ASCII + 33) in the orientation the read is passed in -- who reverse-complements a
+ * strand-1 read reverses its qualities.  A byte above 93 counts as 93 (clamped on the device; there is no error for it).  Everything
+ * gnx_pileup_add_by_offset defines holds, with one change.  An inside M column over read byte b with quality q = min(byte, 93):
+ *   q < min_baseq     counts nowhere (samtools' -Q)
+ *   otherwise         base[strand][b] += 1 as before and, for b < 4, qsum[b] += q
+ * del, ins and the allele log do not depend on quality.  Return codes are those of the plain add, all raised before the pile changes.
+ * The two entries do not mix: gnx_pileup_add_by_offset on a pile that tracks qualities is GNX_EINVAL, this entry on a pile that does not
+ * is GNX_EINVAL, and so is a null qual_cat with n_pairs > 0.  A read adds at most 93 to a qsum counter, so on a quality pile reads_added
+ * may not pass (2^31 - 1) / 93 = 23 091 222: a call that would carry it further is GNX_EINVAL before anything changes.
+ * E.g. window at 100 = ACGTACGTAC, read ACGAACTAC, 6M 1D 3M, qualities 30 30 10 30 40 30 5 30 30, min_baseq 20: the G at 102 and the T at
+ * 107 count nowhere; qsum[A] = 30 at 100, 103 and 108 and 40 at 104; qsum[C] = 30 at 101, 105 and 109; del at 106 as before.
+ * qual_add_kernel (pile_qual.hip.h) has pile_add_kernel's geometry, cuts and switches (GNX_PILE_SUB, GNX_PILE_FORM) and issues up to two
+ * unreturned atomic adds per M column.  gnx_get_timing: fast_path 14, cells as in the plain add, dominant_ms = qual_add_kernel alone.
+ *
+ * gnx_pileup_get_qual: the qsum rows region_start + first .. + count as [count][4] int32, A C G T; gnx_pileup_get's argument rules, and
+ * GNX_EINVAL without quality tracking.
+ *
+ * gnx_pileup_genotypes.  THIS LIBRARY's rule, as gnx_mapq_batch's and gnx_pileup_calls' are: a diploid SNP genotype per position from the
+ * counts and the quality sums, integer only, in centi-Phred (1/100 of a Phred unit).  For every position x of the region, ascending, with
+ * c the reference code at x (c == 4: silent), n[a] = base[0][a] + base[1][a] and Q[a] = qsum[a] for a in A C G T:
+ *   depth = n[0] + n[1] + n[2] + n[3]           (read Ns and deletions are outside the model)
+ *   E[a]  = 100 * Q[a] + 477 * n[a], in 64 bits  what it costs to explain all a bases as errors; 477 = round(1000 log10 3): a miscall
+ *                                               lands on one of three letters.  The -10 log10(1 - e) term of correct bases is dropped.
+ *   b     = the a != c with the largest E[a], ties to the smaller index: the alternative
+ *   L[0]  = E[b]                                ref / ref
+ *   L[1]  = 301 * (n[c] + n[b]) + prior_het     ref / alt; 301 = round(1000 log10 2)
+ *   L[2]  = E[c] + prior_hom                    alt / alt
+ * (bases of the other two letters cost every genotype the same and cancel).  g = argmin L, ties to the smaller index; pl[k] = L[k] - L[g];
+ * gq = the smallest pl[k] with k != g; qual = max(0, L[0] - min(L[1], L[2])); pl, gq and qual saturate at 2^31 - 1.  A record is emitted
+ * iff depth >= min_depth, g != 0 and qual >= min_qual: gt = g, ref = c, alt = b, ref_count = n[c], alt_count = n[b], alt_fwd = base[0][b].
+ * E.g. prior_het 3000, prior_hom 3300: 10 ref + 10 alt bases at q30: L = (34 770, 9 020, 38 070), g = 1, qual = gq = 25 750.  19 ref +
+ * 1 alt at q30: L = (3 477, 9 020, ..), g = 0, nothing is emitted.  17 ref + 3 alt at q30: L = (10 431, 9 020, 62 409), g = 1, qual 1 411.
+ * Twenty q2 alt bases (E = 13 540) against ten q40 ref bases (E = 44 770) are no alt / alt call -- L[2] = 48 070 against L[0] = 13 540 --
+ * where a count rule sees two thirds alt.
+ * Output ordered by position; *out is malloc'd (gnx_free), also for *out_n == 0.  GNX_EINVAL for min_depth < 1, min_qual < 0, a prior
+ * outside 0 .. 2^20, a null pointer, no open pile, a pile without quality tracking -- nothing is written then.  geno_call_kernel
+ * (pile_qual.hip.h) has pile_call_kernel's geometry and reads 12 planes; the rule itself is geno_rule() of gonomics_amd/csrc/geno_rule.h,
+ * which a CPU program can call as well.  gnx_get_timing: fast_path 20, cells = the region's positions.
+ *
+ * Not in scope: indel genotypes (an indel allele carries no quality; gnx_pileup_indel_calls remains the rule for them), mapping qualities
+ * inside the likelihood (filter with `use`), more than two alleles in a genotype. */
+typedef struct gnx_geno_opts { int32_t min_depth, min_qual, prior_het, prior_hom, _reserved[2]; } gnx_geno_opts;
+typedef struct gnx_pile_genotype {   /* 48 bytes */
+    int64_t pos;                     /* 0-based reference position */
+    int32_t pl[3];                   /* centi-Phred, 0 for the called genotype: ref/ref, ref/alt, alt/alt */
+    int32_t gq, qual;                /* centi-Phred */
+    int32_t depth, ref_count, alt_count, alt_fwd;
+    uint8_t gt, ref, alt, _pad;      /* gt 1 (ref / alt) or 2 (alt / alt); ref, alt: base codes; _pad 0 */
+} gnx_pile_genotype;
+int gnx_pileup_track_qualities(int32_t min_baseq);
+int gnx_pileup_qual_info(int32_t *out_tracking, int32_t *out_min_baseq, int64_t *out_device_bytes);
+int gnx_pileup_add_by_offset_qual(const gnx_params *p, int64_t n_pairs, const uint8_t *read_cat, const int64_t *read_off,
+                                  const int64_t *ref_start, const int64_t *ref_len, const uint8_t *strand,
+                                  const gnx_cigar *ops, const int64_t *ops_off, const uint8_t *use /* NULL: all */,
+                                  const uint8_t *qual_cat);
+int gnx_pileup_get_qual(int64_t first, int64_t count, int32_t *out /* [count][4]: A C G T */);
+int gnx_pileup_genotypes(const gnx_geno_opts *o, gnx_pile_genotype **out, int64_t *out_n);
+
 int gnx_get_timing(gnx_timing *out);
 /* Diagnostics (tests only; nothing in the reference corresponds to it): launch n_workgroups workgroups that each hold one CU's whole
  * LDS and spin for `milliseconds` on a stream of their own, and return at once -- the pipelined launches of the library must make

@@ -508,11 +508,22 @@ inline PileInfo PileupInfo() {
 }
 // reads (in the orientation they were aligned in) against windows (start, len) of the resident reference; strands[k] picks the counter;
 // use: empty = all, else use[k] == 0 leaves pair k out.  GNX_AFFINE_GAP_LOCAL.
-inline void PileupAdd(const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, const std::vector<std::vector<dna::Base>> &reads,
-                      const std::vector<std::pair<int64_t, int64_t>> &windows, const std::vector<uint8_t> &strands, const std::vector<std::vector<Cigar>> &routes,
-                      const std::vector<uint8_t> &use = {}) {
+namespace detail {
+// quals == nullptr: gnx_pileup_add_by_offset; else gnx_pileup_add_by_offset_qual with one raw Phred quality per read base
+inline void pile_add(const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, const std::vector<std::vector<dna::Base>> &reads,
+                     const std::vector<std::vector<uint8_t>> *quals, const std::vector<std::pair<int64_t, int64_t>> &windows, const std::vector<uint8_t> &strands,
+                     const std::vector<std::vector<Cigar>> &routes, const std::vector<uint8_t> &use) {
     const int64_t n = (int64_t)routes.size();
     if ((int64_t)reads.size() != n || (int64_t)windows.size() != n || (int64_t)strands.size() != n || (!use.empty() && (int64_t)use.size() != n)) detail::raise(GNX_EINVAL);
+    std::vector<uint8_t> qcat;
+    if (quals) {
+        if ((int64_t)quals->size() != n) detail::raise(GNX_EINVAL);
+        for (int64_t k = 0; k < n; k++) {
+            if ((*quals)[(size_t)k].size() != reads[(size_t)k].size()) detail::raise(GNX_EINVAL);
+            qcat.insert(qcat.end(), (*quals)[(size_t)k].begin(), (*quals)[(size_t)k].end());
+        }
+        qcat.push_back(0);
+    }
     const gnx_params p = detail::params(GNX_AFFINE_GAP_LOCAL, scores, gapOpen, gapExtend, 10000, 10000);
     std::vector<dna::Base> cat;
     std::vector<int64_t> off, ooff((size_t)n + 1, 0), ws, wl;
@@ -526,8 +537,16 @@ inline void PileupAdd(const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExt
         ooff[(size_t)k + 1] = (int64_t)ops.size();
     }
     ops.push_back(gnx_cigar{});
-    const int rc = gnx_pileup_add_by_offset(&p, n, cat.data(), off.data(), ws.data(), wl.data(), st.data(), ops.data(), ooff.data(), use.empty() ? nullptr : use.data());
+    const uint8_t *u = use.empty() ? nullptr : use.data();
+    const int rc = quals ? gnx_pileup_add_by_offset_qual(&p, n, cat.data(), off.data(), ws.data(), wl.data(), st.data(), ops.data(), ooff.data(), u, qcat.data())
+                         : gnx_pileup_add_by_offset(&p, n, cat.data(), off.data(), ws.data(), wl.data(), st.data(), ops.data(), ooff.data(), u);
     if (rc) detail::raise(rc);
+}
+} // namespace detail
+inline void PileupAdd(const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, const std::vector<std::vector<dna::Base>> &reads,
+                      const std::vector<std::pair<int64_t, int64_t>> &windows, const std::vector<uint8_t> &strands, const std::vector<std::vector<Cigar>> &routes,
+                      const std::vector<uint8_t> &use = {}) {
+    detail::pile_add(scores, gapOpen, gapExtend, reads, nullptr, windows, strands, routes, use);
 }
 inline std::vector<gnx_pile> PileupGet(int64_t first = 0, int64_t count = -1) {
     if (count < 0) count = PileupInfo().Len - first;
@@ -545,6 +564,35 @@ inline std::vector<gnx_pile_call> PileupCalls(const PileCallOpts &o = PileCallOp
     if (rc) detail::raise(rc);
     std::vector<gnx_pile_call> res(calls, calls + n);
     gnx_free(calls);
+    return res;
+}
+
+// base qualities in the pile and diploid SNP genotypes (gnx_pileup_track_qualities .. gnx_pileup_genotypes): the open pile, still empty,
+// sums the qualities of what it counts and leaves out bases below minBaseQ; its reads then come with quals[k][j] = the raw Phred quality of
+// reads[k][j] (the same orientation); the rule of the genotypes, in centi-Phred, is gnx_align.h's
+struct GenoOpts { int MinDepth = 1, MinQual = 0, PriorHet = 3000, PriorHom = 3300; };
+inline void PileupTrackQualities(int minBaseQ = 0) { const int rc = gnx_pileup_track_qualities(minBaseQ); if (rc) detail::raise(rc); }
+inline void PileupAdd(const ScoreMatrix &scores, int64_t gapOpen, int64_t gapExtend, const std::vector<std::vector<dna::Base>> &reads,
+                      const std::vector<std::vector<uint8_t>> &quals, const std::vector<std::pair<int64_t, int64_t>> &windows, const std::vector<uint8_t> &strands,
+                      const std::vector<std::vector<Cigar>> &routes, const std::vector<uint8_t> &use = {}) {
+    detail::pile_add(scores, gapOpen, gapExtend, reads, &quals, windows, strands, routes, use);
+}
+inline std::vector<std::array<int32_t, 4>> PileupGetQual(int64_t first = 0, int64_t count = -1) {
+    if (count < 0) count = PileupInfo().Len - first;
+    std::vector<std::array<int32_t, 4>> rows((size_t)(count > 0 ? count : 0) + 1);
+    const int rc = gnx_pileup_get_qual(first, count, rows[0].data());
+    if (rc) detail::raise(rc);
+    rows.pop_back();
+    return rows;
+}
+inline std::vector<gnx_pile_genotype> PileupGenotypes(const GenoOpts &o = GenoOpts()) {
+    const gnx_geno_opts go = {o.MinDepth, o.MinQual, o.PriorHet, o.PriorHom, {0, 0}};
+    gnx_pile_genotype *recs = nullptr;
+    int64_t n = 0;
+    const int rc = gnx_pileup_genotypes(&go, &recs, &n);
+    if (rc) detail::raise(rc);
+    std::vector<gnx_pile_genotype> res(recs, recs + n);
+    gnx_free(recs);
     return res;
 }
 
