@@ -11,7 +11,7 @@ namespace {
 // fp_cert_kernel proves that per pair -- one wave per pair -- and writes score, run count and staged runs exactly as fp_walk_kernel
 // would have; every other pair gets live[p] = 1 and goes through sweep and walk as before.
 //   1. the read's n - 15 16-mers (2 bits per base) go into an open-addressing table in LDS (512 slots, full key compare) with a
-//      16 384-bit prefilter beside it;
+//      16 384-bit prefilter beside it; a 16-mer that holds an N is left out (two bits cannot say N): an N row is in no exact run;
 //   2. the window is streamed 16 columns per lane and round (one 16-byte load, or one dword of the packed reference): a lane packs
 //      its columns into a 32-bit code word, takes the word of the lane before it (__shfl_up) and looks up the 16 16-mers that START in
 //      that earlier word's last 15 columns or at its own first one (v_alignbit): sixteen prefilter tests without a branch, then one
@@ -22,7 +22,8 @@ namespace {
 //      rows -- the read's base from LDS, the window's bases on diagonal c, on its first and on its last columns from memory -- and the
 //      lanes' sums are combined in int64 by wave sums and prefix scans (__shfl on the two halves): the deficit and the score by sums,
 //      "no prefix of f above 0" by a scan of f, d* by a scan of g and a wave-wide (least prefix, first row), the edge rule's four
-//      sums by masked sums once the deficit has fixed T1 and T2.  The call's matrix comes as a kernel argument (built once on the host).
+//      sums by masked sums once the deficit has fixed T1 and T2, the read's N rows (nu of the thresholds) by a sum.  The call's matrix
+//      comes as a kernel argument (built once on the host).  A certified pair whose read holds an N adds one to *n_cert (one atomic).
 // Windows of the packed reference that hold an exception (N, byte >= 5) are not certified; bytes >= 5 raise the sweep's error flag.
 // ------------------------------------------------------------------------------------------------------
 constexpr int CERT_K = 16;
@@ -56,12 +57,12 @@ __global__ __launch_bounds__(64) void fp_cert_kernel(const PairPlan *__restrict_
                                                      const uint8_t *__restrict__ b_buf, const int64_t *__restrict__ b_start,
                                                      KParams kp, TbParams tp, GnxCertMatrix mx, gnx_cigar *__restrict__ stage, int cap,
                                                      int64_t *__restrict__ score_out, int64_t *__restrict__ nops,
-                                                     int64_t *__restrict__ live, int *__restrict__ err) {
+                                                     int64_t *__restrict__ live, int64_t *__restrict__ n_cert, int *__restrict__ err) {
     __shared__ unsigned keys[CERT_SLOTS];
     __shared__ int qv[CERT_SLOTS];
     __shared__ unsigned filt[CERT_SLOTS];
     __shared__ uint8_t sa[CERT_NMAX];
-    __shared__ int64_t sw[32]; // w(x, y) at 8 x + y (the host built mx with mx.ok set, or did not launch)
+    __shared__ int64_t sw[40]; // w(x, y) at 8 x + y, x = 4: the N row (the host built mx with mx.ok set, or did not launch)
     const int p = (int)blockIdx.x;
     if (p >= n_pairs) return;
     const int lane = threadIdx.x;
@@ -79,14 +80,15 @@ __global__ __launch_bounds__(64) void fp_cert_kernel(const PairPlan *__restrict_
     // ---- 1. the read and its 16-mers ----
     for (int x = lane; x < CERT_SLOTS; x += 64) { qv[x] = -1; filt[x] = 0; }
     bool read_ok = true;
-    for (int i = lane; i < n; i += 64) { const uint8_t v = ap[i]; sa[i] = v; if (v >= 4) read_ok = false; }
-    if (__any(!read_ok)) { if (lane == 0) live[p] = 1; return; } // (N in the read: no certificate; a byte >= 5: the sweep flags it)
-    if (lane < 32) sw[lane] = gnx_cert_table8_entry(&mx, lane);
+    for (int i = lane; i < n; i += 64) { const uint8_t v = ap[i]; sa[i] = v; if (v >= 5) read_ok = false; }
+    if (__any(!read_ok)) { if (lane == 0) live[p] = 1; return; } // (a byte >= 5: the sweep flags it)
+    if (lane < 40) sw[lane] = gnx_cert_table8_entry(&mx, lane);
     __syncthreads(); // (sa and the empty table, before the 16-mers are read and inserted)
     for (int q = lane; q + CERT_K <= n; q += 64) {
-        unsigned code = 0;
+        unsigned code = 0, has_n = 0;
 #pragma unroll
-        for (int t = 0; t < CERT_K; t++) code |= (unsigned)sa[q + t] << (2 * t);
+        for (int t = 0; t < CERT_K; t++) { const unsigned v = sa[q + t]; has_n |= v; code |= (v & 3u) << (2 * t); }
+        if (has_n & 4u) continue; // (bytes are 0 .. 4 here)
         const unsigned h = cert_hash(code);
         unsigned slot = h >> 23;
         while (atomicCAS(&qv[slot], -1, q) != -1) slot = (slot + 1) & (CERT_SLOTS - 1); // (a key the read holds twice takes two slots)
@@ -165,9 +167,12 @@ __global__ __launch_bounds__(64) void fp_cert_kernel(const PairPlan *__restrict_
     for (int k = 0; k < CERT_CHUNK; k++) {
         const int i = i0 + k;
         loss[k] = 0;
-        if (k < chunk && i < n) loss[k] = gnx_cert_lane_row<8>(&ln, sw, i, sa[i], (unsigned)bp.at(c + i), (unsigned)bp.at(i), (unsigned)bp.at(m - n + i));
+        if (k < chunk && i < n) loss[k] = gnx_certn_lane_row<8>(&ln, sw, mx.R[4], 1, i, sa[i], (unsigned)bp.at(c + i), (unsigned)bp.at(i), (unsigned)bp.at(m - n + i));
     }
     if (__any(!ln.ok)) { if (lane == 0) live[p] = 1; return; } // a byte >= 5 under the read
+    int nu = 0; // the read's N rows: a wave sum of the chunks' counts, by ballots (scalar)
+#pragma unroll
+    for (int k = 0; k < CERT_CHUNK; k++) nu += __popcll(__ballot(ln.nn > k));
     const int64_t D = cert_wave_sum(ln.loss), mid_sum = cert_wave_sum(ln.mid);
     const int64_t Fi = cert_wave_scan(ln.f, lane), Gi = cert_wave_scan(ln.g, lane);
     const int f_pos = __any(ln.rows > 0 && Fi - ln.f + ln.f_top > 0); // some F_alpha > 0
@@ -175,7 +180,7 @@ __global__ __launch_bounds__(64) void fp_cert_kernel(const PairPlan *__restrict_
     int g_row = ln.rows > 0 ? ln.g_row : n;
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) gnx_cert_low_min(&g_low, &g_row, __shfl_xor(g_low, d, 64), __shfl_xor(g_row, d, 64));
-    const GnxCertBounds t = gnx_cert_bounds(mx.lambda, mx.o, n, CERT_K, D); // (uniform from here on)
+    const GnxCertBounds t = gnx_certn_bounds(mx.lambda, mx.o, n, CERT_K, D, nu); // (uniform from here on)
     int64_t h1 = 0, h2 = 0, t1 = 0, t2 = 0;
     if (t.edge) { // the loss of the first / last T1 and T2 rows
 #pragma unroll
@@ -203,6 +208,7 @@ __global__ __launch_bounds__(64) void fp_cert_kernel(const PairPlan *__restrict_
         nops[p] = cnt;
         score_out[p] = sc;
         live[p] = 0;
+        if (nu > 0) atomicAdd(reinterpret_cast<unsigned long long *>(n_cert), 1ull);
     }
 }
 

@@ -3,6 +3,9 @@
 // fp_cert_kernel (fp_cert.hip.h: 64 lanes with a chunk of rows each, combined by wave sums and scans) and by gnx_cert_decide, their serial
 // composition, which the host-only debug entry gnx_debug_gapless_certificate runs (the CPU tests; tests/cpp/cert_wave_test.cpp
 // evaluates the pieces the kernel's way on the host and requires gnx_cert_decide's results).  Exact integer arithmetic in int64.
+// The gnx_certn_* pieces admit reads that hold N: an N row is never exact and never imperfect, it loses R_N - w(N, y) >= 0 on a cell
+// and R_N >= 0 when skipped, and the nu N rows of the read enter the thresholds beside J.  There is one arithmetic: the gnx_cert_*
+// pieces of the N-free rule are the gnx_certn_* ones with N refused (allow_n = 0, nu = 0), signatures and results as before.
 #pragma once
 #include <stdint.h>
 
@@ -13,10 +16,11 @@
 #endif
 
 // Per call, from gnx_params: w(x, y) = s(x, y) - 2e (the rebasing of section 4), R_x = w(x, x), lambda = the least loss of a read row
-// that is mismatched or skipped.  ok = 0: the matrix (or gapOpen >= 0) admits no certificate.
+// that is mismatched or skipped and is not N; R[4] = R_N = max(0, max_y w(N, y)), so that an N row loses >= 0 wherever it lies.
+// ok = 0: the matrix (or gapOpen >= 0) admits no certificate.
 struct GnxCertMatrix {
     int64_t w[25];
-    int64_t R[4];
+    int64_t R[5];
     int64_t lambda;
     int64_t o, e;
     int32_t ok;
@@ -36,51 +40,66 @@ GNX_CERT_HD inline void gnx_cert_matrix_init(GnxCertMatrix *mx, const int64_t *s
         const int64_t loss = Rx - worst < Rx ? Rx - worst : Rx;
         if (loss < lam) lam = loss;
     }
+    int64_t rn = 0;
+    for (int y = 0; y < 5; y++) if (mx->w[20 + y] > rn) rn = mx->w[20 + y];
+    mx->R[4] = rn;
     mx->lambda = lam;
     mx->ok = (ok && lam > 0) ? 1 : 0;
 }
 
 // Entry k = 8 x + y of the table with row stride 8 (the kernel's copy in LDS: an index without a multiply); y = 5 .. 7 is padding.
+// k < 32: the rows of A C G T (the N-free rule's table); k < 40: with the N row.
 GNX_CERT_HD inline int64_t gnx_cert_table8_entry(const GnxCertMatrix *mx, int k) { return (k & 7) < 5 ? mx->w[(k >> 3) * 5 + (k & 7)] : 0; }
 
 // ---- a row ----
 // Read base a against the window's bases on diagonal c (bd), on its first n columns (bf) and on its last n columns (bl):
 // mid = w(a, bd), the row's loss on the diagonal R_a - mid, and what the row gains on the first / last columns instead.
-// w = the table with row stride STRIDE (5: GnxCertMatrix::w, 8: gnx_cert_table8_entry).  Returns 0 for an N in the read or a byte >= 5.
+// w = the table with row stride STRIDE (5: GnxCertMatrix::w, 8: gnx_cert_table8_entry).  Returns 0 for a byte >= 5, and for an N in the
+// read unless allow_n: then the row's R is rn = R_N (the table needs its row 4).
 struct GnxCertRow {
     int64_t mid, loss, f, g;
 };
 template <int STRIDE>
-GNX_CERT_HD inline int gnx_cert_row(const int64_t *w, unsigned a, unsigned bd, unsigned bf, unsigned bl, GnxCertRow *r) {
-    if (a >= 4 || bd >= 5 || bf >= 5 || bl >= 5) return 0;
+GNX_CERT_HD inline int gnx_certn_row(const int64_t *w, int64_t rn, int allow_n, unsigned a, unsigned bd, unsigned bf, unsigned bl, GnxCertRow *r) {
+    if (a >= (allow_n ? 5u : 4u) || bd >= 5 || bf >= 5 || bl >= 5) return 0;
     const int64_t *wa = w + a * STRIDE;
     const int64_t mid = wa[bd];
-    r->mid = mid; r->loss = wa[a] - mid; r->f = wa[bf] - mid; r->g = wa[bl] - mid;
+    r->mid = mid; r->loss = (a < 4 ? wa[a] : rn) - mid; r->f = wa[bf] - mid; r->g = wa[bl] - mid;
     return 1;
+}
+template <int STRIDE>
+GNX_CERT_HD inline int gnx_cert_row(const int64_t *w, unsigned a, unsigned bd, unsigned bf, unsigned bl, GnxCertRow *r) {
+    return gnx_certn_row<STRIDE>(w, 0, 0, a, bd, bf, bl, r);
 }
 
 // ---- a lane's chunk of consecutive rows, taken in ascending order ----
 // Sums of the four terms; f_top = the largest of the chunk's own prefix sums of f (item 6: the prefix before the chunk + f_top <= 0);
 // g_low = the least sum of g over the chunk's rows BEFORE a row and g_row = the first row that attains it (the suffix sum G from
-// that row on is the chunk's largest, and of equal ones the longest).
+// that row on is the chunk's largest, and of equal ones the longest).  nn = the chunk's N rows (their sum over the lanes is nu).
 struct GnxCertLane {
     int64_t loss, mid, f, g, f_top, g_low;
-    int32_t g_row, rows, ok;
+    int32_t g_row, rows, ok, nn;
 };
 GNX_CERT_HD inline void gnx_cert_lane_init(GnxCertLane *l) {
     l->loss = l->mid = l->f = l->g = l->f_top = l->g_low = 0;
-    l->g_row = 0; l->rows = 0; l->ok = 1;
+    l->g_row = 0; l->rows = 0; l->ok = 1; l->nn = 0;
 }
 // row i joins the chunk; returns its loss (the edge rule's sums)
 template <int STRIDE>
-GNX_CERT_HD inline int64_t gnx_cert_lane_row(GnxCertLane *l, const int64_t *w, int i, unsigned a, unsigned bd, unsigned bf, unsigned bl) {
+GNX_CERT_HD inline int64_t gnx_certn_lane_row(GnxCertLane *l, const int64_t *w, int64_t rn, int allow_n, int i, unsigned a, unsigned bd, unsigned bf,
+                                              unsigned bl) {
     GnxCertRow r;
-    if (!gnx_cert_row<STRIDE>(w, a, bd, bf, bl, &r)) { l->ok = 0; return 0; }
+    if (!gnx_certn_row<STRIDE>(w, rn, allow_n, a, bd, bf, bl, &r)) { l->ok = 0; return 0; }
+    l->nn += a == 4 ? 1 : 0;
     if (l->rows == 0 || l->g < l->g_low) { l->g_low = l->g; l->g_row = i; }
     l->loss += r.loss; l->mid += r.mid; l->f += r.f; l->g += r.g;
     if (l->rows == 0 || l->f > l->f_top) l->f_top = l->f;
     l->rows++;
     return r.loss;
+}
+template <int STRIDE>
+GNX_CERT_HD inline int64_t gnx_cert_lane_row(GnxCertLane *l, const int64_t *w, int i, unsigned a, unsigned bd, unsigned bf, unsigned bl) {
+    return gnx_certn_lane_row<STRIDE>(l, w, 0, 0, i, a, bd, bf, bl);
 }
 // (least prefix, first row) of two chunks
 GNX_CERT_HD inline void gnx_cert_low_min(int64_t *low, int *row, int64_t other_low, int other_row) {
@@ -98,19 +117,20 @@ GNX_CERT_HD inline int64_t gnx_cert_div(int64_t x, int64_t y) {
     if ((((uint64_t)x | (uint64_t)y) >> 32) == 0) return (int64_t)((uint32_t)x / (uint32_t)y);
     return x / y;
 }
-GNX_CERT_HD inline GnxCertBounds gnx_cert_bounds(int64_t lambda, int64_t o, int64_t n, int64_t K, int64_t D) {
+// nu = the read's N rows: rows that cut exact runs like imperfect ones but lose >= 0, not >= lambda, so they stand beside J everywhere
+GNX_CERT_HD inline GnxCertBounds gnx_certn_bounds(int64_t lambda, int64_t o, int64_t n, int64_t K, int64_t D, int64_t nu) {
     GnxCertBounds t = {0, 0, 0, 0};
     const int64_t O = -o;
     if (K > n) return t; // (every ceiling below is at most n)
     if (D == O || D >= 2 * O) return t; // (deficit == -o: a perfect path with three gap runs ties; refused, not argued)
-    const int64_t J = gnx_cert_div(D, lambda), J1 = gnx_cert_div(D + O, lambda);
+    const int64_t J = gnx_cert_div(D, lambda) + nu, J1 = gnx_cert_div(D + O, lambda) + nu; // (with nu: rows that are not in an exact run)
     if (n - J <= 0 || n - J1 <= 0) return t;
     // K <= ceil(x / y)  <=>  (K - 1) y < x
     if ((K - 1) * (3 + J) >= n - J || (K - 1) * (2 + J1) >= n - J1) return t;
     if (D > O) {
         // -o < deficit < -2o: paths with three gap runs.  Off diagonal c they need an exact run of K rows (the third inequality); with a
         // segment on diagonal c they have to save -o or more on the rows outside it: at most T1 rows at one end and T2 at the other.
-        const int64_t J3 = gnx_cert_div(D - O, lambda);
+        const int64_t J3 = gnx_cert_div(D - O, lambda) + nu;
         if ((K - 1) * (4 + J3) >= n - J3) return t;
         t.T1 = (1 + J3) * (K - 1) + J3; t.T2 = (2 + J3) * (K - 1) + J3;
         if (t.T1 + t.T2 >= n) return t; // (every row is an edge row: E = deficit)
@@ -118,6 +138,9 @@ GNX_CERT_HD inline GnxCertBounds gnx_cert_bounds(int64_t lambda, int64_t o, int6
     }
     t.ok = 1;
     return t;
+}
+GNX_CERT_HD inline GnxCertBounds gnx_cert_bounds(int64_t lambda, int64_t o, int64_t n, int64_t K, int64_t D) {
+    return gnx_certn_bounds(lambda, o, n, K, D, 0);
 }
 
 // ---- the tail: G_d = the sum of g over the last d rows, G_0 = 0; the LARGEST d that attains the maximum ----
@@ -139,49 +162,59 @@ GNX_CERT_HD inline int gnx_cert_finish(const GnxCertBounds *t, int64_t o, int64_
     return 1;
 }
 
-// Items 1 (shape and checkerboard), 2 (no N in the read), 4, 5 and 6 of the certificate for a pair whose exact K-mer matches all lie on
-// diagonal c (item 3, the caller's scan).  a[0..n) = the read; bd / bf / bl[0..n) = the window's bases under the read on diagonal c, on
-// the window's first n columns and on its last n columns (b + c, b, b + m - n).  Item 4 has two branches: deficit < -o, or
+// Items 1 (shape and checkerboard), 2 (no N in the read unless allow_n), 4, 5 and 6 of the certificate for a pair whose exact K-mer
+// matches all lie on diagonal c (item 3, the caller's scan).  a[0..n) = the read; bd / bf / bl[0..n) = the window's bases under the read on
+// diagonal c, on the window's first n columns and on its last n columns (b + c, b, b + m - n).  Item 4 has two branches: deficit < -o, or
 // -o < deficit < -2o with the edge rule (a second pass over at most T2 rows from each end, running sums only).  Returns 1 and the
 // closed form -- d* = the trailing read bases that sit on the window's last columns, the score -- or 0: the pair goes through the sweep.
-// The serial composition of the pieces above.
-GNX_CERT_HD inline int gnx_cert_decide(const GnxCertMatrix *mx, const uint8_t *a, int64_t n, const uint8_t *bd, const uint8_t *bf, const uint8_t *bl,
-                                       int64_t m, int64_t c, int64_t K, int64_t ci, int64_t cj, int64_t *d_star, int64_t *score) {
+// edge / nu (may be null): whether the edge rule decided, the read's N rows.  The serial composition of the pieces above.
+GNX_CERT_HD inline int gnx_certn_decide(const GnxCertMatrix *mx, const uint8_t *a, int64_t n, const uint8_t *bd, const uint8_t *bf, const uint8_t *bl,
+                                        int64_t m, int64_t c, int64_t K, int64_t ci, int64_t cj, int allow_n, int64_t *d_star, int64_t *score,
+                                        int64_t *edge, int64_t *nu_out) {
     if (!mx->ok || n < 1 || K < 1 || m < n + 2 || c <= 0 || c >= m - n) return 0;
     if (ci < n || cj < m) return 0; // a checkerboard edge inside the matrix: quirks Q1 / Q2 are the walk's business
+    const int64_t rn = mx->R[4];
     GnxCertRow r, r2;
-    int64_t deficit = 0, mid_sum = 0, F = 0;
+    int64_t deficit = 0, mid_sum = 0, F = 0, nu = 0;
     for (int64_t i = 0; i < n; i++) {
-        if (!gnx_cert_row<5>(mx->w, a[i], bd[i], bf[i], bl[i], &r)) return 0;
+        if (!gnx_certn_row<5>(mx->w, rn, allow_n, a[i], bd[i], bf[i], bl[i], &r)) return 0;
+        nu += a[i] == 4 ? 1 : 0;
         deficit += r.loss;
         mid_sum += r.mid;
         F += r.f; // the first i + 1 rows on the window's first columns instead (ties stay on the diagonal)
         if (F > 0) return 0;
     }
-    const GnxCertBounds t = gnx_cert_bounds(mx->lambda, mx->o, n, K, deficit);
+    const GnxCertBounds t = gnx_certn_bounds(mx->lambda, mx->o, n, K, deficit, nu);
     if (!t.ok) return 0;
     int64_t h1 = 0, h2 = 0, t1 = 0, t2 = 0; // the loss of the first / last T1 and T2 rows
     if (t.edge)
         for (int64_t i = 0; i < t.T2; i++) {
             const int64_t j = n - 1 - i;
-            gnx_cert_row<5>(mx->w, a[i], bd[i], bf[i], bl[i], &r);
-            gnx_cert_row<5>(mx->w, a[j], bd[j], bf[j], bl[j], &r2);
+            gnx_certn_row<5>(mx->w, rn, allow_n, a[i], bd[i], bf[i], bl[i], &r);
+            gnx_certn_row<5>(mx->w, rn, allow_n, a[j], bd[j], bf[j], bl[j], &r2);
             h2 += r.loss; t2 += r2.loss;
             if (i < t.T1) { h1 += r.loss; t1 += r2.loss; }
         }
     int64_t G = 0, best = 0, ds = 0;
     for (int64_t d = 1; d <= n; d++) { // the last d rows on the window's last columns instead: the LARGEST d that attains the maximum
         const int64_t i = n - d;
-        gnx_cert_row<5>(mx->w, a[i], bd[i], bf[i], bl[i], &r);
+        gnx_certn_row<5>(mx->w, rn, allow_n, a[i], bd[i], bf[i], bl[i], &r);
         G += r.g;
         if (G >= best) { best = G; ds = d; }
     }
+    if (edge) *edge = t.edge;
+    if (nu_out) *nu_out = nu;
     return gnx_cert_finish(&t, mx->o, mx->e, n, m, 0, mid_sum, h1, h2, t1, t2, best, ds, d_star, score);
+}
+GNX_CERT_HD inline int gnx_cert_decide(const GnxCertMatrix *mx, const uint8_t *a, int64_t n, const uint8_t *bd, const uint8_t *bf, const uint8_t *bl,
+                                       int64_t m, int64_t c, int64_t K, int64_t ci, int64_t cj, int64_t *d_star, int64_t *score) {
+    return gnx_certn_decide(mx, a, n, bd, bf, bl, m, c, K, ci, cj, 0, d_star, score, nullptr, nullptr);
 }
 
 // Item 3 the naive way (host: the debug entry).  Exact K-mer matches of read positions q .. q + K - 1 and window positions j .. j + K - 1 over
 // all q, j; window bytes that are not A C G T count as their two low bits, like in the kernel's rolling code (a false hit can only
-// refuse).  Returns 1 and the diagonal when the matches are non-empty and share one diagonal c = j - q.
+// refuse).  A K-mer of the read that holds an N matches nothing: the N-aware rule's table leaves such K-mers out, so this is its scan too.
+// Returns 1 and the diagonal when the matches are non-empty and share one diagonal c = j - q.
 inline int gnx_cert_scan_naive(const uint8_t *a, int64_t n, const uint8_t *b, int64_t m, int64_t K, int64_t *c_out) {
     int found = 0;
     int64_t c = 0;

@@ -771,7 +771,8 @@ int gnx_debug_occupy(int n_workgroups, int milliseconds); /* refused with GNX_EI
  * at most one gap open against the score, which is what the tests of megabase pairs (no oracle finishes them) check.
  * which = 5 / 6: rows per lane / snapshot spacing of the last 64-lane affine sweep (bench.py prices its design bytes with them).
  * which = 7 / 8: reads gnx_seed_candidates voted with the table in LDS / in a slab of device memory.
- * which = 9 / 10: pairs the fast path's gapless certificate certified (they skipped sweep and walk) / pairs offered to it.
+ * which = 9 / 10: pairs the fast path's gapless certificate certified by its N-free rule (they skipped sweep and walk) / pairs offered
+ * to it.  which = 11: pairs it certified whose read holds an N (counted in the kernel; 9 + 11 = all certified pairs).
  * reset != 0 zeroes the counter after reading (3 and 4 together). */
 int gnx_debug_counter(int which, int reset, int64_t *out);
 /* Diagnostics (tests only), host only -- no device is needed: the gapless certificate of the fast path for one
@@ -780,6 +781,10 @@ int gnx_debug_counter(int which, int reset, int64_t *out);
  * the window's last columns), the score.  A window that holds a byte >= 5 is never certified (the kernel raises the sweep's error for
  * it).  Refused with GNX_EINVAL unless the process runs with GNX_DEBUG_ENTRY=1. */
 int gnx_debug_gapless_certificate(const gnx_params *p, const uint8_t *a, int64_t n, const uint8_t *b, int64_t m, int64_t K, int64_t *out);
+/* The same with reads that hold N admitted, as the kernel decides ("Reads that hold N"): the 16-mers that hold an N
+ * are left out of the scan, an N row counts beside the imperfect rows in the thresholds.  out[0 .. 6) = certified (0 / 1), c, d*, the
+ * score, whether the edge rule decided (-o < deficit < -2o), the number of N in the read.  Same conditions as above. */
+int gnx_debug_gapless_certificate_n(const gnx_params *p, const uint8_t *a, int64_t n, const uint8_t *b, int64_t m, int64_t K, int64_t *out);
 
 /* ---- "next" row N1: chunk and multiple-alignment variants (what cmd/faChunkAlign and popgen/dunn.go run) ---- */
 /* align.AffineGapChunk (/root/reference/align/affineGap_highMem.go:227-268): the affine DP over chunks of chunk_size
