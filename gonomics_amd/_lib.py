@@ -18,7 +18,7 @@ EXPORTS = ["gnx_device_count", "gnx_init", "gnx_shutdown", "gnx_last_error", "gn
            "gnx_align_batch_windows", "gnx_align_pair", "gnx_align_batch_device", "gnx_get_timing",
            "gnx_affine_gap_chunk_batch", "gnx_multiple_affine_gap_batch", "gnx_gsw_extend_batch",
            "gnx_init_devices", "gnx_n_devices", "gnx_set_reference", "gnx_set_reference_synthetic", "gnx_align_batch_by_offset",
-           "gnx_seed_index_build", "gnx_seed_index_set", "gnx_seed_find_batch", "gnx_seed_index_set_gen", "gnx_seed_find_batch_gen", "gnx_gsw_graph_create", "gnx_gsw_graph_free", "gnx_gsw_map_reads", "gnx_debug_occupy", "gnx_debug_counter", "gnx_debug_gapless_certificate", "gnx_debug_gapless_certificate_n", "gnx_reference_info",
+           "gnx_seed_index_build", "gnx_seed_index_set", "gnx_seed_find_batch", "gnx_seed_index_set_gen", "gnx_seed_find_batch_gen", "gnx_gsw_graph_create", "gnx_gsw_graph_free", "gnx_gsw_map_reads", "gnx_debug_occupy", "gnx_debug_counter", "gnx_debug_fill_scratch", "gnx_debug_gapless_certificate", "gnx_debug_gapless_certificate_n", "gnx_reference_info",
            "gnx_score_batch", "gnx_score_batch_windows", "gnx_score_batch_by_offset", "gnx_score_batch_device",
            "gnx_locate_batch", "gnx_locate_batch_windows", "gnx_locate_batch_by_offset",
            "gnx_locate_span_batch", "gnx_locate_span_batch_windows", "gnx_locate_span_batch_by_offset",
@@ -291,6 +291,9 @@ def lib():
         if hasattr(L, "gnx_debug_gapless_certificate_n"):
             L.gnx_debug_gapless_certificate_n.argtypes = [ctypes.POINTER(GnxParams), c_p, i64, c_p, i64, i64, c_p]
             L.gnx_debug_gapless_certificate_n.restype = ctypes.c_int
+        if hasattr(L, "gnx_debug_fill_scratch"):
+            L.gnx_debug_fill_scratch.argtypes = [ctypes.c_uint32, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+            L.gnx_debug_fill_scratch.restype = ctypes.c_int
         _lib = L
     return _lib
 
@@ -299,6 +302,14 @@ def debug_counter(which=0, reset=True):
     v = ctypes.c_int64()
     check(lib().gnx_debug_counter(which, 1 if reset else 0, ctypes.byref(v)))
     return int(v.value)
+
+
+def debug_fill_scratch(pattern):
+    """Dirties the workspace of every initialised context with a 32-bit pattern (needs GNX_DEBUG_ENTRY=1): scratch buffers over their whole
+    capacity, state buffers behind what their owner wrote; the fast path's cached plans are dropped.  Returns (buffers, bytes) filled."""
+    nb, by = ctypes.c_int64(), ctypes.c_int64()
+    check(lib().gnx_debug_fill_scratch(ctypes.c_uint32(int(pattern) & 0xFFFFFFFF), ctypes.byref(nb), ctypes.byref(by)))
+    return int(nb.value), int(by.value)
 
 
 def debug_gapless_certificate(params, a, b, K=16):

@@ -152,6 +152,7 @@ struct Ctx {
     DevBuf sm[14]; // gnx_summarize_* and gnx_md_* (gnx_host.hip.h, SM_*): sequences, window tables, CIGAR runs and offsets, the score matrix, summaries, the extended CIGAR's counts / offsets / runs (gnx_md_*: the strings' byte counts / offsets / bytes)
     DevBuf bo[19]; // gnx_best_of_* / gnx_best_pair_* (gnx_host.hip.h, BO_*): reads + reverse complements, candidate tables and scores, per-read winners, the winners' tables
     int64_t sd_n = -1, sd_nodes_n = 0; int sd_seed_len = 0;
+    int64_t sd_total = 0, sd_words_n = 0; // bases of the resident index's nodes in sd_nodes / their packed words in sd_words
     // k-mer index of the resident reference (gnx_reference_index_build; context 0 only) and the scratch of gnx_seed_candidates (RS_*)
     DevBuf ri_keys, ri_pos, ri_dir, rs[15];
     int ri_dir_bits = 0; // ri_dir: 2^bits + 1 first entries by key prefix (ref_index_dir_kernel)
@@ -290,6 +291,7 @@ int64_t max_abs_pen(const gnx_params *p, bool affine) {
 
 std::atomic<int64_t> g_cert_ok{0}, g_cert_offered{0}; // pairs certified gapless by the N-free rule / offered to the certificate (gnx_debug_counter(9 / 10))
 std::atomic<int64_t> g_cert_n{0}; // pairs certified whose read holds an N (gnx_debug_counter(11))
+std::atomic<int64_t> g_fpc_hit{0}, g_fpc_miss{0}; // run_device_fp calls that found their plans on the device / that uploaded them (gnx_debug_counter(12 / 13))
 
 // Fast path for batches of short-alpha global affine alignments (see fp_walk_kernel).  Returns GNX_OK, an error,
 // or -1 when the batch should go through the general path after all (workspace too small / staging overflow).
@@ -420,6 +422,7 @@ int run_device_fp(const gnx_params *prm, const KParams &kp, const TbParams &tp, 
         c.fpc_alen.assign(h_alen, h_alen + n_pairs); c.fpc_blen.assign(h_blen, h_blen + n_pairs);
         c.fpc_roff = roff; c.fpc_coff = coff; c.fpc_cells = cells; c.fpc_mmax = m_maxb; c.fpc_ptr = c.plans.p; c.fpc_rboff = rboff; c.fpc_strips = S;
     }
+    (cached ? g_fpc_hit : g_fpc_miss)++; // (host side, one increment per call: what tests/test_scratch_state_gpu.py reads)
     const PairPlan *dpl = reinterpret_cast<const PairPlan *>(c.plans.p);
     int *d_hfwd = reinterpret_cast<int *>(c.hcol.p);
     int *d_whcol = d_hfwd + np;
@@ -1538,9 +1541,12 @@ int run_device_lat(const gnx_params *prm, const KParams &kp, const TbParams &tp,
     int *d_claims = reinterpret_cast<int *>(dm + o_claims);
     HIPCHK(hipMemsetAsync(c.misc.p, 0, 64, stream));
     HIPCHK(hipMemcpyAsync(dm, hm, o_claims, hipMemcpyHostToDevice, stream)); // (pinned: no synchronisation needed; every call ends with one)
-    HIPCHK(hipMemsetAsync(d_claims, 0, (size_t)n_blocks * 4 + 4, stream));
+    // (n_blocks == 0: every pair of a scored int64 batch has an empty side -- nothing to fill, so no claim words, no claim switch and no fill
+    // launch: a grid of 0 workgroups is a launch error.  The traceback's closed forms, the scores, the scan and the reversal run as ever.)
+    const bool any_fill = n_blocks > 0;
+    if (any_fill) HIPCHK(hipMemsetAsync(d_claims, 0, (size_t)n_blocks * 4 + 4, stream));
     if (roff > 0) HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c.rowbuf.p), LAT_SENT, (size_t)roff * 2, stream)); // "not written yet"
-    if ((rc = claim_test_switch(d_claims + n_blocks, stream))) return rc;
+    if (any_fill && (rc = claim_test_switch(d_claims + n_blocks, stream))) return rc;
     const PairPlan *dpl = reinterpret_cast<const PairPlan *>(c.plans.p);
     uint4 *dtrace = reinterpret_cast<uint4 *>(c.trace.p);
     int *dh = reinterpret_cast<int *>(c.hcol.p);
@@ -1558,7 +1564,7 @@ int run_device_lat(const gnx_params *prm, const KParams &kp, const TbParams &tp,
         const long long o4w = 4 * (long long)prm->gap_open, e4w = affine ? 4 * (long long)prm->gap_extend : 0;
         const long long d00w = local ? 0 : o4w, ecolw = local ? 0 : e4w;
 #define GNX_WIDE(A_, L_) hipLaunchKernelGGL((lat_wide_kernel<A_, L_>), gridF, blk, 0, stream, dpl, np, d_a, d_as, d_b, d_bs, kp, o4w, e4w, d00w, ecolw, dtrace, dh, d_s64, drw, ddc, d_err, d_smap, d_claims)
-        if (d_smat) hipLaunchKernelGGL((lat_wide_kernel<true, false, true>), gridF, blk, 0, stream, dpl, np, d_a, d_as, d_b, d_bs, kp, o4w, e4w, d00w, ecolw, dtrace, dh, d_s64, drw, ddc, d_err, d_smap, d_claims, d_smat);
+        if (d_smat) { if (any_fill) hipLaunchKernelGGL((lat_wide_kernel<true, false, true>), gridF, blk, 0, stream, dpl, np, d_a, d_as, d_b, d_bs, kp, o4w, e4w, d00w, ecolw, dtrace, dh, d_s64, drw, ddc, d_err, d_smap, d_claims, d_smat); } // (only this route takes empty sides along)
         else if (affine) { if (local) GNX_WIDE(true, true); else GNX_WIDE(true, false); }
         else GNX_WIDE(false, false);
 #undef GNX_WIDE
@@ -3685,7 +3691,7 @@ static int seed_index_set_locked(const uint64_t *keys, const uint64_t *locs, int
                                     (const int64_t *)c.sd_word_off.p, (int)n_nodes, n_words, (uint64_t *)c.sd_words.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st)); // word_off is a local
-    c.sd_n = n_index; c.sd_nodes_n = n_nodes; c.sd_seed_len = seed_len;
+    c.sd_n = n_index; c.sd_nodes_n = n_nodes; c.sd_seed_len = seed_len; c.sd_total = total; c.sd_words_n = n_words;
     return GNX_OK;
 }
 
@@ -4050,6 +4056,122 @@ int gnx_debug_occupy(int n_workgroups, int milliseconds) {
     return GNX_OK;
 }
 
+/* diagnostics (GNX_DEBUG_ENTRY=1): every buffer of every initialised context is filled with `pattern` where no later call is entitled to read
+ * it -- scratch over its whole capacity, state behind what its owner wrote -- so that a call which reads a word it did not write
+ * reads the pattern, not the zeroes of a fresh allocation or the plausible values of the call before (tests/test_scratch_state_gpu.py;
+ * DESIGN.md 4.29).  tests/test_scratch_state_cpu.py holds the two lists below against the members of Ctx. */
+int gnx_debug_fill_scratch(uint32_t pattern, int64_t *out_buffers, int64_t *out_bytes) {
+    ApiCall api;
+    if (!getenv("GNX_DEBUG_ENTRY")) { set_err("gnx_debug_fill_scratch is a test hook: set GNX_DEBUG_ENTRY=1%s", ""); return GNX_EINVAL; }
+    if (out_buffers) *out_buffers = 0;
+    if (out_bytes) *out_bytes = 0;
+    int n_ctx;
+    { std::lock_guard<std::mutex> lk(g_ctxs_mu); n_ctx = (int)g_ctxs.size(); }
+    int64_t n_filled = 0, bytes_filled = 0;
+    for (int k = 0; k < n_ctx; k++) {
+        Ctx &c = ctx_at(k);
+        CtxScope sc(c);
+        if (!c.inited) continue;
+        HIPCHK(hipSetDevice(c.device));
+        HIPCHK(hipDeviceSynchronize()); // (nothing of an earlier call is in flight under the API lock; a debug kernel on s_in may be)
+        hipStream_t st = c.own_stream;
+        struct Span { char *p; size_t n; }; // the dwords filled of one device buffer, for the check behind the synchronisation
+        std::vector<Span> spans;
+        // bytes [from, to) of a device buffer: the bytes up to a dword boundary, the dwords, the bytes left over (each byte is the one the
+        // dword pattern has at that address)
+        auto fill_dev = [&](DevBuf &b, size_t from, size_t to, bool same_buffer = false) -> int { // same_buffer: a further range of a buffer already counted
+            if (!b.p || from >= to) return GNX_OK;
+            char *base = reinterpret_cast<char *>(b.p);
+            size_t lo = from;
+            for (; lo < to && (lo & 3); lo++) HIPCHK(hipMemsetAsync(base + lo, (int)((pattern >> (8 * (lo & 3))) & 0xff), 1, st));
+            const size_t nd = (to - lo) / 4;
+            if (nd) { HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(base + lo), (int)pattern, nd, st)); spans.push_back({base + lo, nd}); }
+            for (size_t x = lo + nd * 4; x < to; x++) HIPCHK(hipMemsetAsync(base + x, (int)((pattern >> (8 * (x & 3))) & 0xff), 1, st));
+            if (!same_buffer) n_filled++;
+            bytes_filled += (int64_t)(to - from);
+            return GNX_OK;
+        };
+        auto fill_pin = [&](PinBuf &b) {
+            if (!b.p || !b.cap) return;
+            std::fill_n(reinterpret_cast<uint32_t *>(b.p), b.cap / 4, pattern); // (hipHostMalloc: aligned)
+            unsigned char *q = reinterpret_cast<unsigned char *>(b.p);
+            for (size_t x = b.cap & ~(size_t)3; x < b.cap; x++) q[x] = (unsigned char)((pattern >> (8 * (x & 3))) & 0xff);
+            n_filled++; bytes_filled += (int64_t)b.cap;
+        };
+        int rc;
+        // ---- scratch: a call writes what it reads of these ----
+        // [scratch-list-begin]
+        DevBuf *scratch[] = {&c.trace, &c.hcol, &c.rowbuf, &c.dcol, &c.plans, &c.nops, &c.misc, &c.strip_map, &c.tb_scr, &c.tb_scr_off, &c.scan_tmp, &c.fp_tail, &c.fp_rowi, &c.fp_ckpt,
+                             &c.fp_states, &c.fp_stage, &c.fp_thcol, &c.fp_ttrace, &c.fp_redo, &c.fp_strag, &c.mx_idx, &c.mx_tab, &c.mx_score, &c.mx_off, &c.mx_ops, &c.fp_prog,
+                             &c.fp_cflag, &c.fp_live, &c.fp_gplans, &c.in_a, &c.in_b, &c.in_as, &c.in_al, &c.in_bs, &c.in_bl, &c.out_score, &c.out_off, &c.out_ops, &c.out_end,
+                             &c.sc_pairs, &c.sc_mat, &c.sc_err, &c.res_score, &c.res_off, &c.res_ops, &c.gat_score, &c.gat_off, &c.gat_ops, &c.sp_hand, &c.res_start, &c.gat_start,
+                             &c.ss_len, &c.res_end, &c.gat_end, &c.ss_plans, &c.ss_rowbuf, &c.ss_prog, &c.ss_err, &c.ss_off, &c.pl_in, &c.pl_cnt, &c.pl_off, &c.pl_calls,
+                             &c.pl_al, &c.pl_icalls, &c.pl_norm, &c.pl_qin, &c.pl_geno, &c.unpk_b, &c.unpk_off, &c.cl_bases, &c.sc_prof_a, &c.sc_prof_b, &c.mega_rows,
+                             &c.mega_state, &c.farm, &c.mega_arena};
+        for (DevBuf *b : scratch) if ((rc = fill_dev(*b, 0, b->cap))) return rc;
+        for (DevBuf &b : c.fp_wplans) if ((rc = fill_dev(b, 0, b.cap))) return rc;
+        for (DevBuf &b : c.fp_active) if ((rc = fill_dev(b, 0, b.cap))) return rc;
+        for (DevBuf &b : c.pin_a) if ((rc = fill_dev(b, 0, b.cap))) return rc;
+        for (DevBuf &b : c.pin_as) if ((rc = fill_dev(b, 0, b.cap))) return rc;
+        for (DevBuf &b : c.pin_b) if ((rc = fill_dev(b, 0, b.cap))) return rc;
+        for (DevBuf &b : c.pin_bs) if ((rc = fill_dev(b, 0, b.cap))) return rc;
+        for (DevBuf &b : c.sd_tmp) if ((rc = fill_dev(b, 0, b.cap))) return rc;
+        for (DevBuf &b : c.sm) if ((rc = fill_dev(b, 0, b.cap))) return rc;
+        for (DevBuf &b : c.bo) if ((rc = fill_dev(b, 0, b.cap))) return rc;
+        for (DevBuf &b : c.rs) if ((rc = fill_dev(b, 0, b.cap))) return rc;
+        for (DevBuf &b : c.pl_sort) if ((rc = fill_dev(b, 0, b.cap))) return rc;
+        fill_pin(c.h_plans);
+        for (PinBuf &b : c.st_a) fill_pin(b);
+        for (PinBuf &b : c.st_as) fill_pin(b);
+        for (PinBuf &b : c.st_b) fill_pin(b);
+        for (PinBuf &b : c.st_bs) fill_pin(b);
+        // [scratch-list-end]
+        c.fpc_ptr = nullptr; // the cached plans of the fast path are gone
+        // ---- state: the slack behind what the owner wrote (the sizes are the writers': set_reference_packed, gnx_reference_index_build,
+        // seed_index_set_locked, run_pile_open / run_pile_track / run_pile_track_qual / run_pile_add) ----
+        const bool has_ref = c.ref_len >= 0, has_ri = has_ref && c.ri_n >= 0, has_sd = c.sd_n >= 0, has_pile = c.pl_len >= 0;
+        struct State { DevBuf *b; size_t used; };
+        // [state-list-begin]
+        const State state[] = {
+            {&c.ref, has_ref ? ref_words(c.ref_len) * 4 : 0},
+            {&c.ref_flag, has_ref ? ref_flagwords(c.ref_len) * 8 : 0},
+            {&c.ref_rank, has_ref ? ref_flagwords(c.ref_len) * 4 : 0},
+            {&c.ref_exc, has_ref ? (size_t)c.ref_nexc * 16 : 0},
+            {&c.ri_keys, has_ri ? (size_t)c.ri_n * 8 : 0},
+            {&c.ri_pos, has_ri ? (size_t)c.ri_n * 8 : 0},
+            {&c.ri_dir, has_ri ? (((size_t)1 << c.ri_dir_bits) + 1) * 8 : 0},
+            {&c.sd_keys, has_sd ? (size_t)c.sd_n * 8 : 0},
+            {&c.sd_locs, has_sd ? (size_t)c.sd_n * 8 : 0},
+            {&c.sd_nodes, has_sd ? (size_t)c.sd_total : 0},
+            {&c.sd_node_off, has_sd ? (size_t)(c.sd_nodes_n + 1) * 8 : 0},
+            {&c.sd_word_off, has_sd ? (size_t)(c.sd_nodes_n + 1) * 8 : 0},
+            {&c.sd_words, has_sd ? (size_t)c.sd_words_n * 8 : 0},
+            {&c.pl_tab, has_pile ? (size_t)c.pl_len * PILE_PLANES * sizeof(int) : 0},
+            {&c.pl_qsum, has_pile && c.pl_qual ? (size_t)c.pl_len * QUAL_PLANES * sizeof(int) : 0},
+            {&c.pl_cur, has_pile && c.pl_track ? (size_t)8 : 0},
+        };
+        for (const State &s : state) if ((rc = fill_dev(*s.b, std::min(s.used, s.b->cap), s.b->cap))) return rc;
+        // pl_log: two planes of pl_log_cap words; each holds pl_events events
+        if (has_pile && c.pl_track) {
+            const size_t plane = (size_t)c.pl_log_cap * 8, used = (size_t)c.pl_events * 8;
+            if ((rc = fill_dev(c.pl_log, used, plane)) || (rc = fill_dev(c.pl_log, plane + used, 2 * plane, true))) return rc;
+        }
+        else if ((rc = fill_dev(c.pl_log, 0, c.pl_log.cap))) return rc;
+        // [state-list-end]
+        HIPCHK(hipStreamSynchronize(st));
+        // a fill that did not land must not pass for a clean run: the first and the last dword of every fill
+        for (const Span &sp : spans) {
+            uint32_t got[2] = {~pattern, ~pattern};
+            HIPCHK(hipMemcpy(&got[0], sp.p, 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(&got[1], sp.p + (sp.n - 1) * 4, 4, hipMemcpyDeviceToHost));
+            if (got[0] != pattern || got[1] != pattern) { set_err("gnx_debug_fill_scratch: a fill of %s%lld dwords did not land", "", (long long)sp.n); return GNX_EDEVICE; }
+        }
+    }
+    if (out_buffers) *out_buffers = n_filled;
+    if (out_bytes) *out_bytes = bytes_filled;
+    return GNX_OK;
+}
+
 /* diagnostics, host only (no device is touched): the fast path's gapless certificate for ONE pair, with a naive K-mer
  * scan and the decision arithmetic the kernel runs (fp_cert_decide.h).  K is a parameter so that small pairs can exercise the
  * "K is long enough" rule; the kernel uses 16.  out[0..4) = certified (0 / 1), diagonal c, d*, score. */
@@ -4098,7 +4220,13 @@ int gnx_debug_gapless_certificate_n(const gnx_params *p, const uint8_t *a, int64
 int gnx_debug_counter(int which, int reset, int64_t *out) {
     ApiCall api;
     CtxScope sc(ctx_at(0));
-    if (which < 0 || which > 11 || !out) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (which < 0 || which > 13 || !out) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (which >= 12) { // the fast path's plan cache: calls that took the cached branch / that built and uploaded their plans
+        std::atomic<int64_t> &v = which == 12 ? g_fpc_hit : g_fpc_miss;
+        *out = v.load();
+        if (reset) v = 0;
+        return GNX_OK;
+    }
     if (which >= 9) { // the fast path's gapless certificate: pairs certified by the N-free rule / pairs offered to it / certified reads that hold an N
         std::atomic<int64_t> &v = which == 9 ? g_cert_ok : (which == 10 ? g_cert_offered : g_cert_n);
         *out = v.load();

@@ -773,8 +773,17 @@ int gnx_debug_occupy(int n_workgroups, int milliseconds); /* refused with GNX_EI
  * which = 7 / 8: reads gnx_seed_candidates voted with the table in LDS / in a slab of device memory.
  * which = 9 / 10: pairs the fast path's gapless certificate certified by its N-free rule (they skipped sweep and walk) / pairs offered
  * to it.  which = 11: pairs it certified whose read holds an N (counted in the kernel; 9 + 11 = all certified pairs).
+ * which = 12 / 13: fast-path calls that found the plans of the previous call on the device (equal lengths) / that built and uploaded
+ * their plans.
  * reset != 0 zeroes the counter after reading (3 and 4 together). */
 int gnx_debug_counter(int which, int reset, int64_t *out);
+/* Diagnostics: dirties the workspace.  Every device and pinned buffer of every initialised context that is SCRATCH -- written by a call
+ * before that call reads it -- is filled over its whole capacity with the 32-bit `pattern`; of the buffers that hold STATE a later call may
+ * read (the resident reference, the reference index, the seed index, the open pile and its logs) only the slack behind what their owner
+ * wrote.  The fast path's cached plans are dropped.  A call after it must compute what it computes on a fresh workspace
+ * (tests/test_scratch_state_gpu.py).  out_buffers / out_bytes (may be NULL): buffers and bytes filled.  GNX_EDEVICE if
+ * a fill did not land.  Refused with GNX_EINVAL unless the process runs with GNX_DEBUG_ENTRY=1. */
+int gnx_debug_fill_scratch(uint32_t pattern, int64_t *out_buffers, int64_t *out_bytes);
 /* Diagnostics (tests only), host only -- no device is needed: the gapless certificate of the fast path for one
  * global AffineGap pair, a = the read (n bases), b = its window (m bases): a naive scan for exact K-mer matches, then the decision
  * arithmetic the kernel runs (K = 16 there).  out[0 .. 4) = certified (0 / 1), the diagonal c, d* (trailing read bases that sit on

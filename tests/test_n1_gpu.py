@@ -157,6 +157,15 @@ def _n1_got(sc, ops, off, k):
     return (int(sc[k]), [(int(r), int(o)) for r, o in zip(ops["run_length"][off[k]:off[k + 1]], ops["op"][off[k]:off[k + 1]])])
 
 
+def _all_empty_batches(chunk, cells):
+    """batches in which EVERY pair has an empty side (the scored int64 route then has no strip to fill: the traceback's closed forms alone):
+    one pair with an empty alpha, the same pair with the sides swapped, three pairs with one empty side each"""
+    rng = np.random.default_rng(4242)
+    empty = np.zeros(0, np.uint8)
+    long_one, other = rng.integers(0, 5, size=cells * chunk).astype(np.uint8), rng.integers(0, 5, size=(cells // 2 + 1) * chunk).astype(np.uint8)
+    return [([empty], [long_one]), ([long_one], [empty]), ([empty, long_one, empty], [long_one, empty, other])]
+
+
 def test_n1_beyond_int32(gpu_lib, geometry):
     """round 6: the chunk / multiple-alignment variants have no GNX_ERANGE any more -- the reference is int64 there too
     (align/affineGap_highMem.go:227-353).  A call with a pair whose keys 4 * score leave the static int32 range runs on the int64 kernel with explicit
@@ -204,6 +213,13 @@ def test_n1_beyond_int32(gpu_lib, geometry):
         sc, ops, off = gpu_lib.multiple_affine_gap_batch(p, ch, groups, pairs)
         for k, (x, y) in enumerate(pairs):
             assert _n1_got(sc, ops, off, k) == oracle.multiple_affine_gap(big, -8000000, -600000, ch, groups[x], groups[y]), (ch, x, y)
+    # every pair with an empty side, the other one long enough for the int64 route ((nc + mc + 2) * max|penalty| >= 2^27 from 30 cells on)
+    p = gpu_lib.make_params(gpu_lib.GNX_AFFINE_GAP_HIGHMEM, x1000, -2400000, -600000)
+    for alphas, betas in _all_empty_batches(chunk, 100):
+        sc, ops, off = gpu_lib.affine_gap_chunk_batch(p, chunk, alphas, betas)
+        assert gpu_lib.get_timing()["fast_path"] == 4
+        for k, (a, b) in enumerate(zip(alphas, betas)):
+            assert _n1_got(sc, ops, off, k) == oracle.affine_gap_chunk(x1000, -2400000, -600000, chunk, a, b), ("all empty", len(alphas), k)
 
 
 def test_n1_int64_kernel_forced(gpu_lib, geometry, monkeypatch):
@@ -224,3 +240,8 @@ def test_n1_int64_kernel_forced(gpu_lib, geometry, monkeypatch):
         sc, ops, off = gpu_lib.affine_gap_chunk_batch(p, chunk, alphas, betas)
         for k, (a, b) in enumerate(zip(alphas, betas)):
             assert _n1_got(sc, ops, off, k) == oracle.affine_gap_chunk(MX["HumanChimpTwo"], -600, -150, chunk, a, b), (chunk, k)
+        for alphas, betas in _all_empty_batches(chunk, 100):  # every pair with an empty side: no fill launch at all
+            sc, ops, off = gpu_lib.affine_gap_chunk_batch(p, chunk, alphas, betas)
+            assert gpu_lib.get_timing()["fast_path"] == 4
+            for k, (a, b) in enumerate(zip(alphas, betas)):
+                assert _n1_got(sc, ops, off, k) == oracle.affine_gap_chunk(MX["HumanChimpTwo"], -600, -150, chunk, a, b), ("all empty", chunk, len(alphas), k)
