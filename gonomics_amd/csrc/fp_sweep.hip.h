@@ -70,8 +70,8 @@ constexpr int FP8_LW = 10;                 // dwords per lane per base (20 int16
 // 10*lp + 2k, +1 of the plane of ITS base.  Conflict-free whatever the bases are when a plane stride is == 0 (mod 32) and the second
 // pair of the duo sits 16 banks from the first (10*lp mod 32 = {0,10,20,30,8,18,28,6}: with their +1 neighbours 16 distinct banks, the
 // other 16 are theirs + 16).  Compact form (round 3): the two pairs of a duo interleave plane by plane -- pair 0 in dwords [0, 80) of
-// a 160-dword plane, pair 1 in [80, 160), 80 == 16 (mod 32) -- so no padding is left: 3200 dwords of profile, 32 of score table, 128
-// of base rings = 13 440 B per wave, 11 waves per CU (LDS is handed out in granules of 1280 B on gfx950) where the padded form
+// a 160-dword plane, pair 1 in [80, 160), 80 == 16 (mod 32) -- so no padding is left: 3200 dwords of profile, 32 of score table, 144
+// of base rings (skewed, below) = 13 504 B per wave, 11 waves per CU (LDS is handed out in granules of 1280 B on gfx950) where the padded form
 // (96-dword planes, pair stride 496: 16 000 B) allowed 9.
 #ifndef GNX_FP_LDS_COMPACT
 #define GNX_FP_LDS_COMPACT 1
@@ -104,7 +104,7 @@ __device__ __forceinline__ int dpp_next8(int src) { // every lane of the two ban
 
 // Occupancy: 168 VGPRs = three waves per SIMD by registers (round 1 needed ~200 and lost 20 % when capped; since the base ring and the
 // look-ahead of round 3 the kernel fits on its own, and the transposed form is held to 168 by amdgpu_waves_per_eu at the price of
-// three spilled values outside the steady loop: -2.4 %), 13 440 B of LDS = 11 waves per CU (see FP8_LDS above).
+// three spilled values outside the steady loop: -2.4 %), 13 504 B of LDS = 11 waves per CU (see FP8_LDS above).
 // ROLE: reads of 161 .. 320 bases are swept as TWO row blocks of 8 x 20 slots, one launch each (pl.strips == 2):
 //   1 = the TOP block: rows 1 .. n - 160, right-aligned like a short read in 8 x RR slots (RR = 8, 12, 16 or 20: the host picks the
 //       smallest that holds the longest read of the batch); instead of planes / h(n,m) it hands its bottom row down:
@@ -127,7 +127,7 @@ __device__ __forceinline__ int dpp_next8(int src) { // every lane of the two ban
 // (prog_out / prog_in: the last step whose hand-over stores are out, INT_MAX at the end; rows and progress word are agent-scope
 // atomics like the general path's strips, see rb_store).
 template <int RR, bool XP, int ROLE, bool PK>
-__device__ __forceinline__ void fp_sweep_body(int *__restrict__ lds, const int wblk, const PairPlan *__restrict__ plans, int n_pairs,
+__device__ __forceinline__ void fp_sweep_body(int *__restrict__ lds, int *tab, const int wblk, const int lane, const PairPlan *__restrict__ plans, int n_pairs,
                                               const uint8_t *__restrict__ a_buf, const int64_t *__restrict__ a_start,
                                               const uint8_t *__restrict__ b_buf, const int64_t *__restrict__ b_start,
                                               const KParams &kp, int *__restrict__ hcol, int2 *__restrict__ ckpt,
@@ -139,23 +139,34 @@ __device__ __forceinline__ void fp_sweep_body(int *__restrict__ lds, const int w
     constexpr bool HANDS = (ROLE == 1 || ROLE == 3);  // hands its bottom row down through the row buffer
     constexpr bool TAKES = (ROLE >= 2);               // takes the row above it from the row buffer
     constexpr int BOT = G8 * 2 * FP8_LW; // rows of the bottom block (the top block has the rest, in 8 x RR slots: RR as small as they fit)
-    const int lane = threadIdx.x;
     const int g = lane >> 3;
     const int lp = (lane & 8) ? 15 - (lane & 15) : (lane & 7); // position of the lane inside its pair
     const int E4 = kp.e4;
     constexpr int TI = XP ? 1 : 2, TD = XP ? 2 : 1; // tags of the horizontal / vertical gap state (tie order, see above)
     constexpr bool EV = (GNX_FP_EVENTS != 0) && ROLE == 0 && !XP; // plane rows untagged + last-event tracking until the tail (see GNX_FP_EVENTS)
-    if (lane < 25) lds[lane] = kp.sc4[lane] - 2 * E4;
-    else if (lane < 32) lds[lane] = XP ? -E4 : -32768; // padding rows: the diagonal candidate never wins (XP: fake rows that repeat row 0)
+    if (lane < 25) tab[lane] = kp.sc4[lane] - 2 * E4;
+    else if (lane < 32) tab[lane] = XP ? -E4 : -32768; // padding rows: the diagonal candidate never wins (XP: fake rows that repeat row 0)
     int *prof = GNX_FP_LDS_COMPACT ? &lds[32 + (g >> 1) * (5 * FP8_BST) + (g & 1) * (G8 * FP8_LW)] : &lds[32 + g * FP8_PST];
     const char *prof_lane = reinterpret_cast<const char *>(prof + lp * FP8_LW);
 
     const int pbase = wblk * 8;
+    // m_min bounds the steady part of the sweep (every lane inside its matrix) and starts the tagged tail.  One block (ROLE 0): the least
+    // window of the wave's PAIRS -- the slots behind the batch's last pair do not count.  Counted as windows of 0 columns (as the row blocks
+    // of longer reads still count them) they put the last wave of every batch that is no multiple of 8 into the checked, tagged half blocks
+    // from its first column to its last, three times the steady cost per step, and the whole launch waits for that one wave: 35 820
+    // pairs took 12.1 ms where 40 960 took 11.6 (profiles/sweep_rounds.json).  Lanes of an empty slot run the steady steps on padding
+    // (n = 0: every row reproduces row 0) and store nothing: every store below asks for `valid`.  A wave without pairs: m_min = 0.
+    // A launch of ONE wave (n_pairs <= 8) is left as it was: nobody waits for it but its caller, batches that small reach this kernel
+    // only under the test switches (GNX_FP_SMALL, GNX_FASTPATH=2) or as local alignments, and tests/test_concurrent_pairs.py holds
+    // the rate of combined 16-pair calls (full waves, unchanged) to 8 x that of single-pair calls -- the two paths move together or not at all.
     int m_max = 0, m_min = 0x7fffffff;
     for (int q = 0; q < 8; q++) {
-        const int mq = (pbase + q < n_pairs) ? plans[pbase + q].m : 0;
-        m_max = max(m_max, mq); m_min = min(m_min, mq);
+        const bool has = pbase + q < n_pairs;
+        const int mq = has ? plans[pbase + q].m : 0;
+        m_max = max(m_max, mq);
+        if (has || ROLE != 0 || n_pairs <= G8) m_min = min(m_min, mq);
     }
+    if (m_min == 0x7fffffff) m_min = 0;
     const int p = pbase + g;
     const bool valid = p < n_pairs;
     PairPlan pl;
@@ -193,7 +204,7 @@ __device__ __forceinline__ void fp_sweep_body(int *__restrict__ lds, const int w
 #pragma unroll
         for (int b = 0; b < 5; b++) {
 #pragma unroll
-            for (int k = 0; k < FP8_LW; k++) prof[b * FP8_BST + lp * FP8_LW + k] = (lds[a5[2 * k] + b] & 0xffff) | (lds[a5[2 * k + 1] + b] << 16);
+            for (int k = 0; k < FP8_LW; k++) prof[b * FP8_BST + lp * FP8_LW + k] = (tab[a5[2 * k] + b] & 0xffff) | (tab[a5[2 * k + 1] + b] << 16);
         }
         __syncthreads();
     }
@@ -447,14 +458,39 @@ __device__ __forceinline__ void fp_sweep_body(int *__restrict__ lds, const int w
 }
 
 // reads of one row block (n <= 8 * RR)
-template <int RR, bool XP = false, bool PK = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void fp_sweep_kernel(const PairPlan *__restrict__ plans, int n_pairs,
+// WG = waves per workgroup.  1: one wave, its LDS a static array.  4: a workgroup of 256 threads puts ONE wave on each SIMD of its CU, so
+//   every resident workgroup loads the four SIMDs equally wherever the dispatcher sends it (one-wave workgroups land on whichever
+//   SIMD has a slot: 11 per CU sit (3,3,3,2), and a second round goes where slots come free first -- DESIGN.md 4.1).  Each wave sweeps
+//   its own eight pairs, wave index blockIdx.x * 4 + wave, on its own slice of the workgroup's LDS (profile and base rings).
+//   LDS: a wave's 32 + 3200 + 144 dwords are 13 504 B, and four of them 54 016 B = 43 granules of 1280 B -- three workgroups would need
+//   129 of a CU's 128.  The 32-dword score table (4 (s - 2e), the same for every pair of the call) is therefore kept ONCE per workgroup:
+//   all four waves store the same 32 values to it before the first barrier and read it between the two.  32 + 4 x 3344 dwords =
+//   53 632 B = 42 granules: three workgroups = 12 waves per CU, (3,3,3,3), on 126 granules.  A slice starts 3344 dwords = 16 banks
+//   (mod 32) behind the one before it: every bank rule of the layout is about the lanes of ONE wave and is kept by a common shift.
+//   That LDS is DYNAMIC (sized at launch: FP_WG4_LDS_BYTES), so the kernel declares no static LDS -- the static budget of 11 granules that
+//   tests/test_kernel_resources.py pins for every fp_sweep_kernel is the one-wave form's; tests/test_fp_sweep_wg4_resources.py pins this one.
+//   Barriers: ROLE 0 runs exactly two __syncthreads(), both in the prologue (around the profile build), and every wave reaches both
+//   whatever its pairs are -- a wave without pairs builds a profile of padding -- so four waves whose windows differ by hundreds of steps
+//   cannot miss each other.  There is no barrier in the step loop (hand_down's are for the blocks that hand a row down: never ROLE 0).
+constexpr int FP_WG4 = 4;
+constexpr int FP8_SLICE = FP8_LDS - 32; // a wave's LDS without the score table
+constexpr int FP_WG4_LDS_BYTES = (32 + FP_WG4 * FP8_SLICE) * 4;
+static_assert(FP_WG4_LDS_BYTES <= 42 * 1280, "four waves' LDS must fit 42 granules: three workgroups per CU");
+template <int RR, bool XP = false, bool PK = false, int WG = 1>
+__global__ __launch_bounds__(64 * WG) __attribute__((amdgpu_waves_per_eu(3, 3))) void fp_sweep_kernel(const PairPlan *__restrict__ plans, int n_pairs,
                                                       const uint8_t *__restrict__ a_buf, const int64_t *__restrict__ a_start,
                                                       const uint8_t *__restrict__ b_buf, const int64_t *__restrict__ b_start,
                                                       KParams kp, int *__restrict__ hcol, int2 *__restrict__ ckpt,
                                                       unsigned *__restrict__ rowi, unsigned *__restrict__ tail, int *__restrict__ err) {
-    __shared__ int lds[FP8_LDS];
-    fp_sweep_body<RR, XP, 0, PK>(lds, (int)blockIdx.x, plans, n_pairs, a_buf, a_start, b_buf, b_start, kp, hcol, ckpt, rowi, tail, err, nullptr, 0, false, nullptr, nullptr);
+    static_assert(WG == 1 || WG == FP_WG4, "one wave or four per workgroup");
+    if constexpr (WG == 1) {
+        __shared__ int lds[FP8_LDS];
+        fp_sweep_body<RR, XP, 0, PK>(lds, lds, (int)blockIdx.x, (int)threadIdx.x, plans, n_pairs, a_buf, a_start, b_buf, b_start, kp, hcol, ckpt, rowi, tail, err, nullptr, 0, false, nullptr, nullptr);
+    } else {
+        extern __shared__ int fp_wg_lds[];
+        const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6); // (wave-uniform: the slice's base and the wave index stay scalar; the body's profile starts 32 dwords into its slice pointer, behind the shared table for wave 0)
+        fp_sweep_body<RR, XP, 0, PK>(fp_wg_lds + wave * FP8_SLICE, fp_wg_lds, (int)blockIdx.x * WG + wave, (int)threadIdx.x & 63, plans, n_pairs, a_buf, a_start, b_buf, b_start, kp, hcol, ckpt, rowi, tail, err, nullptr, 0, false, nullptr, nullptr);
+    }
 }
 
 // reads of S >= 2 row blocks: the grid holds n_levels levels of W waves, block index = level-major, level level0 + blockIdx.x / W (0 = top).
@@ -483,9 +519,9 @@ __global__ __launch_bounds__(64) void fp_sweep_levels_kernel(const PairPlan *__r
         int *po = prog + (int64_t)level * W + w;
         const int *pi = po - W;
         if (lv != lv_own - n_stolen) __syncthreads(); // the LDS profile of the level before is no longer read
-        if (level == 0) fp_sweep_body<RRTOP, XP, 1, PK>(lds, w, plans, n_pairs, a_buf, a_start, b_buf, b_start, kp, hcol, ckpt, rowi, tail, err, rowbuf, below, piped != 0, nullptr, po);
-        else if (below == 0) fp_sweep_body<2 * FP8_LW, XP, 2, PK>(lds, w, plans, n_pairs, a_buf, a_start, b_buf, b_start, kp, hcol, ckpt, rowi, tail, err, rowbuf, 0, piped != 0, pi, nullptr);
-        else fp_sweep_body<2 * FP8_LW, XP, 3, PK>(lds, w, plans, n_pairs, a_buf, a_start, b_buf, b_start, kp, hcol, ckpt, rowi, tail, err, rowbuf, below, piped != 0, pi, po);
+        if (level == 0) fp_sweep_body<RRTOP, XP, 1, PK>(lds, lds, w, (int)threadIdx.x, plans, n_pairs, a_buf, a_start, b_buf, b_start, kp, hcol, ckpt, rowi, tail, err, rowbuf, below, piped != 0, nullptr, po);
+        else if (below == 0) fp_sweep_body<2 * FP8_LW, XP, 2, PK>(lds, lds, w, (int)threadIdx.x, plans, n_pairs, a_buf, a_start, b_buf, b_start, kp, hcol, ckpt, rowi, tail, err, rowbuf, 0, piped != 0, pi, nullptr);
+        else fp_sweep_body<2 * FP8_LW, XP, 3, PK>(lds, lds, w, (int)threadIdx.x, plans, n_pairs, a_buf, a_start, b_buf, b_start, kp, hcol, ckpt, rowi, tail, err, rowbuf, below, piped != 0, pi, po);
     }
 }
 

@@ -33,10 +33,12 @@
 //   lat_fill.hip.h     lat_fill_kernel: one pair per wave (64 lanes x 2 rows), launches of few long pairs
 //   gnx_host.hip.h     host-buffer entry points: pinned staging, sub-batches, resident reference, contexts per GPU, RCCL
 //   host_cut.h         the sub-batch cut of the host flows (plain C++, tested on the CPU)
+//   fp_rounds.h        which form of the headline sweep a batch gets; the four-wave form's launches (plain C++, tested on the CPU)
 //   gnx_align.hip      host orchestration + C ABI (this file)
 #include "gnx_common.hip.h"
 #include "fill_affine.hip.h"
 #include "fp_sweep.hip.h"
+#include "fp_rounds.h"
 #include "fill_const.hip.h"
 #include "traceback.hip.h"
 #include "fp_walk.hip.h"
@@ -517,6 +519,26 @@ int run_device_fp(const gnx_params *prm, const KParams &kp, const TbParams &tp, 
             for (int level = 0; level < S; level++)
                 hipLaunchKernelGGL(klev, grid8, blockF, 0, st, splans, cnt, d_a, d_as, d_b, d_bs, kp, d_hfwd, d_ckpt, d_rowi, d_tail, d_err, rb, S, W, level, 0, prog);
             HIPCHK(hipGetLastError());
+            return GNX_OK;
+        }
+        // One row block: one-wave workgroups, or four-wave workgroups -- one wave on each SIMD of the CU, three workgroups per CU by LDS --
+        // by the pair count (gnx_fp_sweep_form: the measured rule, DESIGN.md 4.1, profiles/sweep_rounds.json).  Read per call:
+        // GNX_FP_WG4=0: never the four-wave form; =2: always, whatever the size.  GNX_FP_ROUND=k: the four-wave form as whole rounds of k
+        // workgroups and then the remainder, two launches on the one stream (fp_rounds.h: measured, never faster than one launch; tests).
+        // Same results in every form.
+        const char *w4env = getenv("GNX_FP_WG4"), *rdenv = getenv("GNX_FP_ROUND");
+        const int w4 = (w4env && *w4env) ? atoi(w4env) : 1;
+        if (w4 >= 2 || (w4 == 1 && gnx_fp_sweep_form(cnt, c.n_cu) == GNX_FP_FORM_WG4)) {
+            auto k4 = xp ? (kp.b2 ? (rows_per_lane == 19 ? fp_sweep_kernel<19, true, true, FP_WG4> : fp_sweep_kernel<20, true, true, FP_WG4>) // (no caller today: AffineGapLocal gets byte windows)
+                                  : (rows_per_lane == 19 ? fp_sweep_kernel<19, true, false, FP_WG4> : fp_sweep_kernel<20, true, false, FP_WG4>))
+                      : kp.b2 ? (rows_per_lane == 19 ? fp_sweep_kernel<19, false, true, FP_WG4> : fp_sweep_kernel<20, false, true, FP_WG4>)
+                              : (rows_per_lane == 19 ? fp_sweep_kernel<19, false, false, FP_WG4> : fp_sweep_kernel<20, false, false, FP_WG4>);
+            GnxFpLaunch ln[2];
+            const int nl = gnx_fp_round_plan(cnt, (rdenv && *rdenv) ? atoll(rdenv) : 0, FP_WG4 * G8, ln);
+            for (int x = 0; x < nl; x++) { // (two: on the one stream, one after the other)
+                hipLaunchKernelGGL(k4, dim3((unsigned)ln[x].grid), dim3(64 * FP_WG4), FP_WG4_LDS_BYTES, st, splans + ln[x].first, (int)ln[x].count, d_a, d_as, d_b, d_bs, kp, d_hfwd, d_ckpt, d_rowi, d_tail, d_err);
+                HIPCHK(hipGetLastError());
+            }
             return GNX_OK;
         }
         auto k = xp ? (rows_per_lane == 19 ? fp_sweep_kernel<19, true> : fp_sweep_kernel<20, true>)
