@@ -506,6 +506,48 @@ def align_batch(params, alphas, betas):
     return scores[:n], ops, off
 
 
+def _h_lens(n, h_len):
+    """a host length table of the device entries as (array kept alive, pointer): None stays NULL"""
+    if h_len is None:
+        return None, None
+    h = _i64(h_len)
+    if h.shape[0] < n:
+        raise ValueError("length table shorter than n_pairs")
+    return h, h.ctypes.data
+
+
+def align_batch_device(params, n_pairs, d_alpha_buf, d_alpha_start, d_beta_buf, d_beta_start, h_alpha_len, h_beta_len,
+                       d_score, d_ops, ops_capacity, d_ops_off, stream=0, d_alpha_len=0, d_beta_len=0, want_total=True):
+    """gnx_align_batch_device as the C ABI has it: every d_* is a raw device address (an int; 0 = NULL), h_*_len are host int64 arrays
+    (None = NULL), stream is a hipStream_t handle as an int (0 = the NULL stream).  Returns (rc, total_ops) and never raises
+    on a return code -- GNX_ECAPACITY comes back with the number of runs the whole batch needs.  want_total=False passes out_total_ops = NULL
+    (total_ops is then None)."""
+    keep_a, pa = _h_lens(int(n_pairs), h_alpha_len)
+    keep_b, pb = _h_lens(int(n_pairs), h_beta_len)
+    total = ctypes.c_int64(-1)
+    rc = lib().gnx_align_batch_device(ctypes.byref(params), int(n_pairs), d_alpha_buf or None, d_alpha_start or None, d_alpha_len or None,
+                                      d_beta_buf or None, d_beta_start or None, d_beta_len or None, pa, pb,
+                                      d_score or None, d_ops or None, int(ops_capacity), d_ops_off or None,
+                                      ctypes.byref(total) if want_total else None, stream or None)
+    del keep_a, keep_b
+    return int(rc), (int(total.value) if want_total else None)
+
+
+def score_batch_device(params, n_pairs, d_alpha_buf, d_alpha_start, d_beta_buf, d_beta_start, h_alpha_len, h_beta_len,
+                       d_score, stream=0, d_alpha_len=0, d_beta_len=0):
+    """gnx_score_batch_device on raw device addresses (see align_batch_device).  Returns rc."""
+    keep_a, pa = _h_lens(int(n_pairs), h_alpha_len)
+    keep_b, pb = _h_lens(int(n_pairs), h_beta_len)
+    rc = lib().gnx_score_batch_device(ctypes.byref(params), int(n_pairs), d_alpha_buf or None, d_alpha_start or None, d_alpha_len or None,
+                                      d_beta_buf or None, d_beta_start or None, d_beta_len or None, pa, pb, d_score or None, stream or None)
+    del keep_a, keep_b
+    return int(rc)
+
+
+def last_error():
+    return lib().gnx_last_error().decode("utf-8", "replace")
+
+
 def score_batch_windows(params, a_buf, a_start, a_len, b_buf, b_start, b_len):
     """gnx_score_batch_windows: the scores of align_batch_windows without the CIGARs.  Returns scores[int64]."""
     L = lib()

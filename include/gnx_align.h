@@ -193,7 +193,14 @@ int gnx_align_pair(const gnx_params *p, const uint8_t *alpha, int64_t n, const u
 /* All d_* pointers are device memory on the bound device; h_* are host copies of the window tables used
  * for planning.  Kernels are enqueued on `stream` (a hipStream_t, may be NULL) and the call returns
  * after they finished.  d_ops has room for ops_capacity elements; *out_total_ops receives the number
- * used (GNX_ECAPACITY if it did not fit). */
+ * used (GNX_ECAPACITY if it did not fit).
+ * Contract (tests/test_device_entry_gpu.py): everything that reads the inputs or writes the outputs is queued on
+ * `stream` and on nothing else, so "same stream" orders the call behind the caller's earlier work; on return the outputs are final
+ * for any stream.  With GNX_ECAPACITY *out_total_ops is the need of the WHOLE batch, exactly (a second call with that capacity
+ * succeeds), nothing is written at or behind d_ops[ops_capacity] in either case, and the refused call leaves no state behind.  What
+ * d_score and d_ops_off hold after a refusal is UNSPECIFIED (most routes have written every score and offset, the mixed-batch route
+ * neither).  The base pointers need no alignment; windows may overlap, repeat and come in any order; d_*_len and out_total_ops may
+ * be NULL, d_ops may not; n_pairs == 0 writes d_ops_off[0] = 0 and nothing else. */
 int gnx_align_batch_device(const gnx_params *p, int64_t n_pairs,
                            const uint8_t *d_alpha_buf, const int64_t *d_alpha_start, const int64_t *d_alpha_len,
                            const uint8_t *d_beta_buf, const int64_t *d_beta_start, const int64_t *d_beta_len,
@@ -226,7 +233,10 @@ int gnx_score_batch_windows(const gnx_params *p, int64_t n_pairs,
 /* beta = windows of the resident reference (gnx_set_reference; read packed, 2 bits per base) */
 int gnx_score_batch_by_offset(const gnx_params *p, int64_t n_pairs, const uint8_t *alpha_cat, const int64_t *alpha_off,
                               const int64_t *ref_start, const int64_t *ref_len, int64_t *out_score);
-/* device-resident twin of gnx_align_batch_device: d_score[n_pairs] is device memory, the call returns after the kernels finished */
+/* device-resident twin of gnx_align_batch_device: d_score[n_pairs] is device memory, the call returns after the kernels finished.
+ * The same contract: queued on `stream` alone, d_score final on return and equal to the d_score of gnx_align_batch_device on the same
+ * arguments, nothing written behind d_score[n_pairs]; off the sweep (routes 7 / 8) it runs the align entry's route into a CIGAR buffer
+ * of the context's own, so it never returns GNX_ECAPACITY.  n_pairs == 0 is GNX_OK and writes nothing. */
 int gnx_score_batch_device(const gnx_params *p, int64_t n_pairs,
                            const uint8_t *d_alpha_buf, const int64_t *d_alpha_start, const int64_t *d_alpha_len,
                            const uint8_t *d_beta_buf, const int64_t *d_beta_start, const int64_t *d_beta_len,

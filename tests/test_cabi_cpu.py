@@ -44,6 +44,25 @@ def test_no_cpu_fallback():
     assert ei.value.code == _lib.GNX_EDEVICE
 
 
+def test_device_entries_without_a_device():
+    """both device-resident entries: GNX_EDEVICE before anything else is looked at, through the bindings that hand the code back"""
+    L = _lib.lib()
+    if L.gnx_device_count() > 0:
+        pytest.skip("a GPU is visible; covered by the gpu tests")
+    p = _lib.make_params(_lib.GNX_AFFINE_GAP, align.DefaultScoreMatrix, -400, -30)
+    lens = np.asarray([4], np.int64)
+    for n, h in ((1, lens), (0, None)):
+        assert _lib.align_batch_device(p, n, 0, 0, 0, 0, h, h, 0, 0, 0, 0) == (_lib.GNX_EDEVICE, -1)
+        assert _lib.align_batch_device(p, n, 0, 0, 0, 0, h, h, 0, 0, 0, 0, want_total=False) == (_lib.GNX_EDEVICE, None)
+        assert _lib.score_batch_device(p, n, 0, 0, 0, 0, h, h, 0) == _lib.GNX_EDEVICE
+    assert "device" in _lib.last_error().lower()
+
+
+def test_the_binding_does_not_import_torch():
+    src = open(os.path.join(ROOT, "gonomics_amd", "_lib.py")).read()
+    assert not re.search(r"^\s*(import|from)\s+torch\b", src, flags=re.M)
+
+
 def test_host_helpers():
     a = dna.StringToBases("ACGTNacgtn-.*")
     assert a.tolist() == list(range(13))

@@ -42,6 +42,16 @@ def test_score_without_a_device_is_an_error():
     assert ei.value.code == _lib.GNX_EDEVICE
 
 
+def test_score_device_entry_without_a_device_is_an_error():
+    L = _lib.lib()
+    if L.gnx_device_count() > 0:
+        pytest.skip("a GPU is visible; covered by the gpu tests")
+    assert callable(_lib.score_batch_device) and callable(_lib.align_batch_device)
+    for mode in range(5):
+        p = _lib.make_params(mode, align.DefaultScoreMatrix, -400, -30 if mode in (0, 2, 3) else 0)
+        assert _lib.score_batch_device(p, 2, 0, 0, 0, 0, np.asarray([3, 4], np.int64), np.asarray([5, 6], np.int64), 0) == _lib.GNX_EDEVICE
+
+
 def test_align_best_of_selection_rule(monkeypatch):
     """first maximum in candidate order, ties to the lowest index, K_r varying, K_r = 1 -- with stub score and align functions"""
     table = {}  # (read id, candidate id) -> score; a sequence's id is its first element
