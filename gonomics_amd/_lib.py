@@ -18,7 +18,7 @@ EXPORTS = ["gnx_device_count", "gnx_init", "gnx_shutdown", "gnx_last_error", "gn
            "gnx_align_batch_windows", "gnx_align_pair", "gnx_align_batch_device", "gnx_get_timing",
            "gnx_affine_gap_chunk_batch", "gnx_multiple_affine_gap_batch", "gnx_gsw_extend_batch",
            "gnx_init_devices", "gnx_n_devices", "gnx_set_reference", "gnx_set_reference_synthetic", "gnx_align_batch_by_offset",
-           "gnx_seed_index_build", "gnx_seed_index_set", "gnx_seed_find_batch", "gnx_seed_index_set_gen", "gnx_seed_find_batch_gen", "gnx_gsw_graph_create", "gnx_gsw_graph_free", "gnx_gsw_map_reads", "gnx_debug_occupy", "gnx_debug_counter", "gnx_debug_fill_scratch", "gnx_debug_gapless_certificate", "gnx_debug_gapless_certificate_n", "gnx_reference_info",
+           "gnx_seed_index_build", "gnx_seed_index_set", "gnx_seed_find_batch", "gnx_seed_index_set_gen", "gnx_seed_find_batch_gen", "gnx_gsw_graph_create", "gnx_gsw_graph_free", "gnx_gsw_map_reads", "gnx_debug_occupy", "gnx_debug_counter", "gnx_debug_fill_scratch", "gnx_debug_gapless_certificate", "gnx_debug_gapless_certificate_n", "gnx_debug_gapless_certificate_edge", "gnx_reference_info",
            "gnx_score_batch", "gnx_score_batch_windows", "gnx_score_batch_by_offset", "gnx_score_batch_device",
            "gnx_locate_batch", "gnx_locate_batch_windows", "gnx_locate_batch_by_offset",
            "gnx_locate_span_batch", "gnx_locate_span_batch_windows", "gnx_locate_span_batch_by_offset",
@@ -291,6 +291,9 @@ def lib():
         if hasattr(L, "gnx_debug_gapless_certificate_n"):
             L.gnx_debug_gapless_certificate_n.argtypes = [ctypes.POINTER(GnxParams), c_p, i64, c_p, i64, i64, c_p]
             L.gnx_debug_gapless_certificate_n.restype = ctypes.c_int
+        if hasattr(L, "gnx_debug_gapless_certificate_edge"):
+            L.gnx_debug_gapless_certificate_edge.argtypes = [ctypes.POINTER(GnxParams), c_p, i64, c_p, i64, i64, c_p]
+            L.gnx_debug_gapless_certificate_edge.restype = ctypes.c_int
         if hasattr(L, "gnx_debug_fill_scratch"):
             L.gnx_debug_fill_scratch.argtypes = [ctypes.c_uint32, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
             L.gnx_debug_fill_scratch.restype = ctypes.c_int
@@ -322,12 +325,22 @@ def debug_gapless_certificate(params, a, b, K=16):
 
 
 def debug_gapless_certificate_n(params, a, b, K=16):
-    """The same with reads that hold N admitted, as the kernel decides: (certified, c, d_star, score, edge rule decided, N in the read)."""
+    """The same with reads that hold N admitted, the kernel's rule before its graded edge test: (certified, c, d_star, score, edge rule decided, N in the read)."""
     a = np.ascontiguousarray(a, dtype=np.uint8)
     b = np.ascontiguousarray(b, dtype=np.uint8)
     out = np.zeros(6, dtype=np.int64)
     check(lib().gnx_debug_gapless_certificate_n(ctypes.byref(params), a.ctypes.data, a.shape[0], b.ctypes.data, b.shape[0], int(K), out.ctypes.data))
     return bool(out[0]), int(out[1]), int(out[2]), int(out[3]), bool(out[4]), int(out[5])
+
+
+def debug_gapless_certificate_edge(params, a, b, K=16):
+    """The same with the edge rule graded by the window's first and last columns, as the kernel decides: the six fields above, admitted by
+    the graded test only, the largest grade at which the bounds without the bytes would have refused (-1: none)."""
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    b = np.ascontiguousarray(b, dtype=np.uint8)
+    out = np.zeros(8, dtype=np.int64)
+    check(lib().gnx_debug_gapless_certificate_edge(ctypes.byref(params), a.ctypes.data, a.shape[0], b.ctypes.data, b.shape[0], int(K), out.ctypes.data))
+    return bool(out[0]), int(out[1]), int(out[2]), int(out[3]), bool(out[4]), int(out[5]), bool(out[6]), int(out[7])
 
 
 def check(rc):

@@ -23,7 +23,10 @@ namespace {
 //      lanes' sums are combined in int64 by wave sums and prefix scans (__shfl on the two halves): the deficit and the score by sums,
 //      "no prefix of f above 0" by a scan of f, d* by a scan of g and a wave-wide (least prefix, first row), the edge rule's four
 //      sums by masked sums once the deficit has fixed T1 and T2, the read's N rows (nu of the thresholds) by a sum.  The call's matrix
-//      comes as a kernel argument (built once on the host).  A certified pair whose read holds an N adds one to *n_cert (one atomic).
+//      comes as a kernel argument (built once on the host).  A certified pair whose read holds an N adds one to *n_cert (one atomic);
+//   5. a pair that fails the edge rule's corners and nothing else gets the corners graded by the real bytes on diagonals 0 and m - n
+//      (gnx_certe_*: scans of the chunks' non-free counts, a ballot for the lane that holds the (j + 1)-th non-free row, E from a prefix
+//      scan of the chunks' losses read by readlane); one it admits adds one to n_cert[1] instead.
 // Windows of the packed reference that hold an exception (N, byte >= 5) are not certified; bytes >= 5 raise the sweep's error flag.
 // ------------------------------------------------------------------------------------------------------
 constexpr int CERT_K = 16;
@@ -41,6 +44,17 @@ __device__ __forceinline__ int64_t cert_wave_scan(int64_t v, int lane) { // incl
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) { const int64_t t = __shfl_up(v, d, 64); if (lane >= d) v += t; }
     return v;
+}
+
+__device__ __forceinline__ int cert_wave_scan32(int v, int lane) { // inclusive prefix sums of small counts
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(v, d, 64); if (lane >= d) v += t; }
+    return v;
+}
+__device__ __forceinline__ int64_t cert_read_lane64(int64_t v, int src) { // lane src's value, src uniform
+    const int s = __builtin_amdgcn_readfirstlane(src);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(uint64_t)v, s), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((uint64_t)v >> 32), s);
+    return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
 __device__ __forceinline__ unsigned cert_hash(unsigned code) { return code * 0x9E3779B1u; } // slot = top 9 bits, filter bit = top 14 bits
@@ -97,7 +111,7 @@ __global__ __launch_bounds__(64) void fp_cert_kernel(const PairPlan *__restrict_
     }
     __syncthreads();
 
-    // ---- 2. the window, 16 columns per lane and round, aligned to the 16-byte / dword grid of its buffer ----
+    // ---- 2 and 3. the window, 16 columns per lane and round; all hits on one diagonal, aligned to the 16-byte / dword grid of its buffer ----
     const int sh = PK ? (int)(boff & 15) : (int)((uintptr_t)(b_buf + boff) & 15); // columns of the first group that lie before the window
     const int n_groups = (sh + m + 15) >> 4;
     const uint8_t *bw = b_buf + boff - sh;              // bytes: the first group's address (16-byte aligned)
@@ -158,7 +172,7 @@ __global__ __launch_bounds__(64) void fp_cert_kernel(const PairPlan *__restrict_
     const int c = dmin;
     if (dmin != dmax || c <= 0 || c >= m - n) { if (lane == 0) live[p] = 1; return; } // (no hit at all: dmin > dmax)
 
-    // ---- 3. the decision across the wave: the real bases under a lane's rows on diagonal c, on the window's first and last columns ----
+    // ---- 4. the decision across the wave: the real bases under a lane's rows on diagonal c, on the window's first and last columns ----
     const int chunk = (n + 63) >> 6, i0 = lane * chunk;
     GnxCertLane ln;
     gnx_cert_lane_init(&ln);
@@ -195,7 +209,46 @@ __global__ __launch_bounds__(64) void fp_cert_kernel(const PairPlan *__restrict_
     }
     int64_t best, ds, sc;
     gnx_cert_tail(__shfl(Gi, 63, 64), g_low, g_row, n, &best, &ds);
-    if (!gnx_cert_finish(&t, mx.o, mx.e, n, m, f_pos, mid_sum, h1, h2, t1, t2, best, ds, &ds, &sc)) { if (lane == 0) live[p] = 1; return; }
+    bool by_edge = false; // admitted by the graded corners only
+    if (!gnx_cert_finish(&t, mx.o, mx.e, n, m, f_pos, mid_sum, h1, h2, t1, t2, best, ds, &ds, &sc)) {
+        // ---- 5. refused for the corners and for nothing else: the edge rule graded by the bytes on diagonals 0 and m - n (uniform) ----
+        if (!(t.ok && !f_pos && t.edge && ds < n && (h1 + t2 >= -mx.o || h2 + t1 >= -mx.o))) { if (lane == 0) live[p] = 1; return; }
+        GnxCertEdgeLane el;
+        gnx_certe_lane_init(&el, i0);
+#pragma unroll
+        for (int k = 0; k < CERT_CHUNK; k++) {
+            const int i = i0 + k;
+            if (k < chunk && i < n) gnx_certe_lane_row(&el, sa[i], (unsigned)bp.at(i), (unsigned)bp.at(m - n + i));
+        }
+        const int inc0 = cert_wave_scan32(el.c0, lane), incm = cert_wave_scan32(el.cm, lane);
+        const int before0 = inc0 - el.c0, afterm = __builtin_amdgcn_readlane(incm, 63) - incm;
+        // P[k] = the loss of the first k rows: the lane of row k holds it (k0 before its first row)
+        const int64_t k0 = cert_wave_scan(ln.loss, lane) - ln.loss;
+        auto prefix = [&](int k) -> int64_t {
+            if (k >= n) return D;
+            const int L = k / chunk, r = k - L * chunk;
+            int64_t v = k0; // (sums, not a choice of three values: nothing here may turn into a table in private memory)
+#pragma unroll
+            for (int x = 0; x + 1 < CERT_CHUNK; x++) v += r > x ? loss[x] : 0;
+            return cert_read_lane64(v, L);
+        };
+        const int J30 = (int)gnx_certe_grades(mx.lambda, mx.o, D);
+        bool pass = true;
+        for (int j = 0; j <= J30 && pass; j++) {
+            const int hr = gnx_certe_head_row(&el, before0, j), tr = gnx_certe_tail_row(&el, afterm, j);
+            const unsigned long long bh = __ballot(hr >= 0), bt = __ballot(tr >= 0); // (one lane at most holds the row)
+            const int A0 = bh ? __builtin_amdgcn_readlane(hr, __builtin_amdgcn_readfirstlane(__ffsll(bh) - 1)) : n;
+            const int Am = bt ? n - 1 - __builtin_amdgcn_readlane(tr, __builtin_amdgcn_readfirstlane(__ffsll(bt) - 1)) : n;
+            int64_t pq[4], ha, ta, hb, tb;
+            gnx_certe_corners(CERT_K, nu, j, A0, Am, pq);
+            gnx_certe_span(n, pq[0], pq[1], &ha, &ta);
+            gnx_certe_span(n, pq[2], pq[3], &hb, &tb);
+            pass = gnx_certe_grade(mx.lambda, mx.o, j, prefix((int)ha) + D - prefix((int)ta), prefix((int)hb) + D - prefix((int)tb)) != 0;
+        }
+        if (!pass) { if (lane == 0) live[p] = 1; return; }
+        sc = mid_sum + best + 2 * mx.o + mx.e * ((int64_t)n + m);
+        by_edge = true;
+    }
     if (lane == 0) {
         // the runs in traceback order, as fp_walk_kernel stages them: [d* M] [m - n - c I] [n - d* M] [c I]
         gnx_cigar *stg = stage + (int64_t)p * cap;
@@ -208,7 +261,8 @@ __global__ __launch_bounds__(64) void fp_cert_kernel(const PairPlan *__restrict_
         nops[p] = cnt;
         score_out[p] = sc;
         live[p] = 0;
-        if (nu > 0) atomicAdd(reinterpret_cast<unsigned long long *>(n_cert), 1ull);
+        if (by_edge) atomicAdd(reinterpret_cast<unsigned long long *>(n_cert + 1), 1ull);
+        else if (nu > 0) atomicAdd(reinterpret_cast<unsigned long long *>(n_cert), 1ull);
     }
 }
 

@@ -14,6 +14,7 @@
 #else
 #define GNX_CERT_HD
 #endif
+#define GNX_CERTE_HD GNX_CERT_HD __attribute__((always_inline)) // the graded edge rule's pieces: called in a loop of the kernel with their arguments in registers
 
 // Per call, from gnx_params: w(x, y) = s(x, y) - 2e (the rebasing of section 4), R_x = w(x, x), lambda = the least loss of a read row
 // that is mismatched or skipped and is not N; R[4] = R_N = max(0, max_y w(N, y)), so that an N row loses >= 0 wherever it lies.
@@ -209,6 +210,121 @@ GNX_CERT_HD inline int gnx_certn_decide(const GnxCertMatrix *mx, const uint8_t *
 GNX_CERT_HD inline int gnx_cert_decide(const GnxCertMatrix *mx, const uint8_t *a, int64_t n, const uint8_t *bd, const uint8_t *bf, const uint8_t *bl,
                                        int64_t m, int64_t c, int64_t K, int64_t ci, int64_t cj, int64_t *d_star, int64_t *score) {
     return gnx_certn_decide(mx, a, n, bd, bf, bl, m, c, K, ci, cj, 0, d_star, score, nullptr, nullptr);
+}
+
+// ---- the edge rule graded by the known end diagonals ("The edge rule on the known end diagonals") ----
+// Applies where gnx_certn_bounds gave ok and edge, items 3 and 6 hold and a corner of gnx_cert_finish failed.  A three-run path that
+// reaches diagonal c by its first run has the rows before that on diagonal 0, one that leaves c by its last run has the rows after it on
+// diagonal m - n: both are loaded for item 6, so the real bytes bound those segments instead of "exact runs shorter than K".
+// Row i is non-free on diagonal 0 (nf0) / m - n (nfm) when its read base is not N and differs from the window's byte there.
+GNX_CERTE_HD inline void gnx_certe_flags(unsigned a, unsigned bf, unsigned bl, int *nf0, int *nfm) {
+    *nf0 = (a != 4 && a != bf) ? 1 : 0;
+    *nfm = (a != 4 && a != bl) ? 1 : 0;
+}
+// A lane's chunk of consecutive rows from row i0 on, taken in ascending order: bit k of bits0 / bitsm = row i0 + k is non-free.
+struct GnxCertEdgeLane {
+    int32_t bits0, bitsm, c0, cm, i0, rows;
+};
+GNX_CERTE_HD inline void gnx_certe_lane_init(GnxCertEdgeLane *l, int i0) { l->bits0 = l->bitsm = l->c0 = l->cm = 0; l->i0 = i0; l->rows = 0; }
+GNX_CERTE_HD inline void gnx_certe_lane_row(GnxCertEdgeLane *l, unsigned a, unsigned bf, unsigned bl) {
+    int f0, fm;
+    gnx_certe_flags(a, bf, bl, &f0, &fm);
+    l->bits0 |= f0 << l->rows; l->bitsm |= fm << l->rows;
+    l->c0 += f0; l->cm += fm;
+    l->rows++;
+}
+// The chunk's row that is the (j + 1)-th non-free one on diagonal 0 counted from row 0, when before0 = the non-free rows of the chunks
+// before this one; -1: not in this chunk.  A0(j) = that row (the first A0 rows hold j non-free ones), n when no chunk has it.
+GNX_CERTE_HD inline int gnx_certe_head_row(const GnxCertEdgeLane *l, int before0, int j) {
+    int r = j - before0;
+    if (r < 0 || r >= l->c0) return -1;
+    for (int k = 0; k < l->rows; k++) if ((l->bits0 >> k) & 1) { if (r == 0) return l->i0 + k; r--; }
+    return -1;
+}
+// The same from the read's end on diagonal m - n, afterm = the non-free rows of the chunks after this one; Am(j) = n - 1 - that row.
+GNX_CERTE_HD inline int gnx_certe_tail_row(const GnxCertEdgeLane *l, int afterm, int j) {
+    int r = j - afterm;
+    if (r < 0 || r >= l->cm) return -1;
+    for (int k = l->rows - 1; k >= 0; k--) if ((l->bitsm >> k) & 1) { if (r == 0) return l->i0 + k; r--; }
+    return -1;
+}
+// The graded corners for j imperfect non-N rows outside the segment on diagonal c: rows before / after the segment of the two families
+// (delta1 = c: pq[0], pq[1]; delta2 = c: pq[2], pq[3]).  Ts(J3) = T1 and Tt(J3) = T2 of gnx_certn_bounds.
+GNX_CERTE_HD inline void gnx_certe_corners(int64_t K, int64_t nu, int64_t j, int64_t A0, int64_t Am, int64_t pq[4]) {
+    const int64_t Ts = (1 + j + nu) * (K - 1) + j + nu, Tt = (2 + j + nu) * (K - 1) + j + nu;
+    pq[0] = A0 < Ts ? A0 : Ts; pq[1] = Ts + Am < Tt ? Ts + Am : Tt;
+    pq[2] = Ts + A0 < Tt ? Ts + A0 : Tt; pq[3] = Am < Ts ? Am : Ts;
+}
+// E(p, q) as two prefix sums of the loss: the rows [0, *head) and [*tail, n), E = P[*head] + D - P[*tail] with P[k] = the loss of the first k rows
+GNX_CERTE_HD inline void gnx_certe_span(int64_t n, int64_t p, int64_t q, int64_t *head, int64_t *tail) {
+    const int64_t pp = p < n ? p : n, qq = q < n - pp ? q : n - pp;
+    *head = pp; *tail = n - qq;
+}
+// one grade: both corners strictly below O + lambda j
+GNX_CERTE_HD inline int gnx_certe_grade(int64_t lambda, int64_t o, int64_t j, int64_t e1, int64_t e2) {
+    const int64_t lim = -o + lambda * j;
+    return (e1 < lim && e2 < lim) ? 1 : 0;
+}
+// the number of grades: j = 0 .. J3 without nu
+GNX_CERTE_HD inline int64_t gnx_certe_grades(int64_t lambda, int64_t o, int64_t D) { return gnx_cert_div(D + o, lambda); }
+
+// The serial decision: today's rule, then -- only where it fails at the corners -- the graded test.  by_edge (may be null) = 1 when the graded
+// test admitted the pair and the old rule did not; jdec (may be null) = the largest grade at which the K-run bound alone (A0 = Am = n)
+// would have refused, -1 when none (diagnostics: which grade the bytes decided).  Score and d* are the old rule's closed form.
+GNX_CERT_HD inline int gnx_certe_decide(const GnxCertMatrix *mx, const uint8_t *a, int64_t n, const uint8_t *bd, const uint8_t *bf, const uint8_t *bl,
+                                        int64_t m, int64_t c, int64_t K, int64_t ci, int64_t cj, int allow_n, int64_t *d_star, int64_t *score,
+                                        int64_t *edge, int64_t *nu_out, int64_t *by_edge, int64_t *jdec) {
+    if (by_edge) *by_edge = 0;
+    if (jdec) *jdec = -1;
+    if (gnx_certn_decide(mx, a, n, bd, bf, bl, m, c, K, ci, cj, allow_n, d_star, score, edge, nu_out)) return 1;
+    if (!mx->ok || n < 1 || K < 1 || m < n + 2 || c <= 0 || c >= m - n || ci < n || cj < m) return 0;
+    const int64_t rn = mx->R[4];
+    GnxCertRow r;
+    int64_t D = 0, mid_sum = 0, F = 0, nu = 0;
+    for (int64_t i = 0; i < n; i++) {
+        if (!gnx_certn_row<5>(mx->w, rn, allow_n, a[i], bd[i], bf[i], bl[i], &r)) return 0;
+        nu += a[i] == 4 ? 1 : 0;
+        D += r.loss; mid_sum += r.mid; F += r.f;
+        if (F > 0) return 0;
+    }
+    const GnxCertBounds t = gnx_certn_bounds(mx->lambda, mx->o, n, K, D, nu);
+    if (!t.ok || !t.edge) return 0;
+    int64_t G = 0, best = 0, ds = 0;
+    for (int64_t d = 1; d <= n; d++) {
+        gnx_certn_row<5>(mx->w, rn, allow_n, a[n - d], bd[n - d], bf[n - d], bl[n - d], &r);
+        G += r.g;
+        if (G >= best) { best = G; ds = d; }
+    }
+    if (ds >= n) return 0;
+    // P[k] by a running sum: E of a corner walks its rows (serial: at most (1 + J3) corners of <= n rows)
+    auto E = [&](int64_t p, int64_t q) -> int64_t {
+        int64_t head, tail, s = 0;
+        gnx_certe_span(n, p, q, &head, &tail);
+        for (int64_t i = 0; i < n; i++)
+            if (i < head || i >= tail) { gnx_certn_row<5>(mx->w, rn, allow_n, a[i], bd[i], bf[i], bl[i], &r); s += r.loss; }
+        return s;
+    };
+    const int64_t J30 = gnx_certe_grades(mx->lambda, mx->o, D);
+    for (int64_t j = 0; j <= J30; j++) {
+        int64_t A0 = n, Am = n, seen = 0;
+        int f0, fm;
+        for (int64_t i = 0; i < n; i++) { gnx_certe_flags(a[i], bf[i], bl[i], &f0, &fm); if (f0 && seen++ == j) { A0 = i; break; } }
+        seen = 0;
+        for (int64_t i = n - 1; i >= 0; i--) { gnx_certe_flags(a[i], bf[i], bl[i], &f0, &fm); if (fm && seen++ == j) { Am = n - 1 - i; break; } }
+        int64_t pq[4];
+        gnx_certe_corners(K, nu, j, A0, Am, pq);
+        if (!gnx_certe_grade(mx->lambda, mx->o, j, E(pq[0], pq[1]), E(pq[2], pq[3]))) return 0;
+        if (jdec) {
+            gnx_certe_corners(K, nu, j, n, n, pq);
+            if (!gnx_certe_grade(mx->lambda, mx->o, j, E(pq[0], pq[1]), E(pq[2], pq[3]))) *jdec = j;
+        }
+    }
+    *d_star = ds;
+    *score = mid_sum + best + 2 * mx->o + mx->e * (n + m);
+    if (edge) *edge = 1;
+    if (nu_out) *nu_out = nu;
+    if (by_edge) *by_edge = 1;
+    return 1;
 }
 
 // Item 3 the naive way (host: the debug entry).  Exact K-mer matches of read positions q .. q + K - 1 and window positions j .. j + K - 1 over

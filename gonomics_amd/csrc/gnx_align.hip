@@ -293,6 +293,7 @@ int64_t max_abs_pen(const gnx_params *p, bool affine) {
 
 std::atomic<int64_t> g_cert_ok{0}, g_cert_offered{0}; // pairs certified gapless by the N-free rule / offered to the certificate (gnx_debug_counter(9 / 10))
 std::atomic<int64_t> g_cert_n{0}; // pairs certified whose read holds an N (gnx_debug_counter(11))
+std::atomic<int64_t> g_cert_edge{0}; // pairs certified by the edge rule graded on the end diagonals and by no older rule (gnx_debug_counter(14))
 std::atomic<int64_t> g_fpc_hit{0}, g_fpc_miss{0}; // run_device_fp calls that found their plans on the device / that uploaded them (gnx_debug_counter(12 / 13))
 
 // Fast path for batches of short-alpha global affine alignments (see fp_walk_kernel).  Returns GNX_OK, an error,
@@ -457,10 +458,10 @@ int run_device_fp(const gnx_params *prm, const KParams &kp, const TbParams &tp, 
     PairPlan *d_gpl = nullptr;
     bool gathered = false; // the certificate ran: d_gpl / d_live hold the live pairs
     if (cert) {
-        if ((rc = c.fp_cflag.ensure((size_t)(2 * np + 3) * 8))) return rc;
+        if ((rc = c.fp_cflag.ensure((size_t)(2 * np + 4) * 8))) return rc;
         if ((rc = c.fp_live.ensure((size_t)np * 4))) return rc;
         if ((rc = c.fp_gplans.ensure((size_t)np * sizeof(PairPlan)))) return rc;
-        d_cflag = reinterpret_cast<int64_t *>(c.fp_cflag.p); d_coff = d_cflag + np + 2; // [np] of the flags = the scan's carry word, [np + 1] = the certified reads that hold an N
+        d_cflag = reinterpret_cast<int64_t *>(c.fp_cflag.p); d_coff = d_cflag + np + 3; // [np] of the flags = the scan's carry word, [np + 1] = the certified reads that hold an N, [np + 2] = the pairs only the graded edge rule admits
         d_live = reinterpret_cast<int *>(c.fp_live.p);
         d_gpl = reinterpret_cast<PairPlan *>(c.fp_gplans.p);
     }
@@ -471,21 +472,22 @@ int run_device_fp(const gnx_params *prm, const KParams &kp, const TbParams &tp, 
         gnx_cert_matrix_init(&mx, sc64, (int64_t)(kp.o4 >> 2), (int64_t)(kp.e4 >> 2));
         g_cert_offered += np;
         if (!mx.ok) return GNX_OK; // no certificate under this matrix: everyone through the sweep (n_live = np), nothing launched
-        HIPCHK(hipMemsetAsync(d_cflag + np, 0, 16, st));
+        HIPCHK(hipMemsetAsync(d_cflag + np, 0, 24, st));
         auto kc = kp.b2 ? fp_cert_kernel<true> : fp_cert_kernel<false>;
         hipLaunchKernelGGL(kc, dim3((unsigned)np), dim3(64), 0, st, dpl, np, d_a, d_as, d_b, d_bs, kp, tp, mx, d_stage, CAP, d_score, d_nops, d_cflag, d_cflag + np + 1, d_err);
         HIPCHK(hipGetLastError());
         if ((rc = launch_scan(d_cflag, np, d_coff, d_cflag + np, st))) return rc;
         hipLaunchKernelGGL(fp_cert_gather_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, np, d_cflag, d_coff, dpl, d_live, d_gpl);
         HIPCHK(hipGetLastError());
-        int64_t nl[2] = {0, 0}; // the scan's carry word afterwards = the live pairs (the sweep's grid), and the N-rule exits beside it
-        HIPCHK(hipMemcpyAsync(nl, d_cflag + np, 16, hipMemcpyDeviceToHost, st));
+        int64_t nl[3] = {0, 0, 0}; // the scan's carry word afterwards = the live pairs (the sweep's grid), the N-rule exits and the graded edge rule's beside it
+        HIPCHK(hipMemcpyAsync(nl, d_cflag + np, 24, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         n_live = (int)nl[0];
         gathered = true;
-        g_cert_ok += np - n_live - nl[1];
+        g_cert_ok += np - n_live - nl[1] - nl[2];
         g_cert_n += nl[1];
-        if (getenv("GNX_DEBUG")) fprintf(stderr, "[gnx fp] gapless certificate: %d of %d pairs certified (%d of them hold an N), %d go through the sweep\n", np - n_live, np, (int)nl[1], n_live);
+        g_cert_edge += nl[2];
+        if (getenv("GNX_DEBUG")) fprintf(stderr, "[gnx fp] gapless certificate: %d of %d pairs certified (%d of them hold an N, %d by the graded edge rule only), %d go through the sweep\n", np - n_live, np, (int)nl[1], (int)nl[2], n_live);
         return GNX_OK;
     };
 
@@ -4216,7 +4218,7 @@ int gnx_debug_gapless_certificate(const gnx_params *p, const uint8_t *a, int64_t
     return GNX_OK;
 }
 
-/* the same with reads that hold N admitted (gnx_certn_decide: what fp_cert_kernel decides).  out[0..6) = certified (0 / 1), diagonal c, d*,
+/* the same with reads that hold N admitted (gnx_certn_decide: what fp_cert_kernel decides before its graded edge test).  out[0..6) = certified (0 / 1), diagonal c, d*,
  * score, whether the edge rule decided (-o < deficit < -2o), the read's N rows. */
 int gnx_debug_gapless_certificate_n(const gnx_params *p, const uint8_t *a, int64_t n, const uint8_t *b, int64_t m, int64_t K, int64_t *out) {
     g_err[0] = 0;
@@ -4237,12 +4239,40 @@ int gnx_debug_gapless_certificate_n(const gnx_params *p, const uint8_t *a, int64
     return GNX_OK;
 }
 
+/* the same through gnx_certe_decide: the old rule, then the edge rule graded by the bytes on diagonals 0 and m - n where the old one fails at
+ * its corners.  out[0..8) = the _n entry's six fields, admitted by the graded test only (0 / 1), the largest grade j at which the K-run
+ * bounds alone would have refused (-1: none). */
+int gnx_debug_gapless_certificate_edge(const gnx_params *p, const uint8_t *a, int64_t n, const uint8_t *b, int64_t m, int64_t K, int64_t *out) {
+    g_err[0] = 0;
+    if (!getenv("GNX_DEBUG_ENTRY")) { set_err("gnx_debug_gapless_certificate_edge is a test hook: set GNX_DEBUG_ENTRY=1%s", ""); return GNX_EINVAL; }
+    KParams kp; TbParams tp; bool affine, local, lowmem;
+    int rc = check_params(p, kp, tp, affine, local, lowmem);
+    if (rc) return rc;
+    if (!a || !b || !out || n < 1 || m < 1 || K < 1 || !affine || local) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    for (int x = 0; x < 8; x++) out[x] = 0;
+    out[7] = -1;
+    GnxCertMatrix mx;
+    gnx_cert_matrix_init(&mx, p->scores, p->gap_open, p->gap_extend);
+    int64_t c = 0, ds = 0, sc = 0, edge = 0, nu = 0, by_edge = 0, jdec = -1;
+    for (int64_t j = 0; j < m; j++) if (b[j] >= 5) return GNX_OK;
+    if (m < n + 2 || K > n || !gnx_cert_scan_naive(a, n, b, m, K, &c)) return GNX_OK;
+    if (c <= 0 || c >= m - n) return GNX_OK;
+    if (!gnx_certe_decide(&mx, a, n, b + c, b, b + (m - n), m, c, K, tp.ci, tp.cj, 1, &ds, &sc, &edge, &nu, &by_edge, &jdec)) return GNX_OK;
+    out[0] = 1; out[1] = c; out[2] = ds; out[3] = sc; out[4] = edge; out[5] = nu; out[6] = by_edge; out[7] = jdec;
+    return GNX_OK;
+}
+
 /* diagnostics: counters kept on context 0's device.  which = 0: items of piped launches that were run by a workgroup other than
  * their own since the last reset (claim_items: the abnormal path the tests force); reset != 0 zeroes it after reading. */
 int gnx_debug_counter(int which, int reset, int64_t *out) {
     ApiCall api;
     CtxScope sc(ctx_at(0));
-    if (which < 0 || which > 13 || !out) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (which < 0 || which > 14 || !out) { set_err("bad argument%s", ""); return GNX_EINVAL; }
+    if (which == 14) { // the gapless certificate: pairs that only the edge rule graded on the end diagonals admitted
+        *out = g_cert_edge.load();
+        if (reset) g_cert_edge = 0;
+        return GNX_OK;
+    }
     if (which >= 12) { // the fast path's plan cache: calls that took the cached branch / that built and uploaded their plans
         std::atomic<int64_t> &v = which == 12 ? g_fpc_hit : g_fpc_miss;
         *out = v.load();

@@ -782,7 +782,9 @@ int gnx_debug_occupy(int n_workgroups, int milliseconds); /* refused with GNX_EI
  * which = 5 / 6: rows per lane / snapshot spacing of the last 64-lane affine sweep (bench.py prices its design bytes with them).
  * which = 7 / 8: reads gnx_seed_candidates voted with the table in LDS / in a slab of device memory.
  * which = 9 / 10: pairs the fast path's gapless certificate certified by its N-free rule (they skipped sweep and walk) / pairs offered
- * to it.  which = 11: pairs it certified whose read holds an N (counted in the kernel; 9 + 11 = all certified pairs).
+ * to it.  which = 11: pairs it certified whose read holds an N (counted in the kernel).
+ * which = 14: pairs that only the edge rule graded on the end diagonals certified (9 + 11 + 14 = all certified pairs; 9 and 11 keep
+ * counting what the older rules admit).
  * which = 12 / 13: fast-path calls that found the plans of the previous call on the device (equal lengths) / that built and uploaded
  * their plans.
  * reset != 0 zeroes the counter after reading (3 and 4 together). */
@@ -800,10 +802,15 @@ int gnx_debug_fill_scratch(uint32_t pattern, int64_t *out_buffers, int64_t *out_
  * the window's last columns), the score.  A window that holds a byte >= 5 is never certified (the kernel raises the sweep's error for
  * it).  Refused with GNX_EINVAL unless the process runs with GNX_DEBUG_ENTRY=1. */
 int gnx_debug_gapless_certificate(const gnx_params *p, const uint8_t *a, int64_t n, const uint8_t *b, int64_t m, int64_t K, int64_t *out);
-/* The same with reads that hold N admitted, as the kernel decides ("Reads that hold N"): the 16-mers that hold an N
+/* The same with reads that hold N admitted (the kernel's rule before its graded edge test; DESIGN.md 4.22, "Reads that hold N"): the 16-mers that hold an N
  * are left out of the scan, an N row counts beside the imperfect rows in the thresholds.  out[0 .. 6) = certified (0 / 1), c, d*, the
  * score, whether the edge rule decided (-o < deficit < -2o), the number of N in the read.  Same conditions as above. */
 int gnx_debug_gapless_certificate_n(const gnx_params *p, const uint8_t *a, int64_t n, const uint8_t *b, int64_t m, int64_t K, int64_t *out);
+/* The same with the edge rule graded by the known end diagonals, as the kernel decides ("The edge rule on the known end
+ * diagonals"): the rule above, then, where it fails at the edge rule's corners only, corners bounded by the window's real bytes on its
+ * first and last columns.  out[0 .. 8) = the six fields above, admitted by the graded test only (0 / 1), the largest grade j at which
+ * the bounds without the bytes would have refused (-1: none, or not admitted by the graded test).  Same conditions as above. */
+int gnx_debug_gapless_certificate_edge(const gnx_params *p, const uint8_t *a, int64_t n, const uint8_t *b, int64_t m, int64_t K, int64_t *out);
 
 /* ---- "next" row N1: chunk and multiple-alignment variants (what cmd/faChunkAlign and popgen/dunn.go run) ---- */
 /* align.AffineGapChunk (/root/reference/align/affineGap_highMem.go:227-268): the affine DP over chunks of chunk_size
